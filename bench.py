@@ -7,7 +7,14 @@ N = 100 000 nodes, 100-NN geometric graph (Morton order), T = 1024, F_in = 64, r
 K = 4  ->  D_out = 320, 131 GB of output, 157 GB resident.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload target|c1|c2|c3|c4|c5|small|random|smallrand]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the steps and prints the line (``ms_per_step`` = milliseconds of one timed
+step).  ``--full`` adds what takes work of its own after the timed steps: the check of the timed output against the
+exact-fp32 CSR kernel and the CPU oracle, the exact-fp32 hop line and the CPU baseline.  ``--dump-outputs DIR``
+writes what the last timed step computed as ``DIR/*.npy`` (``dump_outputs``); inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 With N > 1 the SAME graph is node-partitioned across the ranks (strong scaling): reservoir
 local, one all_to_all of halo rows per hop over RCCL.  Rank 0 prints ONE JSON line.  Started
@@ -21,6 +28,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -93,6 +101,32 @@ def build_graph(w):
 def hop_bytes(n, t, d, nnz):
     """Algorithmic HBM bytes of one hop: X read once, Y written once, CSR once."""
     return 2 * n * t * d * 4 + nnz * 8 + (n + 1) * 4
+
+
+DUMP_BYTES = 48 * 10**6        # --dump-outputs writes about this much at most (the option promises 64 MB)
+
+
+def dump_outputs(path, out, n_t, t_first=0, order=None, seed=0):
+    """``--dump-outputs``: what the last timed step left in ``out`` -- its first ``n_t`` time steps, which are steps
+    ``t_first ..`` of the sequence (the last time chunk when the embedding is produced in chunks) -- as float32 ``.npy``
+    files under ``path``, nodes in the caller's numbering (``order[i]`` = node of row i; None: row i is node i).
+    ``embedding.npy`` [n_t, N, D] when that fits in DUMP_BYTES; otherwise a fixed sample of (step, node) rows drawn
+    with a seeded generator: ``embedding_rows.npy`` [S, D] and ``embedding_rows_index.npy`` [S, 2] (sequence step,
+    node; float64) -- the same rows for the same arguments, so two builds compare row for row."""
+    os.makedirs(path, exist_ok=True)
+    n, d = out.shape[1], out.shape[2]
+    row = torch.arange(n)                                  # node -> row of out
+    if order is not None:
+        row[order.long()] = torch.arange(n)
+    if n_t * n * d * 4 <= DUMP_BYTES:
+        emb = out[:n_t] if order is None else out[:n_t, row.to(out.device)]
+        np.save(os.path.join(path, "embedding.npy"), emb.cpu().numpy())
+        return
+    s = DUMP_BYTES // (d * 4 + 16)
+    flat = torch.unique(torch.randint(0, n_t * n, (s,), generator=torch.Generator().manual_seed(seed)))  # sorted
+    t, node = flat // n, flat % n
+    np.save(os.path.join(path, "embedding_rows.npy"), out[t.to(out.device), row[node].to(out.device)].cpu().numpy())
+    np.save(os.path.join(path, "embedding_rows_index.npy"), torch.stack([t + t_first, node], 1).double().numpy())
 
 
 def cpu_model():
@@ -185,7 +219,7 @@ def RESERVOIR_ARITHMETIC(R, F, N=None, activation="tanh"):
 HOP_ARITHMETIC = {
     "spmm_split": "operands as two fp16 pieces of the scaled value (22 bits), products hi*hi + hi*lo + lo*hi on "
                   "v_mfma_f32_16x16x32_f16, fp32 accumulation; max |error| vs fp64 ~1e-7 of the operand scale "
-                  "(tests/test_gpu_split.py); the exact-fp32 kernel is timed in roofline_exact_fp32",
+                  "(tests/test_gpu_split.py); the exact-fp32 kernel is timed in roofline_exact_fp32 (--full)",
 }
 
 
@@ -329,16 +363,29 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="target", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check the timed output, time the exact-fp32 hop kernel and "
+                         "measure the CPU baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/*.npy (float32, at most 64 MB: a fixed, "
+                         "seeded sample of rows when the embedding is larger)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the check of the timed output (sampled steps of every hop block against the "
+                    help="--full: skip the check of the timed output (sampled steps of every hop block against the "
                          "generic CSR kernel on the block it read, first steps against the CPU oracle)")
     ap.add_argument("--no-exact-line", action="store_true",
-                    help="skip timing the exact-fp32 hop kernel next to the default (split-fp16) one")
+                    help="--full: skip timing the exact-fp32 hop kernel next to the default (split-fp16) one")
     ap.add_argument("--t-steps", type=int, default=0,
                     help="override the workload's number of time steps (functional tests of the big "
                          "configurations on a small box; the record says so)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    verify = args.full and not args.no_verify
+    exact_line = args.full and not args.no_exact_line
+    cpu_base = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         hip.require_gpu()
@@ -497,8 +544,11 @@ def main():
             torch.save(out.cpu(), os.path.join(dump, f"out_w{world}_r{rank}.pt"))
         if order is not None and rank == 0:
             torch.save(dict(order=order, bounds=bounds), os.path.join(dump, f"order_w{world}.pt"))
+    if args.dump_outputs:
+        t_last = (T - 1) // tc * tc                      # first step of the last time chunk
+        dump_outputs(args.dump_outputs, out, T - t_last, t_last, order)
     verify_multi = None
-    if world > 1 and spatial is not None and not args.no_verify:
+    if world > 1 and spatial is not None and verify:
         verify_multi = verify_partitioned(enc, ops, spatial, x, out, state, w, T, tc, bounds, order, rank, world, backend, dev)
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -557,7 +607,7 @@ def main():
                                "launches_timed": len(all_ms),
                                "arithmetic": HOP_ARITHMETIC.get(kernel, "exact fp32 products (fp32 MFMA / FMA)")}
             exact_bts = bts / pieces if pieces > 1 else bts
-            want_exact_line = kernel == "spmm_split" and not args.no_exact_line
+            want_exact_line = kernel == "spmm_split" and exact_line
         elif timeline:
             # rank 0's GPU: a hop of the local block = its launches over the time chunks; the
             # exchange of a hop = gather + all_to_all on the communication stream
@@ -588,7 +638,7 @@ def main():
                                         "under the SpMM of the previous time chunk; the reservoir of "
                                         "the next time piece runs under both (third stream)"}
         # the timed output is verified BEFORE anything else writes to it (the exact-fp32 line below overwrites hop slot 1)
-        if world == 1 and spatial is None and not args.no_verify:
+        if world == 1 and spatial is None and verify:
             rec["verify"] = verify_output(enc, ops, x, out, w, T, tc, d_h)
             rec["verified"] = bool(rec["verify"]["ok"])
         if verify_multi is not None:
@@ -596,7 +646,7 @@ def main():
             rec["verified"] = bool(verify_multi["ok"])
         if hop_ms and want_exact_line:
             rec["roofline_exact_fp32"] = exact_hop_line(ops[0], out, d_h, exact_bts)
-        if not args.no_cpu_baseline and world == 1:
+        if cpu_base and world == 1:
             rec["cpu_baseline"] = cpu_baseline(w, ei, ew)
         os.write(json_fd, (json.dumps(rec) + "\n").encode())
     if dist.is_initialized():

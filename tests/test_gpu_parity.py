@@ -994,7 +994,7 @@ def test_bench_two_ranks_share_one_gpu_matches_single_rank(tmp_path):
     # the driver's command form: no launcher, bench.py starts its own ranks (they share this
     # box's single GPU over gloo when fewer than 2 devices are visible)
     two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                          "--workload", "small", "--steps", "1", "--warmup", "0"],
+                          "--workload", "small", "--steps", "1", "--warmup", "0", "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert two.returncode == 0, two.stderr[-2000:]
     lines = [l for l in two.stdout.splitlines() if l.startswith("{")]
@@ -1020,6 +1020,34 @@ def _run_bench(args, env, timeout=1500):
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_are_the_timed_output(tmp_path):
+    """--dump-outputs writes what the last timed step computed: for the small workload (393 MB of embedding) a seeded
+    sample of rows equal to those rows of the output the run left behind, the same in a --full run; for a
+    configuration under 64 MB the whole embedding.  A plain run does none of --full's work."""
+    env = dict(os.environ, SGP_BENCH_DUMP=str(tmp_path))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SGP_BENCH_BACKEND"):
+        env.pop(k, None)
+    base = ["--workload", "small", "--steps", "2", "--warmup", "1"]
+    plain = _run_bench(base + ["--dump-outputs", str(tmp_path / "a")], env)
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0
+    assert not {"verify", "verified", "roofline_exact_fp32", "cpu_baseline"} & set(plain)
+    out = torch.load(tmp_path / "out_w1_r0.pt")
+    rows = np.load(tmp_path / "a" / "embedding_rows.npy")
+    idx = torch.from_numpy(np.load(tmp_path / "a" / "embedding_rows_index.npy")).long()
+    assert rows.dtype == np.float32 and rows.shape == (idx.shape[0], out.shape[2]) and idx.shape[0] > 10000
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 * 10**6
+    assert torch.equal(torch.from_numpy(rows), out[idx[:, 0], idx[:, 1]])
+    full = _run_bench(base + ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "b")], env)
+    assert full["verified"] is True and "cpu_baseline" not in full
+    assert full["roofline"]["kernel"] != "spmm_split" or "roofline_exact_fp32" in full
+    assert np.array_equal(np.load(tmp_path / "b" / "embedding_rows_index.npy"), idx.numpy())
+    close(np.load(tmp_path / "b" / "embedding_rows.npy"), rows, rtol=1e-6, atol=1e-6)
+    _run_bench(["--workload", "c1", "--t-steps", "64", "--steps", "1", "--warmup", "0",
+                "--dump-outputs", str(tmp_path / "c")], env)
+    emb = np.load(tmp_path / "c" / "embedding.npy")
+    assert emb.dtype == np.float32 and torch.equal(torch.from_numpy(emb), torch.load(tmp_path / "out_w1_r0.pt"))
 
 
 @pytest.mark.parametrize("exchange", ["auto", "gather"])

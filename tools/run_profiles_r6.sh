@@ -9,11 +9,11 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 for w in ${@:-target}; do
   steps=3; [ $w = c5 ] && steps=1
-  timeout 600 python bench.py --workload $w --steps $steps --warmup 1 > $OUT/bench_${w}_line.json 2> $OUT/bench_$w.err
+  timeout 600 python bench.py --workload $w --steps $steps --warmup 1 --full > $OUT/bench_${w}_line.json 2> $OUT/bench_$w.err
   P=$ROOTD/gpurun_out/prof_r6_$w
   mkdir -p $P
   ( cd /tmp
-    timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d $P/trace -o t -- python $ROOTD/bench.py --workload $w --steps 2 --warmup 1 --no-cpu-baseline --no-verify > $P/trace.log 2>&1
+    timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d $P/trace -o t -- python $ROOTD/bench.py --workload $w --steps 2 --warmup 1 --full --no-cpu-baseline --no-verify > $P/trace.log 2>&1
     timeout 400 rocprofv3 --output-format csv --pmc FETCH_SIZE TCC_HIT_sum -d $P/pmc_fetch -o p -- python $ROOTD/bench.py --workload $w --steps 2 --warmup 1 --no-cpu-baseline --no-verify --no-exact-line > $P/pmc_fetch.log 2>&1
     timeout 400 rocprofv3 --output-format csv --pmc WRITE_SIZE TCC_MISS_sum -d $P/pmc_write -o p -- python $ROOTD/bench.py --workload $w --steps 2 --warmup 1 --no-cpu-baseline --no-verify --no-exact-line > $P/pmc_write.log 2>&1 )
   python tools/summarize_prof.py $P > $P/summary.txt 2>&1
