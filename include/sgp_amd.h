@@ -572,6 +572,54 @@ int sgp_grouped_linear_wgrad_f32(const float* X, int64_t x_row_stride, int64_t x
                                  int32_t n_rows, int32_t groups, int32_t ic, int32_t oc,
                                  sgp_stream_t stream);
 
+/* ---------------------------------------------------------- Ridge readout ---
+ * The closed-form baseline's readout (experiments/run_closed_form.py:169-247): sklearn Ridge(alpha) fitted once per
+ * lag on a host copy of [data | encoded_x].  Here the design matrix is VIRTUAL and never materialised: row
+ * r = s * n_nodes + n (s < n_steps) is node n at step steps[s] (int32, device, any order), and its columns are up to 8
+ * SEGMENTS laid side by side.  `segs` is a HOST table of n_segs x 6 int64:
+ *   (device pointer, step stride, node stride, width, step offset, reps)
+ * and column q * width + c of a segment (c < width, q < reps) is
+ *   base[(steps[s] + offset + q) * step_stride + n * node_stride + c]
+ * (fp32; node stride 0 broadcasts a global [T, c] series over the nodes; offset 1 with reps H is the target of lags
+ * 1 .. H as one segment).  The caller guarantees
+ * that every steps[s] + offset addresses a step of the tensor (sgp_amd/readout.py checks it before any device work).
+ * All reductions are fp64 in a fixed order, without atomics: results are bit-identical run to run.
+ *
+ * Workspace sizes (bytes, -1 on a bad size): which = 0 colmeans, 1 Gram (n_cols counts the ones column), 2 predict
+ * (n_out = horizon x channels).  n_rows = n_steps x n_nodes. */
+int64_t sgp_ridge_workspace_bytes(int32_t which, int64_t n_rows, int32_t n_cols, int32_t n_out);
+
+/* means[c] = column means of the virtual matrix (fp64; the fp32 values are summed in fp64).
+ *   replaces the centring inside sklearn Ridge.fit (run_closed_form.py:195, _preprocess_data) */
+int sgp_ridge_colmeans_f32(const int64_t* segs, int32_t n_segs, const int32_t* steps, int64_t n_steps,
+                           int64_t n_nodes, double* means, void* work, int64_t work_bytes, sgp_stream_t stream);
+
+/* gram[i * ldg + j] (fp64, both triangles) = Zc^T Zc for Zc = [Z - shift | 1]: shift[c] (fp32, device; NULL = no
+ * shift) is subtracted in fp32, the ones column is appended when ones = 1.  EXACT-FP32 contract: the products are
+ * v_mfma_f32_32x32x2_f32 (one fp32 rounding per product-add, no reduced-precision inputs) over at most 256 rows, and
+ * each such partial is added into fp64.  Only upper-triangle 128 x 128 tiles are computed.
+ *   replaces the X^T X + X^T y of the 12 Ridge.fit calls at run_closed_form.py:191-196 (one Gram for every lag: the
+ *   targets are columns of the same matrix) */
+int sgp_ridge_gram_f32(const int64_t* segs, int32_t n_segs, const int32_t* steps, int64_t n_steps, int64_t n_nodes,
+                       const float* shift, int32_t ones, double* gram, int64_t ldg, void* work, int64_t work_bytes,
+                       sgp_stream_t stream);
+
+/* One pass over the rows for all H x C outputs: yhat = X W + b with W [D, H*C] (fp32, column l * C + c = lag l + 1,
+ * channel c) held in LDS and b [H*C] fp64; products v_mfma_f32_16x16x4_f32 over 64-column partials added in fp64.
+ * scale / bias (NULL = none; element (n, c) at n * sc_node_stride + c) apply tsl's inverse_transform
+ * yhat * (scale + 5e-8) + bias.  With y (raw target, (t, n, c) at t * y_ss + n * y_ns + c) the masked sums of tsl's
+ * numpy_metrics against the target at step steps[s] + l + 1 and mask (uint8, NULL = all valid) go to sums[H][4] =
+ * (sum |e|, sum e^2, sum |e / (y + 5e-8)|, count).  yhat [S, H, N, C] fp32 is written when not NULL.
+ * SGP_EUNSUP when W does not fit in LDS (D rounded up to 32, times H*C rounded up to 16, times 4 bytes, plus about
+ * 8 KiB + 512 bytes per output column within 160 KiB); H * C <= 64.
+ *   replaces Ridge.predict + inverse_transform + masked_mae / mse / mape of run_closed_form.py:199-247 */
+int sgp_ridge_predict_score_f32(const int64_t* segs, int32_t n_segs, const int32_t* steps, int64_t n_steps,
+                                int64_t n_nodes, const float* W, const double* b, int32_t horizon, int32_t channels,
+                                const float* scale, const float* bias, int64_t sc_node_stride,
+                                const float* y, int64_t y_ss, int64_t y_ns,
+                                const uint8_t* mask, int64_t m_ss, int64_t m_ns, int64_t m_cs,
+                                float* yhat, double* sums, void* work, int64_t work_bytes, sgp_stream_t stream);
+
 
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were

@@ -6,6 +6,7 @@ from . import dataloader, datasets, hip
 from .graph import ShiftOperator
 from .nn.encoders import GESNEncoder, SGPEncoder, SGPSpatialEncoder, SGPTemporalEncoder
 from .nn.reservoir import GESNLayer, GraphESN, Reservoir, ReservoirLayer
+from .readout import RidgeReadout, closed_form_readout
 from .sgp_preprocessing import (preprocess_adj, preprocess_dataset, reservoir_preprocessing_,
                                 sgp_spatial_embedding, sgp_spatial_support)
 from .utils import encode_dataset, self_normalizing_activation

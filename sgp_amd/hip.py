@@ -142,6 +142,12 @@ SIGNATURES = {
                                              c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_p]),
     "sgp_spmm_colblock_rows_cap": (c_i32, []),
     "sgp_spmm_colblock_round_pad": (c_i32, []),
+    "sgp_ridge_workspace_bytes": (c_i64, [c_i32, c_i64, c_i32, c_i32]),
+    "sgp_ridge_colmeans_f32": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p]),
+    "sgp_ridge_gram_f32": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_i64, c_p, c_i32, c_p, c_i64, c_p, c_i64, c_p]),
+    "sgp_ridge_predict_score_f32": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i32, c_i32,
+                                                   c_p, c_p, c_i64, c_p, c_i64, c_i64,
+                                                   c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p]),
     "sgp_event_create": (ctypes.c_int, [ctypes.POINTER(c_p)]),
     "sgp_event_destroy": (ctypes.c_int, [c_p]),
     "sgp_event_record": (ctypes.c_int, [c_p, c_p]),
@@ -953,3 +959,58 @@ class Event:
             load().sgp_event_destroy(self._h)
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------- ridge readout (sgp_amd/readout.py)
+def _ridge_table(segs):
+    """[(tensor, step_stride, node_stride, width, step_offset, reps)] -> the host int64 table of include/sgp_amd.h."""
+    tab = (ctypes.c_int64 * (6 * len(segs)))()
+    for k, (t, ss, ns, width, off, reps) in enumerate(segs):
+        tab[6 * k:6 * k + 6] = [t.data_ptr(), ss, ns, width, off, reps]
+    return tab
+
+
+def ridge_workspace(which, n_rows, n_cols, n_out, device):
+    nbytes = load().sgp_ridge_workspace_bytes(which, n_rows, n_cols, n_out)
+    if nbytes < 0:
+        raise ValueError(f"ridge readout: no workspace for {n_rows} rows x {n_cols} columns")
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+@_on_device
+def ridge_colmeans(segs, steps, n_nodes, means):
+    lib = require_gpu()
+    ncols = sum(s[3] * s[5] for s in segs)
+    ws = ridge_workspace(0, steps.numel() * n_nodes, ncols, 0, steps.device)
+    _check(lib.sgp_ridge_colmeans_f32(_ridge_table(segs), len(segs), steps.data_ptr(), steps.numel(), n_nodes,
+                                      means.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(steps)),
+           "sgp_ridge_colmeans_f32")
+    return means
+
+
+@_on_device
+def ridge_gram(segs, steps, n_nodes, shift, ones, gram):
+    lib = require_gpu()
+    mp = sum(s[3] * s[5] for s in segs) + int(ones)
+    ws = ridge_workspace(1, steps.numel() * n_nodes, mp, 0, steps.device)
+    _check(lib.sgp_ridge_gram_f32(_ridge_table(segs), len(segs), steps.data_ptr(), steps.numel(), n_nodes,
+                                  shift.data_ptr() if shift is not None else None, int(ones), gram.data_ptr(),
+                                  gram.stride(0), ws.data_ptr(), ws.numel() * 8, _stream(steps)),
+           "sgp_ridge_gram_f32")
+    return gram
+
+
+@_on_device
+def ridge_predict_score(segs, steps, n_nodes, w, b, horizon, channels, scale=None, bias=None, sc_node_stride=0,
+                        y=None, mask=None, yhat=None, sums=None):
+    """``y`` / ``mask``: [T, N, C] views (mask uint8, its channel axis may be broadcast with stride 0)."""
+    lib = require_gpu()
+    ws = ridge_workspace(2, steps.numel() * n_nodes, sum(s[3] * s[5] for s in segs), horizon * channels, steps.device)
+    P = lambda t: t.data_ptr() if t is not None else None
+    ys = (y.stride(0), y.stride(1)) if y is not None else (0, 0)
+    ms = (mask.stride(0), mask.stride(1), mask.stride(2)) if mask is not None else (0, 0, 0)
+    _check(lib.sgp_ridge_predict_score_f32(_ridge_table(segs), len(segs), steps.data_ptr(), steps.numel(), n_nodes,
+                                           w.data_ptr(), b.data_ptr(), horizon, channels,
+                                           P(scale), P(bias), sc_node_stride, P(y), *ys, P(mask), *ms,
+                                           P(yhat), P(sums), ws.data_ptr(), ws.numel() * 8, _stream(steps)),
+           "sgp_ridge_predict_score_f32")
