@@ -621,6 +621,65 @@ int sgp_ridge_predict_score_f32(const int64_t* segs, int32_t n_segs, const int32
                                 float* yhat, double* sums, void* work, int64_t work_bytes, sgp_stream_t stream);
 
 
+/* ------------------------------------------------ Decoder MLP and readout -----
+ * The trained layers of SGPModel after its input layer (decoder_mlp.hip), forward and backward.  EXACT-FP32
+ * contract: every product is a v_mfma_f32_16x16x4_f32 (no reduced-precision inputs).
+ *
+ * Packed weights: the matrix M[n_out, k] of a layer (transpose = 0: M[j][i] = w[j * w_row_stride + i], an nn.Linear
+ * weight; transpose = 1: M[j][i] = w[i * w_row_stride + j], its transpose for dX) in the fragment order of the dense
+ * kernel, sgp_dense_packed_floats(n_out, k) floats, 16-byte aligned. */
+int64_t sgp_dense_packed_floats(int32_t n_out, int32_t k);
+int sgp_dense_pack_f32(const float* w, int64_t w_row_stride, int32_t transpose, int32_t n_out, int32_t k,
+                       float* packed, sgp_stream_t stream);
+
+/* out = epilogue(X M^T) over n_rows rows.  Row r of X is X[src(r) * x_row_stride + 0 .. k-1] with
+ * src(r) = gather[r % row_mod] (gather != NULL; row_mod = 0: r) or r % row_mod (gather == NULL).  Epilogue of
+ * column c < n_out, v = (X M^T)[r, c] (+ bias[c]):
+ *   dmode = 0, c < n_act:  pre[r * pre_row_stride + c] = v (pre != NULL);  v = act(v) * keep(r, c)
+ *   dmode = 1, c < n_act:  v = v * act'(dpre[r * dpre_row_stride + c]) * keep(r, c)      (the backward pass)
+ *   then v += add[r * add_row_stride + c] (add != NULL), stored at
+ *   out[(r / m0) m1 + (r % m0) m2 + (c / m3) m4 + (c % m3) m5] with out_map = {m0, .., m5} (host array).
+ * act: 0 linear, 1 relu, 2 silu; keep(r, c) = the Philox dropout factor of decoder.hip at flat index
+ * r * drop_width + c (1 when dropout_p = 0, 0 when dropout_p = 1).
+ *   replaces nn.Linear + activation + Dropout of tsl Dense (tsl/nn/base/dense.py:19-23), the stacked Linear1 / skip
+ *   of ResidualMLP (tsl/nn/blocks/encoders/mlp.py:86-111), lin_emb + the positional add (sgp_model.py:76,97), the
+ *   readout and its Rearrange (tsl/nn/blocks/decoders/linear_readout.py:23-26), and every dX of their backward */
+int sgp_dense_f32(const float* X, int64_t x_row_stride, const int32_t* gather, int64_t row_mod,
+                  const float* w_packed, const float* bias, int32_t n_rows, int32_t k, int32_t n_out,
+                  int32_t act, int32_t n_act, int32_t dmode, const float* dpre, int64_t dpre_row_stride,
+                  float* pre, int64_t pre_row_stride, double dropout_p, uint64_t seed, int64_t drop_width,
+                  const float* add, int64_t add_row_stride,
+                  float* out, const int64_t* out_map, sgp_stream_t stream);
+
+/* dw[o * dw_row_stride + i] = sum_r dZ[r * dz_row_stride + o] * X_row(r)[i] and (db != NULL) db[o] = sum_r dZ[r, o],
+ * X_row as in sgp_dense_f32.  Row slices write partials into `work` (sgp_dense_wgrad_workspace_floats floats,
+ * with_bias = db != NULL), added in slice order in fp64: no float atomics, bit-identical from run to run.
+ *   replaces the weight / bias gradients autograd forms for every nn.Linear of the decoder */
+int64_t sgp_dense_wgrad_workspace_floats(int64_t n_rows, int32_t n_out, int32_t k, int32_t with_bias);
+int sgp_dense_wgrad_f32(const float* dZ, int64_t dz_row_stride, const float* X, int64_t x_row_stride,
+                        const int32_t* gather, int64_t row_mod, int32_t n_rows, int32_t n_out, int32_t k,
+                        float* dw, int64_t dw_row_stride, float* db, float* work, int64_t work_floats,
+                        sgp_stream_t stream);
+
+/* out[n_seg, width] = per-node sums of the rows of g, in a fixed order (fp64):
+ *   perm == NULL: out[n] = sum_b g[b * n_seg + n]   (n_rows a multiple of n_seg)
+ *   otherwise keys = the rows' node ids stably sorted, perm = the row of each sorted position; out[keys[p]] = sum of
+ *   g[perm[p]] over the run of p (nodes without rows: 0).
+ *   replaces the node_emb.emb gradient of the embedding lookup (tsl/nn/base/embedding.py:93, sgp_model.py:97) */
+int sgp_row_segsum_f32(const float* g, int64_t g_row_stride, int64_t n_rows, int32_t width,
+                       const int32_t* perm, const int32_t* keys, int32_t n_seg, float* out, sgp_stream_t stream);
+
+/* loss[0] = sum of |y_hat - y| over the counted elements / their number (count[0], fp64; 0 when nothing counts, as
+ * tsl's MaskedMetric.compute), one workgroup, fp64
+ * sums: element e counts when mask[e] != 0 (mask != NULL) and, with mask_nans, when |y_hat - y| is not NaN.
+ * grad[e] = grad_out[0] / count[0] * sign(y_hat - y) on the counted elements, 0 elsewhere.
+ *   replaces MaskedMAE (tsl/nn/metrics/metric_base.py:79-96, metric_fn = F.l1_loss(reduction='none')) */
+int sgp_masked_mae_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t n, int32_t mask_nans,
+                       float* loss, double* count, sgp_stream_t stream);
+int sgp_masked_mae_bwd_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t n, int32_t mask_nans,
+                           const float* grad_out, const double* count, float* grad, sgp_stream_t stream);
+
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

@@ -11,6 +11,7 @@
 // k order inside every 16-block permuted to (4 q + s) so that a lane's 16-byte load of its row
 // IS the B operand of 4 consecutive MFMAs (the same trick as the reservoir kernel).
 #include "common.h"
+#include "decoder_ops.h"
 
 using sgp::f32x4;
 
@@ -50,30 +51,6 @@ struct GlArgs {
     unsigned seed_lo, seed_hi;        // Philox word >= drop_thresh = p * 2^32, scaled by keep_scale = 1 / (1 - p);
     float keep_scale;                 // drop_thresh == 0: no dropout (eval mode / p = 0)
 };
-
-// Philox4x32-10 keyed by the call's seed, counter = flat element index (row * width + column): the
-// backward pass recomputes the mask from (seed, index) instead of storing it.
-__device__ __forceinline__ unsigned philox_word(unsigned long long idx, unsigned k0, unsigned k1) {
-    unsigned c0 = (unsigned)idx, c1 = (unsigned)(idx >> 32), c2 = 0x53475021u, c3 = 0u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
-__device__ __forceinline__ float keep_factor(unsigned long long idx, unsigned thresh, unsigned k0, unsigned k1, float scale) {
-    if (thresh == 0u) return 1.f;
-    return philox_word(idx, k0, k1) >= thresh ? scale : 0.f;
-}
-
-__device__ __forceinline__ float activate(float v, int act) {
-    if (act == 1) return fmaxf(v, 0.f);                                   // relu
-    if (act == 2) return v * __builtin_amdgcn_rcpf(1.f + __expf(-v));     // silu = x * sigmoid(x)
-    return v;
-}
 
 // One wave = 16 rows x one group (blockIdx.y).  JTC output tiles (16 channels each) are accumulated
 // together so that every row piece is loaded once; the row pieces of 8 k-blocks are requested
@@ -164,12 +141,6 @@ __global__ __launch_bounds__(64) void grouped_linear(GlArgs a) {
 //                                                                    packed as a [groups*ic, oc] weight
 //   dW[g*oc + o, i]   = sum_row dz[row, g*oc + o] x[row, g*ic + i] (wgrad_kernel below)
 //   db[g*oc + o]      = sum_row dz[row, g*oc + o]                  (column sums: sgp_node_mean_bcast_f32)
-__device__ __forceinline__ float dactivate(float z, int act) {
-    if (act == 1) return z > 0.f ? 1.f : 0.f;
-    if (act == 2) { const float sg = __builtin_amdgcn_rcpf(1.f + __expf(-z)); return sg * (1.f + z * (1.f - sg)); }
-    return 1.f;
-}
-
 __global__ __launch_bounds__(256) void dact_kernel(const float* __restrict__ dy, long long dyrs,
                                                    const float* __restrict__ pre, float* __restrict__ dz,
                                                    long long n_rows, int width, int act,
@@ -245,13 +216,6 @@ __global__ __launch_bounds__(64) void wgrad_kernel(WgArgs a) {
 }
 
 }  // namespace
-
-static void set_dropout(unsigned& thresh, unsigned& k0, unsigned& k1, float& scale, double p, uint64_t seed) {
-    double t = p * 4294967296.0;
-    thresh = p > 0.0 ? (unsigned)(t < 1.0 ? 1.0 : (t > 4294967295.0 ? 4294967295.0 : t)) : 0u;
-    k0 = (unsigned)seed; k1 = (unsigned)(seed >> 32);
-    scale = (float)(1.0 / (1.0 - p));
-}
 
 extern "C" {
 

@@ -148,6 +148,17 @@ SIGNATURES = {
     "sgp_ridge_predict_score_f32": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i32, c_i32,
                                                    c_p, c_p, c_i64, c_p, c_i64, c_i64,
                                                    c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p]),
+    "sgp_dense_packed_floats": (c_i64, [c_i32, c_i32]),
+    "sgp_dense_pack_f32": (ctypes.c_int, [c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p]),
+    "sgp_dense_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i32, c_i32, c_i32,
+                                     c_i32, c_i32, c_i32, c_p, c_i64, c_p, c_i64, c_f64, c_u64, c_i64,
+                                     c_p, c_i64, c_p, c_p, c_p]),
+    "sgp_dense_wgrad_workspace_floats": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "sgp_dense_wgrad_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_i32,
+                                           c_p, c_i64, c_p, c_p, c_i64, c_p]),
+    "sgp_row_segsum_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i32, c_p, c_p, c_i32, c_p, c_p]),
+    "sgp_masked_mae_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p]),
+    "sgp_masked_mae_bwd_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p]),
     "sgp_event_create": (ctypes.c_int, [ctypes.POINTER(c_p)]),
     "sgp_event_destroy": (ctypes.c_int, [c_p]),
     "sgp_event_record": (ctypes.c_int, [c_p, c_p]),
@@ -935,6 +946,114 @@ def grouped_linear_wgrad(x2, dz, groups, ic, oc, step_index=None, node_index=Non
     _check(lib.sgp_grouped_linear_wgrad_f32(xp, xrs, xbs, sp, np_, dz.data_ptr(), dw.data_ptr(),
                                             K, groups, ic, oc, _stream(dw)), "sgp_grouped_linear_wgrad_f32")
     return dw
+
+
+# ---------------------------------------------------------------- decoder MLP / readout (decoder_mlp.hip)
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _rows2(t, name, width):
+    """2-D float32 CUDA view [rows, >= width] with unit column stride -> (ptr, row_stride)."""
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{name}: expected a 2-D float32 CUDA view with unit column stride, got "
+                         f"{tuple(t.shape)} {t.dtype} {t.device} strides {t.stride()}")
+    if t.shape[1] < width:
+        raise ValueError(f"{name}: {t.shape[1]} columns, {width} needed")
+    return t.data_ptr(), max(t.stride(0), width)
+
+
+@_on_device
+def dense_pack(w, transpose=False):
+    """nn.Linear weight [out, in] (CUDA) -> the packed M = w (or w^T with ``transpose``) of sgp_dense_f32."""
+    lib = require_gpu()
+    w = w.detach().float()
+    if w.stride(1) != 1:
+        w = w.contiguous()
+    n_out, k = (w.shape[1], w.shape[0]) if transpose else (w.shape[0], w.shape[1])
+    packed = torch.empty(lib.sgp_dense_packed_floats(n_out, k), dtype=torch.float32, device=w.device)
+    _check(lib.sgp_dense_pack_f32(w.data_ptr(), w.stride(0), int(transpose), n_out, k, packed.data_ptr(), _stream(w)),
+           "sgp_dense_pack_f32")
+    return packed
+
+
+@_on_device
+def dense(x, packed, n_out, k, n_rows=None, bias=None, gather=None, row_mod=0, activation=None, n_act=None,
+          dpre=None, pre=None, dropout_p=0., seed=0, drop_width=None, add=None, out=None, out_map=None):
+    """out = epilogue(x M^T) (include/sgp_amd.h, sgp_dense_f32).  ``x``: [rows, >= k] (or the source table of a
+    gather); ``n_act``: the leading columns that get the activation (default all when ``activation`` is given);
+    ``dpre``: backward epilogue (multiply by act'(dpre) * keep); ``out_map``: the six-entry row / column map, default a
+    fresh contiguous [n_rows, n_out]."""
+    lib = require_gpu()
+    xp, xrs = _rows2(x, "x", k)
+    if n_rows is None:
+        n_rows = x.shape[0]
+    if n_act is None:
+        n_act = n_out if (GL_ACT_CODES[activation] or dpre is not None or dropout_p > 0.) else 0
+    if out is None:
+        out = torch.empty(n_rows, n_out, dtype=torch.float32, device=x.device)
+    if out_map is None:
+        out_map = (1 << 62, 0, out.stride(0), 1 << 30, 0, 1)
+    om = (ctypes.c_int64 * 6)(*[int(v) for v in out_map])
+    dp, dprs = _rows2(dpre, "dpre", n_act) if dpre is not None else (None, 0)
+    pp, prs = _rows2(pre, "pre", n_act) if pre is not None else (None, 0)
+    ap, ars = _rows2(add, "add", n_out) if add is not None else (None, 0)
+    _check(lib.sgp_dense_f32(xp, xrs, _ptr(gather), int(row_mod), packed.data_ptr(), _ptr(bias), n_rows, k, n_out,
+                             GL_ACT_CODES[activation], n_act, int(dpre is not None), dp, dprs, pp, prs,
+                             float(dropout_p), int(seed), int(n_act if drop_width is None else drop_width),
+                             ap, ars, out.data_ptr(), om, _stream(out)), "sgp_dense_f32")
+    return out
+
+
+@_on_device
+def dense_wgrad(dz, x, n_out, k, n_rows=None, gather=None, row_mod=0, bias=True, dw=None, db=None):
+    """(dW [n_out, k], db [n_out] or None) = dZ^T X (+ column sums of dZ); deterministic (slice partials, fp64)."""
+    lib = require_gpu()
+    dzp, dzrs = _rows2(dz, "dz", n_out)
+    xp, xrs = _rows2(x, "x", k)
+    n_rows = dz.shape[0] if n_rows is None else n_rows
+    if dw is None:
+        dw = torch.empty(n_out, k, dtype=torch.float32, device=dz.device)
+    if bias and db is None:
+        db = torch.empty(n_out, dtype=torch.float32, device=dz.device)
+    nw = lib.sgp_dense_wgrad_workspace_floats(n_rows, n_out, k, int(bool(bias)))
+    work = torch.empty(max(nw, 1), dtype=torch.float32, device=dz.device)
+    _check(lib.sgp_dense_wgrad_f32(dzp, dzrs, xp, xrs, _ptr(gather), int(row_mod), n_rows, n_out, k,
+                                   dw.data_ptr(), dw.stride(0), _ptr(db) if bias else None, work.data_ptr(), work.numel(),
+                                   _stream(dz)), "sgp_dense_wgrad_f32")
+    return dw, (db if bias else None)
+
+
+@_on_device
+def row_segsum(g, n_seg, perm=None, keys=None):
+    """[n_seg, width] per-node sums of the rows of g (strided over the batch, or along stably sorted keys)."""
+    lib = require_gpu()
+    gp, grs = _rows2(g, "g", g.shape[1])
+    out = torch.empty(n_seg, g.shape[1], dtype=torch.float32, device=g.device)
+    _check(lib.sgp_row_segsum_f32(gp, grs, g.shape[0], g.shape[1], _ptr(perm), _ptr(keys), n_seg, out.data_ptr(),
+                                  _stream(g)), "sgp_row_segsum_f32")
+    return out
+
+
+@_on_device
+def masked_mae(y_hat, y, mask=None, mask_nans=False):
+    """(loss [] float32, count [1] float64) of MaskedMAE over contiguous float32 tensors of one shape."""
+    lib = require_gpu()
+    loss = torch.empty((), dtype=torch.float32, device=y_hat.device)
+    count = torch.empty(1, dtype=torch.float64, device=y_hat.device)
+    _check(lib.sgp_masked_mae_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), y_hat.numel(), int(mask_nans),
+                                  loss.data_ptr(), count.data_ptr(), _stream(loss)), "sgp_masked_mae_f32")
+    return loss, count
+
+
+@_on_device
+def masked_mae_bwd(y_hat, y, mask, mask_nans, grad_out, count):
+    lib = require_gpu()
+    grad = torch.empty_like(y_hat)
+    _check(lib.sgp_masked_mae_bwd_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), y_hat.numel(), int(mask_nans),
+                                      grad_out.data_ptr(), count.data_ptr(), grad.data_ptr(), _stream(grad)),
+           "sgp_masked_mae_bwd_f32")
+    return grad
 
 
 class Event:

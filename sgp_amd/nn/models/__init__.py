@@ -1,3 +1,3 @@
-from .sgp_model import SGPInputEncoder
+from .sgp_model import OnlineSGPModel, SGPInputEncoder, SGPModel, masked_mae
 
-__all__ = ["SGPInputEncoder"]
+__all__ = ["SGPInputEncoder", "SGPModel", "OnlineSGPModel", "masked_mae"]
