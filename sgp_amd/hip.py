@@ -294,6 +294,18 @@ def _view3(t, name):
     return t.data_ptr(), t.stride(1), t.stride(0)
 
 
+def _hop_operands(x, y, halo, n_own):
+    """Operands of the hop bindings: ``(xp, xrs, xbs, hp, hrs, hbs, n_own, yp, yrs, ybs)`` in the ABI's order, and the
+    source column count (rows of x + halo).  ``n_own`` (rows of x that are owned columns) defaults to the rows of x
+    where a halo is given; without one it is 0."""
+    xp, xrs, xbs = _view3(x, "x")
+    yp, yrs, ybs = _view3(y, "y")
+    if halo is None:
+        return (xp, xrs, xbs, None, 0, 0, 0, yp, yrs, ybs), x.shape[1]
+    hp, hrs, hbs = _view3(halo, "halo")
+    return (xp, xrs, xbs, hp, hrs, hbs, x.shape[1] if n_own is None else n_own, yp, yrs, ybs), x.shape[1] + halo.shape[1]
+
+
 MAX_GRID_BATCH = 65535
 
 
@@ -302,15 +314,10 @@ MAX_GRID_BATCH = 65535
 def spmm_csr(rowptr, col, val, x, y, halo=None, n_own=None, pred=None):
     """y[b, i, :] = sum_e val[e] x[b, col[e], :] (generic CSR kernel)."""
     lib = require_gpu()
-    xp, xrs, xbs = _view3(x, "x")
-    yp, yrs, ybs = _view3(y, "y")
+    (xp, xrs, xbs, hp, hrs, hbs, n_own, yp, yrs, ybs), n_cols = _hop_operands(x, y, halo, n_own)
+    if halo is None:
+        n_own = n_cols                                # (this kernel's convention: without a halo every column is owned)
     n_rows = rowptr.numel() - 1
-    n_cols = x.shape[1] + (halo.shape[1] if halo is not None else 0)
-    if halo is not None:
-        hp, hrs, hbs = _view3(halo, "halo")
-        n_own = x.shape[1] if n_own is None else n_own
-    else:
-        hp, hrs, hbs, n_own = None, 0, 0, n_cols
     B, D = x.shape[0], x.shape[2]
     # the vector kernel walks 4 batch entries per grid row; feature widths / strides that are not
     # multiples of 4 floats (or unaligned pointers) take the scalar kernel: one entry per grid row
@@ -329,44 +336,28 @@ def spmm_csr(rowptr, col, val, x, y, halo=None, n_own=None, pred=None):
 
 @_on_device
 def spmm_tiled(plan, x, y, halo=None, n_own=None, pred=None):
-    """Same product through the LDS-staged kernel; ``plan`` from graph.TilePlan.to(device)."""
+    """Same product through the LDS-staged kernel; ``plan`` from tileplan.TilePlan.to(device)."""
     lib = require_gpu()
-    xp, xrs, xbs = _view3(x, "x")
-    yp, yrs, ybs = _view3(y, "y")
-    if halo is not None:
-        hp, hrs, hbs = _view3(halo, "halo")
-        n_own = x.shape[1] if n_own is None else n_own
-    else:
-        hp, hrs, hbs, n_own = None, 0, 0, 0
+    ops, n_cols = _hop_operands(x, y, halo, n_own)
     _check(lib.sgp_spmm_tiled_f32(
         plan.trow.data_ptr(), plan.uptr.data_ptr(), plan.ucol.data_ptr(), plan.erow.data_ptr(),
         plan.ecol.data_ptr(), plan.eval.data_ptr(),
         plan.tile_rows, plan.n_tiles, plan.max_union, plan.max_row_edges,
-        xp, xrs, xbs, hp, hrs, hbs, n_own, yp, yrs, ybs,
-        plan.n_rows, x.shape[1] + (halo.shape[1] if halo is not None else 0),
-        x.shape[0], x.shape[2], *_pred(pred), _stream(x)), "sgp_spmm_tiled_f32")
+        *ops, plan.n_rows, n_cols, x.shape[0], x.shape[2], *_pred(pred), _stream(x)), "sgp_spmm_tiled_f32")
 
 
 @_on_device
 def spmm_res(plan, x, y, halo=None, n_own=None, pred=None):
     """Register-resident two-phase row-group product, exact fp32 (plan: ``TilePlan.pipe``)."""
     lib = require_gpu()
-    xp, xrs, xbs = _view3(x, "x")
-    yp, yrs, ybs = _view3(y, "y")
-    if halo is not None:
-        hp, hrs, hbs = _view3(halo, "halo")
-        n_own = x.shape[1] if n_own is None else n_own
-    else:
-        hp, hrs, hbs, n_own = None, 0, 0, 0
+    ops, n_cols = _hop_operands(x, y, halo, n_own)
     ps = plan.pipe
     _check(lib.sgp_spmm_res_f32(
         ps["uptr"].data_ptr(), ps["ucol"].data_ptr(), ps["usplit"].data_ptr(),
         ps["gptr"].data_ptr(), ps["gsup"].data_ptr(), ps["gidx"].data_ptr(), ps["gw"].data_ptr(),
         ps["rowmap"].data_ptr(),
         plan.n_tiles, ps["max_union"], ps["max_tile_quads"],
-        xp, xrs, xbs, hp, hrs, hbs, n_own, yp, yrs, ybs,
-        plan.n_rows, x.shape[1] + (halo.shape[1] if halo is not None else 0),
-        x.shape[0], x.shape[2], *_pred(pred), _stream(x)), "sgp_spmm_res_f32")
+        *ops, plan.n_rows, n_cols, x.shape[0], x.shape[2], *_pred(pred), _stream(x)), "sgp_spmm_res_f32")
 
 
 @_on_device
@@ -374,21 +365,13 @@ def spmm_mix(plan, x, y, halo=None, n_own=None, pred=None):
     """Mixed dense (16x16x4) / sparse (4x4x1) row-group product (plan: sgp_amd.mixplan.MixPlan on the
     device of ``x``)."""
     lib = require_gpu()
-    xp, xrs, xbs = _view3(x, "x")
-    yp, yrs, ybs = _view3(y, "y")
-    if halo is not None:
-        hp, hrs, hbs = _view3(halo, "halo")
-        n_own = x.shape[1] if n_own is None else n_own
-    else:
-        hp, hrs, hbs, n_own = None, 0, 0, 0
+    ops, n_cols = _hop_operands(x, y, halo, n_own)
     _check(lib.sgp_spmm_mix_f32(
         plan.uptr.data_ptr(), plan.ucol.data_ptr(), plan.usplit.data_ptr(),
         plan.gptr.data_ptr(), plan.gsup.data_ptr(), plan.gidx.data_ptr(), plan.gw.data_ptr(),
         plan.rowmap.data_ptr(), plan.dptr.data_ptr(), plan.didx.data_ptr(), plan.dw.data_ptr(),
         plan.n_tiles, plan.max_union, plan.max_dense,
-        xp, xrs, xbs, hp, hrs, hbs, n_own, yp, yrs, ybs,
-        plan.n_rows, x.shape[1] + (halo.shape[1] if halo is not None else 0),
-        x.shape[0], x.shape[2], *_pred(pred), _stream(x)), "sgp_spmm_mix_f32")
+        *ops, plan.n_rows, n_cols, x.shape[0], x.shape[2], *_pred(pred), _stream(x)), "sgp_spmm_mix_f32")
 
 
 @_on_device
@@ -529,13 +512,7 @@ def spmm_split(plan, x, y, profile, t_chunk=0, halo=None, n_own=None, predicated
     callers that force the kernel).  ``predicated``: launch under ``profile.flag == 1`` (the caller enqueues the
     exact kernel under ``== 0`` behind it)."""
     lib = require_gpu()
-    xp, xrs, xbs = _view3(x, "x")
-    yp, yrs, ybs = _view3(y, "y")
-    if halo is not None:
-        hp, hrs, hbs = _view3(halo, "halo")
-        n_own = x.shape[1] if n_own is None else n_own
-    else:
-        hp, hrs, hbs, n_own = None, 0, 0, 0
+    ops, _ = _hop_operands(x, y, halo, n_own)
     if not isinstance(profile, SplitProfile):
         profile = split_profile(x, halo, profile, guard=False)
     plans = plan if isinstance(plan, (list, tuple)) else [plan]
@@ -547,7 +524,7 @@ def spmm_split(plan, x, y, profile, t_chunk=0, halo=None, n_own=None, predicated
         _check(entry(
             p.hdr.data_ptr(), p.rowid.data_ptr(), p.ucol.data_ptr(), p.afr.data_ptr(), p.adr.data_ptr(),
             p.rinv.data_ptr(), p.n_tiles,
-            xp, xrs, xbs, hp, hrs, hbs, n_own, yp, yrs, ybs, p.n_rows, p.n_cols, x.shape[0], x.shape[2],
+            *ops, p.n_rows, p.n_cols, x.shape[0], x.shape[2],
             profile.tab.data_ptr(), int(p.accumulate), t_chunk, *pr, _stream(x)), "sgp_spmm_split_f32")
     return profile
 
@@ -557,17 +534,10 @@ def spmm_colblock(plan, x, y, halo=None, n_own=None, pred=None):
     """Column-blocked hop for graphs without locality (plan: sgp_amd.colblock.ColBlockPlan on the device
     of ``x``)."""
     lib = require_gpu()
-    xp, xrs, xbs = _view3(x, "x")
-    yp, yrs, ybs = _view3(y, "y")
-    if halo is not None:
-        hp, hrs, hbs = _view3(halo, "halo")
-        n_own = x.shape[1] if n_own is None else n_own
-    else:
-        hp, hrs, hbs, n_own = None, 0, 0, 0
+    ops, _ = _hop_operands(x, y, halo, n_own)
     _check(lib.sgp_spmm_colblock_f32(
         plan.entries.data_ptr(), plan.segptr.data_ptr(), plan.wg_row0.data_ptr(), plan.n_wg, plan.n_blocks,
-        xp, xrs, xbs, hp, hrs, hbs, n_own, yp, yrs, ybs, plan.n_rows, plan.n_cols, x.shape[0], x.shape[2], *_pred(pred),
-        _stream(x)), "sgp_spmm_colblock_f32")
+        *ops, plan.n_rows, plan.n_cols, x.shape[0], x.shape[2], *_pred(pred), _stream(x)), "sgp_spmm_colblock_f32")
 
 
 def split_limits(wide=False):

@@ -2,7 +2,7 @@
 row-group SpMM behind ``x = adj @ x`` (reference: lib/sgp_preprocessing.py:200-203).
 
 Tiles, staged rows, the parity cut into segments A | B and the 4-row groups are those of the
-two-phase kernels (``graph.build_phase_stream``).  New: the 16 groups of a tile form 4 BLOCKS of
+two-phase kernels (``tileplan.build_phase_stream``).  New: the 16 groups of a tile form 4 BLOCKS of
 16 rows, and a block's columns are split in two sets --
 
 * **dense** columns: used by at least ``thr`` of the block's 4 groups.  They go through
@@ -27,7 +27,7 @@ import itertools
 import numpy as np
 import torch
 
-from .graph import GROUP_ROWS, GROUPS_PER_TILE, build_phase_stream, tile_unions
+from .tileplan import GROUP_ROWS, GROUPS_PER_TILE, build_phase_stream, tile_unions
 
 BLOCK_GROUPS = 4
 BLOCKS_PER_TILE = GROUPS_PER_TILE // BLOCK_GROUPS
@@ -37,7 +37,7 @@ _PERMS = np.array(list(itertools.permutations(range(BLOCK_GROUPS))), dtype=np.in
 
 def _cluster_blocks(member):
     """Blocks of 4 groups that share most columns: ``member`` = bool [16, U] (group uses column).
-    Greedy like ``graph.cluster_rows_in_tiles``: seed with the group that overlaps least with the
+    Greedy like ``tileplan.cluster_rows_in_tiles``: seed with the group that overlaps least with the
     free ones (a corner of the tile), add the 3 groups that overlap most with the block.  Returns
     the block of every group."""
     m = member.astype(np.float32)
@@ -246,9 +246,9 @@ class MixPlan:
 
 
 def build_mix_plan(rowptr, col, val, n_rows, base, thr=4, dh=10, order=None, pad_dense=False):
-    """Mixed plan on the tiles and row groups of ``base`` (a ``graph.TilePlan`` with a two-phase
+    """Mixed plan on the tiles and row groups of ``base`` (a ``tileplan.TilePlan`` with a two-phase
     stream).  ``order`` (new id k = old id ``order[k]``): ``base`` was built on the renumbered
-    operator (``graph.build_reordered_plan``); the plan then addresses ORIGINAL ids through ``ucol``
+    operator (``tileplan.build_reordered_plan``); the plan then addresses ORIGINAL ids through ``ucol``
     / ``rowmap`` like the base plan does."""
     if base is None or base.pipe is None:
         return None

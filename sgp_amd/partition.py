@@ -434,7 +434,7 @@ def choose_numbering(ops_global: List[ShiftOperator], world_size, balance="nnz",
         own = max(1, bounds[mid + 1] - bounds[mid])
         plain = halo_rows(ops_global[0], bounds, mid)
         if locality == "always" or 2 * plain > own:
-            from .graph import locality_order
+            from .tileplan import locality_order
             fwd = ops_global[0]
             order = torch.from_numpy(np.ascontiguousarray(
                 locality_order(fwd.rowptr.numpy(), fwd.col.numpy(), n))).long()
@@ -495,7 +495,7 @@ def make_partitioned_spatial(ops_global: List[ShiftOperator], receptive_field, g
     nodes ``bounds[r] .. bounds[r+1]``, else an int64 tensor and rank r owns
     ``node_order[bounds[r]:bounds[r+1]]`` (in that order: row i of the rank's tensors is global
     node ``node_order[bounds[r] + i]``).  ``locality``: "auto" renumbers the nodes by
-    ``graph.locality_order`` when a contiguous cut of the given numbering would make a rank fetch
+    ``tileplan.locality_order`` when a contiguous cut of the given numbering would make a rank fetch
     more than half as many halo rows as it owns (a k-NN graph of stations in file order:
     near-full exchange) and the renumbering fetches at least 30 % fewer; "never" keeps the
     numbering; "always" renumbers.

@@ -11,7 +11,7 @@ import torch
 import sgp_amd
 from conftest import GOLDEN, golden_files
 from oracle import sgp_oracle as O
-from sgp_amd import graph, synthetic
+from sgp_amd import graph, synthetic, tileplan
 from sgp_amd.sgp_preprocessing import spatial_operators
 
 
@@ -98,7 +98,7 @@ LIMITS = dict(max_union=512, max_tile_rows=128, max_row_edges=128)
 def test_tile_plan_knn_graph():
     ei, ew, _ = synthetic.knn_graph(3000, 40, seed=5)
     op = graph.ShiftOperator.from_edges(ei, ew, 3000)
-    plan = graph.build_tile_plan(op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), 3000, **LIMITS)
+    plan = tileplan.build_tile_plan(op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), 3000, **LIMITS)
     assert plan is not None and plan.tile_rows == 64 and plan.max_row_edges == 48
     _check_plan(op, plan)
 
@@ -106,19 +106,19 @@ def test_tile_plan_knn_graph():
 def test_tile_plan_splits_oversized_tiles_and_gives_up_on_random_graphs():
     ei, ew, _ = synthetic.knn_graph(3000, 40, seed=5)
     op = graph.ShiftOperator.from_edges(ei, ew, 3000)
-    small = graph.build_tile_plan(op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), 3000,
+    small = tileplan.build_tile_plan(op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), 3000,
                                   max_union=160, max_tile_rows=128, max_row_edges=128)
     assert small is not None and small.max_union <= 160
     assert np.diff(small.trow.numpy()).min() < small.tile_rows      # some tiles were halved
     _check_plan(op, small)
     ei, ew = synthetic.random_graph(4000, 100, seed=5)
     op = graph.ShiftOperator.from_edges(ei, ew, 4000)
-    assert graph.build_tile_plan(op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), 4000,
+    assert tileplan.build_tile_plan(op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), 4000,
                                  **LIMITS) is None
     # rows longer than the kernel's register budget -> generic kernel
     ei, ew = synthetic.random_graph(300, 200, seed=1)
     op = graph.ShiftOperator.from_edges(ei, ew, 300)
-    assert graph.build_tile_plan(op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), 300,
+    assert tileplan.build_tile_plan(op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), 300,
                                  **LIMITS) is None
 
 
@@ -131,11 +131,11 @@ def test_reordered_plan_for_graphs_without_locality_in_the_numbering():
     perm = np.random.default_rng(1).permutation(n)
     op = graph.ShiftOperator.from_edges(torch.from_numpy(perm[ei.numpy()]), ew, n)
     args = (op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), n)
-    plain = graph.build_tile_plan(*args, **LIMITS)
+    plain = tileplan.build_tile_plan(*args, **LIMITS)
     assert plain is None or plain.tile_rows < 32
-    order = graph.locality_order(op.rowptr.numpy(), op.col.numpy(), n)
+    order = tileplan.locality_order(op.rowptr.numpy(), op.col.numpy(), n)
     assert sorted(order.tolist()) == list(range(n))
-    plan = graph.build_reordered_plan(*args, order, **LIMITS)
+    plan = tileplan.build_reordered_plan(*args, order, **LIMITS)
     assert plan is not None and plan.reordered and plan.tile_rows == 64 and plan.max_union <= 448
     ps = plan.pipe
     gptr, gw, gidx = ps["gptr"].numpy(), ps["gw"].numpy(), ps["gidx"].numpy()
@@ -159,7 +159,7 @@ def test_reordered_plan_for_graphs_without_locality_in_the_numbering():
 def test_tile_plan_small_sparse_graph():
     ei, ew = synthetic.sparse_traffic_graph(207, 1515, seed=3)
     op = graph.ShiftOperator.from_edges(ei, ew, 207)
-    plan = graph.build_tile_plan(op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), 207, **LIMITS)
+    plan = tileplan.build_tile_plan(op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), 207, **LIMITS)
     assert plan is not None
     _check_plan(op, plan)
 
@@ -424,7 +424,7 @@ def test_dropout_rate_is_validated_like_dropout_adj():
 
 
 def test_equal_cost_tiles_cover_the_rows_and_respect_the_limits():
-    """graph.equal_cost_tiles (opt-in planner step): boundaries cover every row once,
+    """tileplan.equal_cost_tiles (opt-in planner step): boundaries cover every row once,
     tiles are whole 4-row groups of at most 64 rows with at most max_union distinct columns, and
     the spread of the per-tile cost shrinks against uniform 64-row tiles."""
     import numpy as np
@@ -434,8 +434,8 @@ def test_equal_cost_tiles_cover_the_rows_and_respect_the_limits():
     op = graph.ShiftOperator.from_edges(ei, ew, n)
     lim = dict(max_union=448, max_tile_rows=64, max_row_edges=4096)
     rp, col, val = op.rowptr.numpy(), op.col.numpy(), op.val.numpy()
-    base = graph.build_tile_plan(rp, col, val, n, equalize=False, **lim)
-    eq = graph.build_tile_plan(rp, col, val, n, equalize=True, **lim)
+    base = tileplan.build_tile_plan(rp, col, val, n, equalize=False, **lim)
+    eq = tileplan.build_tile_plan(rp, col, val, n, equalize=True, **lim)
     assert base is not None and eq is not None and base.n_tiles >= 512
     trow = eq.trow.numpy()
     assert trow[0] == 0 and trow[-1] == n and (np.diff(trow) > 0).all()

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from sgp_amd import graph, mixplan, partition, synthetic
+from sgp_amd import graph, mixplan, partition, synthetic, tileplan
 
 LIMITS = dict(max_union=448, max_tile_rows=64, max_row_edges=128)
 DH = 10
@@ -14,8 +14,8 @@ DH = 10
 
 def _plan(op, thr=4, dh=DH, order=None):
     args = (op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), op.num_nodes)
-    base = graph.build_tile_plan(*args, **LIMITS) if order is None else \
-        graph.build_reordered_plan(*args, order, **LIMITS)
+    base = tileplan.build_tile_plan(*args, **LIMITS) if order is None else \
+        tileplan.build_reordered_plan(*args, order, **LIMITS)
     assert base is not None and base.pipe is not None
     return mixplan.build_mix_plan(*args, base, thr=thr, dh=dh, order=order)
 
@@ -77,7 +77,7 @@ def test_reordered_plan_keeps_original_ids():
     ei, ew, _ = synthetic.knn_graph(n, 15, seed=6)
     perm = torch.randperm(n, generator=torch.Generator().manual_seed(1))
     op = graph.ShiftOperator.from_edges(perm[ei], ew, n)
-    order = graph.locality_order(op.rowptr.numpy(), op.col.numpy(), n)
+    order = tileplan.locality_order(op.rowptr.numpy(), op.col.numpy(), n)
     plan = _plan(op, order=order)
     assert plan.reordered
     _check(op, plan)

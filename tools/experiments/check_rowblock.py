@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from sgp_amd import graph, partition, rowblock, synthetic
+from sgp_amd import graph, partition, rowblock, synthetic, tileplan
 
 MAX_UNION, WAVES = 608, 8
 
@@ -56,7 +56,7 @@ def test_reordered_plan_keeps_original_ids():
     plain = rowblock.build_rowblock_plan(op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), n,
                                          MAX_UNION, WAVES)
     assert plain is None or plain.fill < 0.4        # no locality in the numbering
-    order = graph.locality_order(op.rowptr.numpy(), op.col.numpy(), n)
+    order = tileplan.locality_order(op.rowptr.numpy(), op.col.numpy(), n)
     plan = rowblock.build_rowblock_plan(op.rowptr.numpy(), op.col.numpy(), op.val.numpy(), n,
                                         MAX_UNION, WAVES, order=order)
     assert plan is not None and plan.reordered and plan.fill > 0.5 and plan.tile_rows == 128

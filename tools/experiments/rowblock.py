@@ -2,7 +2,7 @@
 that stands behind ``x = adj @ x`` (reference: lib/sgp_preprocessing.py:202).
 
 A tile is up to ``4 * 4 * waves`` consecutive rows (128 with 8 waves).  Rows are clustered into
-groups of 4 that share most of their source columns (``graph.cluster_rows_in_tiles``); a wave owns
+groups of 4 that share most of their source columns (``tileplan.cluster_rows_in_tiles``); a wave owns
 FOUR groups, one per 16-lane class of ``v_mfma_f32_4x4x1_16b_f32``: in a super-step lane (q, li)
 reads 16 bytes of class q's next source row and the 4 MFMAs add that column's contribution to the
 4 rows of group q -- every class walks its OWN column list, so the accumulators of a lane already
@@ -28,7 +28,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from .graph import GROUP_ROWS, cluster_rows_in_tiles, split_tiles, tile_unions
+from .tileplan import GROUP_ROWS, cluster_rows_in_tiles, split_tiles, tile_unions
 
 
 @dataclass
