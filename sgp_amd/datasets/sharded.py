@@ -3,10 +3,11 @@ SURVEY.md 8b "for outputs > host RAM the build's harness writes shards"; ``run_l
 logs 629 GB for configuration C5) and node shards on devices ("GPU-resident, node-sharded
 embedding ... trivially sharded").
 
-* ``ShardedEmbedding``: index over shard files ``dict(t0, steps, rows | None, embedding[steps, rows, D])`` as
-  ``SGPEncoder.encode_to_shards`` (one GPU: time shards of all nodes) and ``multigpu.encode_multi_gpu(...,
-  shard_dir=)`` (N GPUs: time x node-block shards) write them; loads any time range back, in the original node
-  order.
+* ``ShardedEmbedding``: index over shard files ``dict(t0, steps, rows | None, embedding[steps, rows, D])``
+  (``write_shard``).  The host time-chunk pipeline (``hostpipe.run_chunks``) writes one per chunk:
+  ``SGPEncoder.encode_to_shards`` on one GPU (time shards of all nodes), the ranks of
+  ``multigpu.encode_multi_gpu(..., shard_dir=)`` on N GPUs (time x node-block shards).  Loads any time range back,
+  in the original node order.
 * ``ShardedIIDSampler``: the reference's ``IIDDataset.sample`` (``lib/datasets/iid_dataset.py:57-99``) on a
   NODE-SHARDED embedding.  The index sequence is drawn once, exactly as the reference draws it; every shard
   gathers the rows of the nodes it owns with ``sgp_gather_rows_f32`` on its own device and the pieces meet in
@@ -34,6 +35,12 @@ class ShardedEmbedding:
         meta = torch.load(os.path.join(shard_dir, "index.pt"))
         paths = [os.path.join(shard_dir, os.path.basename(p)) for p in meta["paths"]]
         return cls(paths, *meta["shape"])
+
+    @staticmethod
+    def write_shard(path, t0, steps, rows, embedding, **extra):
+        """One shard file: ``dict(t0, steps, **extra, rows, embedding)``.  ``embedding`` is saved as a copy of its
+        own (the writers hand over a pinned slot that their pipeline refills)."""
+        torch.save(dict(t0=t0, steps=steps, **extra, rows=rows, embedding=embedding.clone()), path)
 
     @staticmethod
     def write_index(shard_dir, paths, shape):

@@ -13,7 +13,8 @@ environment variable ``SGP_AMD_GPUS``, else 1) that same call
 * moves the caller's input into shared memory in place (one copy, no clone) and
 * starts N ranks -- one process per GPU, ``torch.multiprocessing.spawn``, rendezvous on 127.0.0.1 -- that rebuild the
   caller's encoder from ``encoder.describe()`` (constructor arguments, per-layer leaking rates, weights) and run
-  ``RankPipeline``: per time chunk a host gather of the rank's rows into a pinned slot, an asynchronous H2D,
+  the host time-chunk pipeline of every host-in encode (``hostpipe.run_chunks``): per time chunk a host gather of
+  the rank's rows into a pinned slot, an asynchronous H2D,
   ``partition.encode_partitioned`` (reservoir of piece c + 1 under the hops + halo exchange of piece c; packed
   all_to_all / all_gather over RCCL), an asynchronous D2H into a pinned slot and a host scatter into the shared
   result -- two slots each way, so the transfers and the host copies of chunks i - 1 and i + 1 run under the
@@ -70,83 +71,6 @@ def chunk_steps(T, n_own, f_in, d_out, budget_bytes, floor=8):
     return int(max(min(T, floor), min(T, budget_bytes // max(1, 4 * per_step))))
 
 
-class RankPipeline:
-    """Time-chunk pipeline of one rank: host rows -> pinned slot -> device -> ``encode(xs, oc)`` -> pinned slot ->
-    ``sink(t0, n, rows_tensor)``.  Two slots each way; H2D and D2H on their own streams; the host gathers chunk i + 1
-    and scatters chunk i - 1 while the device encodes chunk i (``encode`` only enqueues: nothing on the compute stream
-    waits for the host).  ``events``: a list that receives per chunk ``(compute start, compute end, d2h end)`` timing
-    events (tests: the D2H of chunk i ends after the compute of chunk i + 1 has started)."""
-
-    def __init__(self, dev, tc, n_own, f_in, d_out, nbuf=2):
-        self.dev, self.tc, self.nbuf = dev, tc, nbuf
-        self.xin = [torch.empty(tc, n_own, f_in, dtype=torch.float32, device=dev) for _ in range(nbuf)]
-        self.buf = [torch.empty(tc, n_own, d_out, dtype=torch.float32, device=dev) for _ in range(nbuf)]
-        self.pin_in = [torch.empty(tc, n_own, f_in, dtype=torch.float32, pin_memory=True) for _ in range(nbuf)]
-        self.pin_out = [torch.empty(tc, n_own, d_out, dtype=torch.float32, pin_memory=True) for _ in range(nbuf)]
-        self.h2d, self.d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
-
-    def run(self, x, rows, T, encode, sink, events=None):
-        tc, nbuf, dev = self.tc, self.nbuf, self.dev
-        main = torch.cuda.current_stream(dev)
-        starts = list(range(0, T, tc))
-        timing = events is not None
-        ev_h2d = [None] * nbuf            # the input slot holds its chunk
-        ev_done = [None] * nbuf           # compute of the slot's chunk finished
-        ev_d2h = [None] * nbuf            # the chunk has left buf[slot]
-
-        def stage_in(i):
-            s, t0 = i % nbuf, starts[i]
-            n = min(tc, T - t0)
-            if ev_h2d[s] is not None:
-                ev_h2d[s].synchronize()                          # the slot's previous H2D has read the pinned rows
-            src = x[t0:t0 + n]
-            if isinstance(rows, slice):
-                self.pin_in[s][:n].copy_(src[:, rows])            # host gather (+ dtype cast)
-            else:
-                torch.index_select(src if src.dtype == torch.float32 else src.float(), 1, rows, out=self.pin_in[s][:n])
-            with torch.cuda.stream(self.h2d):
-                if ev_done[s] is not None:
-                    self.h2d.wait_event(ev_done[s])               # the chunk that used xin[s] is encoded
-                self.xin[s][:n].copy_(self.pin_in[s][:n], non_blocking=True)
-                ev_h2d[s] = torch.cuda.Event()
-                ev_h2d[s].record(self.h2d)
-
-        def drain(i):
-            s, t0 = i % nbuf, starts[i]
-            ev_d2h[s].synchronize()                              # (the device is busy with the next chunk meanwhile)
-            sink(t0, min(tc, T - t0), self.pin_out[s][:min(tc, T - t0)])
-
-        if not starts:
-            return
-        stage_in(0)
-        for i, t0 in enumerate(starts):
-            s = i % nbuf
-            n = min(tc, T - t0)
-            if i + 1 < len(starts):
-                stage_in(i + 1)
-            main.wait_event(ev_h2d[s])
-            if ev_d2h[s] is not None:
-                drain(i - nbuf)                                  # chunk i - nbuf leaves pin_out[s] ...
-                main.wait_event(ev_d2h[s])                       # ... and has left buf[s]
-            if timing:
-                c0 = torch.cuda.Event(enable_timing=True)
-                c0.record(main)
-            encode(self.xin[s][:n], self.buf[s][:n])
-            ev_done[s] = torch.cuda.Event(enable_timing=timing)
-            ev_done[s].record(main)
-            with torch.cuda.stream(self.d2h):
-                self.d2h.wait_event(ev_done[s])
-                self.pin_out[s][:n].copy_(self.buf[s][:n], non_blocking=True)
-                ev_d2h[s] = torch.cuda.Event(enable_timing=timing)
-                ev_d2h[s].record(self.d2h)
-            if timing:
-                events.append((c0, ev_done[s], ev_d2h[s]))
-        for i in range(max(0, len(starts) - nbuf), len(starts)):
-            drain(i)
-        main.wait_stream(self.h2d)
-        main.wait_stream(self.d2h)
-
-
 def dist_timeout():
     """Timeout of the ranks' process group: generous (the first collective waits for the slowest rank's graph plans and
     RCCL's own bring-up over xGMI), explicit rather than the backend's default."""
@@ -171,7 +95,8 @@ def _rank_main(rank, world, port, desc, x, out_file, out_shape, plan_dir, shard_
     backing file (None with ``shard_dir``); ``plan_dir``: where the parent left this rank's partition blocks and
     where the rank leaves its report."""
     import torch.distributed as dist
-    from . import hip, partition
+    from . import hip, hostpipe, partition
+    from .datasets.sharded import ShardedEmbedding
     from .nn.encoders.sgp_encoder import SGPEncoder
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -202,9 +127,7 @@ def _rank_main(rank, world, port, desc, x, out_file, out_shape, plan_dir, shard_
         tcs = torch.tensor([tc], dtype=torch.int64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tcs, op=dist.ReduceOp.MIN)
         tc = int(tcs.item())
-        L, R = len(enc.reservoir.reservoir_layers), enc.reservoir.hidden_size
-        state = torch.zeros(L, n_own, R, dtype=torch.float32, device=dev)
-        hip.mark_unit_bounded(state)                          # starts at zero (SGPEncoder._state_bound)
+        state = enc.zero_state(n_own, dev)
         out = None
         if out_file is not None:
             numel = out_shape[0] * out_shape[1] * out_shape[2]
@@ -225,15 +148,14 @@ def _rank_main(rank, world, port, desc, x, out_file, out_shape, plan_dir, shard_
 
         def sink(t0, n, emb):
             if shard_dir is not None:
-                path = os.path.join(shard_dir, f"embedding_r{rank:02d}_t{t0:08d}.pt")
-                torch.save(dict(t0=t0, steps=n, rank=rank, rows=row_ids, embedding=emb.clone()), path)
-                shards.append(path)
+                shards.append(os.path.join(shard_dir, f"embedding_r{rank:02d}_t{t0:08d}.pt"))
+                ShardedEmbedding.write_shard(shards[-1], t0, n, row_ids, emb, rank=rank)
             elif isinstance(rows, slice):
                 out[t0:t0 + n, rows] = emb
             else:
                 out[t0:t0 + n].index_copy_(1, rows, emb)
 
-        RankPipeline(dev, tc, n_own, F, d_out).run(x, rows, T, encode, sink)
+        hostpipe.run_chunks(x, T, tc, encode, dev, n_own, d_out, rows=rows, sink=sink)
         torch.cuda.synchronize(dev)
         dist.barrier()
         blk = spatial.blocks[0]

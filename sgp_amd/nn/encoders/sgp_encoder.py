@@ -1,82 +1,10 @@
 import torch
 from torch import nn
 
-from ... import hip, tune
+from ... import hip, hostpipe, tune
 from ..reservoir import Reservoir
 from ._args import add_reservoir_args, add_spatial_args
 from .sgp_spatial_encoder import SGPSpatialEncoder
-
-
-class _RegisteredSink:
-    """Destination of the pipelined host path: an ORDINARY (pageable) host tensor whose pages are
-    registered with the HIP runtime block by block in a helper thread, so that the D2H copies go
-    straight into it at PCIe speed -- no pinned bounce buffer, no host memcpy.  What remains is
-    the kernel's first-touch cost of fresh pages (11-13 GB/s measured on the MI355X host,
-    tools/probe_hostmem.py): the floor of ANY way of producing into new host memory.  The
-    registration is dropped when the encode is done; the tensor is then plain memory again
-    (the reference's drivers fork DataLoader workers that inherit it copy-on-write)."""
-    BLOCK = 256 << 20
-
-    def __init__(self, out):
-        import threading
-        self.out = out
-        self.rt = torch.cuda.cudart()
-        page = 4096
-        lo = out.data_ptr() // page * page
-        hi = -(-(out.data_ptr() + out.numel() * out.element_size()) // page) * page
-        self.base, self.blocks = out.data_ptr(), []
-        self.todo = [(a, min(self.BLOCK, hi - a)) for a in range(lo, hi, self.BLOCK)]
-        self.done_bytes = 0                     # bytes of ``out`` (from its start) that are registered
-        self.failed = False
-        self.cv = threading.Condition()
-        self.thread = threading.Thread(target=self._run, daemon=True)
-        self.thread.start()
-
-    def _run(self):
-        for addr, size in self.todo:
-            ok = False
-            try:
-                ok = int(self.rt.cudaHostRegister(addr, size, 0)) == 0
-            except Exception:
-                ok = False
-            with self.cv:
-                if ok:
-                    self.blocks.append(addr)
-                    self.done_bytes = addr + size - self.base
-                else:
-                    self.failed = True
-                self.cv.notify_all()
-            if not ok:
-                return
-
-    def wait(self, end_byte):
-        """True once bytes [0, end_byte) of the tensor are registered; False if registration is
-        not available (the caller then goes through its pinned slot)."""
-        with self.cv:
-            while self.done_bytes < end_byte and not self.failed:
-                self.cv.wait()
-            return self.done_bytes >= end_byte
-
-    def pieces(self, b0, b1):
-        """[b0, b1) (bytes from the tensor's start) cut at the block boundaries: one asynchronous
-        copy must stay inside ONE registered range."""
-        first = self.todo[0][0] - self.base                 # <= 0: start of block 0
-        cuts = [b0]
-        k = (b0 - first) // self.BLOCK + 1
-        while first + k * self.BLOCK < b1:
-            cuts.append(first + k * self.BLOCK)
-            k += 1
-        cuts.append(b1)
-        return list(zip(cuts[:-1], cuts[1:]))
-
-    def close(self):
-        self.thread.join()
-        for addr in self.blocks:
-            try:
-                self.rt.cudaHostUnregister(addr)
-            except Exception:
-                pass
-        self.blocks = []
 
 
 class SGPEncoder(nn.Module):
@@ -197,9 +125,7 @@ class SGPEncoder(nn.Module):
                 hip.mark_unit_bounded(state)                  # (carried on: encode_streamed, the time pieces below)
             return out
         if state is None:
-            state = torch.zeros(len(self.reservoir.reservoir_layers), N, self.reservoir.hidden_size,
-                                dtype=torch.float32, device=x.device)
-            hip.mark_unit_bounded(state)
+            state = self.zero_state(N, x.device)
         main = torch.cuda.current_stream(x.device)
         key = str(x.device)
         if key not in self._side_streams:
@@ -255,8 +181,8 @@ class SGPEncoder(nn.Module):
         lib/utils.py:24-31): two device buffers per direction, H2D of chunk i+1 (through a pinned
         slot) and D2H of chunk i-1 on their own streams while chunk i is encoded; the D2H goes
         straight into the result tensor, whose pages a helper thread registers with the runtime
-        ahead of the copies (``_RegisteredSink``; pinned bounce slots + a host memcpy if the
-        runtime refuses).  The recurrence is
+        ahead of the copies (``hostpipe.run_chunks`` / ``RegisteredSink``; pinned bounce slots + a host
+        memcpy if the runtime refuses).  The recurrence is
         carried across chunks in a device-resident state ``[L, N, R]`` and the propagation is
         independent per time step, so the result is bit-identical to a single pass.  This is
         also how embeddings larger than the 288 GB of HBM (BASELINE config C5: 629 GB) or than
@@ -266,147 +192,58 @@ class SGPEncoder(nn.Module):
         ``out``: a caller-supplied contiguous float32 host tensor ``[T, N, D_out]`` to fill instead
         of a fresh one.  A FRESH result tensor costs this host a page fault + zeroing per page
         (11-13 GB/s) -- more than the PCIe transfer; a tensor that is re-used between
-        calls (or was touched before) skips that, and a pinned one (``pin_memory=True``) is written
+        calls (or was touched before) skips that, and a pinned one (``.pin_memory()``) is written
         by the D2H copies directly, without the registration thread."""
         hip.require_gpu()
-        T, N, F = x.shape
+        T, N, _ = x.shape
         dev = torch.device("cuda", torch.cuda.current_device())
-        L, R = len(self.reservoir.reservoir_layers), self.reservoir.hidden_size
-        d_h, D = L * R, self.output_size
-        tc = max(1, min(int(t_chunk), T))
-        starts = list(range(0, T, tc))
+        D = self.output_size
         if out is None:
             out = torch.empty(T, N, D, dtype=torch.float32)
         elif (out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (T, N, D)
               or not out.is_contiguous()):
             raise ValueError(f"out must be a contiguous float32 host tensor of shape {(T, N, D)}")
-        if T == 0:
-            return out
-        out_pinned = out.is_pinned()
-        state = torch.zeros(L, N, R, dtype=torch.float32, device=dev)
-        hip.mark_unit_bounded(state)                          # starts at zero (see _state_bound)
-        nbuf = 2 if len(starts) > 1 else 1
-        xin = [torch.empty(tc, N, F, dtype=torch.float32, device=dev) for _ in range(nbuf)]
-        buf = [torch.empty(tc, N, D, dtype=torch.float32, device=dev) for _ in range(nbuf)]
-        x_pinned = x.is_pinned() and x.dtype == torch.float32
-        pin_in = None if x_pinned else [torch.empty(tc, N, F, dtype=torch.float32, pin_memory=True)
-                                        for _ in range(nbuf)]
-        sink = _RegisteredSink(out) if self.register_output and not out_pinned else None
-        pin_out = [None] * nbuf                                  # pinned bounce slots: only if needed
-        main = torch.cuda.current_stream(dev)
-        h2d, d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
-        ev_h2d = [torch.cuda.Event() for _ in range(nbuf)]      # input slot holds its chunk
-        ev_done = [torch.cuda.Event() for _ in range(nbuf)]     # compute of the slot's chunk finished
-        ev_d2h = [torch.cuda.Event() for _ in range(nbuf)]      # the chunk has left buf[slot]
-        used = [False] * nbuf
-        bounced = [False] * nbuf                                 # chunk sits in pin_out[slot], not in out
-        row_bytes = N * D * 4
-        out_flat = out.view(-1)
-
-        def stage_in(i):
-            s, t0 = i % nbuf, starts[i]
-            n = min(tc, T - t0)
-            if x_pinned:
-                src = x[t0:t0 + n]
-            else:
-                if used[s]:
-                    ev_h2d[s].synchronize()                      # the slot's previous H2D has read it
-                pin_in[s][:n].copy_(x[t0:t0 + n])                # host memcpy (+ dtype cast)
-                src = pin_in[s][:n]
-            with torch.cuda.stream(h2d):
-                if used[s]:
-                    h2d.wait_event(ev_done[s])                   # the chunk that used xin[s] is encoded
-                xin[s][:n].copy_(src, non_blocking=True)
-                ev_h2d[s].record(h2d)
-
-        def send_out(i):
-            """D2H of chunk i: straight into ``out`` once its pages are registered, else through a
-            pinned slot that ``drain`` copies out."""
-            s, t0 = i % nbuf, starts[i]
-            n = min(tc, T - t0)
-            direct = out_pinned or (sink is not None and sink.wait((t0 + n) * row_bytes))
-            if not direct and pin_out[s] is None:
-                pin_out[s] = torch.empty(tc, N, D, dtype=torch.float32, pin_memory=True)
-            bounced[s] = not direct
-            with torch.cuda.stream(d2h):
-                d2h.wait_event(ev_done[s])
-                if direct:
-                    src = buf[s][:n].reshape(-1)
-                    e0 = t0 * (row_bytes // 4)
-                    cuts = [(t0 * row_bytes, (t0 + n) * row_bytes)] if out_pinned else \
-                        sink.pieces(t0 * row_bytes, (t0 + n) * row_bytes)
-                    for a, b in cuts:
-                        out_flat[a // 4:b // 4].copy_(src[a // 4 - e0:b // 4 - e0], non_blocking=True)
-                else:
-                    pin_out[s][:n].copy_(buf[s][:n], non_blocking=True)
-                ev_d2h[s].record(d2h)
-
-        def drain(i):
-            s, t0 = i % nbuf, starts[i]
-            n = min(tc, T - t0)
-            if bounced[s]:
-                ev_d2h[s].synchronize()
-                out[t0:t0 + n].copy_(pin_out[s][:n])             # host memcpy into pageable memory
-                bounced[s] = False
-
-        try:
-            stage_in(0)
-            for i, t0 in enumerate(starts):
-                s = i % nbuf
-                n = min(tc, T - t0)
-                if i + 1 < len(starts):
-                    stage_in(i + 1)
-                main.wait_event(ev_h2d[s])
-                if used[s]:
-                    drain(i - nbuf)                              # (no-op on the direct path)
-                    main.wait_event(ev_d2h[s])                   # buf[s] has been copied out
-                oc = buf[s][:n]
-                self.encode_device(xin[s][:n], ops, out=oc, state=state)
-                ev_done[s].record(main)
-                send_out(i)
-                used[s] = True
-            for i in range(max(0, len(starts) - nbuf), len(starts)):
-                drain(i)
-            d2h.synchronize()
-            main.wait_stream(h2d)
-            main.wait_stream(d2h)
-        finally:
-            if sink is not None:
-                torch.cuda.synchronize(dev)
-                sink.close()
+        state = self.zero_state(N, dev)
+        hostpipe.run_chunks(x, T, max(1, min(int(t_chunk), T)),
+                            lambda xs, oc: self.encode_device(xs, ops, out=oc, state=state),
+                            dev, N, D, out=out, register=self.register_output)
         return out
 
     def encode_to_shards(self, x, ops, shard_dir, shard_steps):
-        """Host tensor x[T, N, F] -> time shards on disk, ``shard_steps`` steps each, never holding more than
-        one shard on the host: embeddings larger than host RAM (configuration C5 is 629 GB,
-        ``experiments/run_largescale_sgp.py:208-212``).  The reservoir state is carried on the device, the
-        propagation is independent per step: the shards are bit-identical to slices of one pass.  Returns a
-        ``sgp_amd.datasets.ShardedEmbedding`` (``load_steps(t0, t1)`` reads any time range back)."""
+        """Host tensor x[T, N, F] -> time shards on disk, ``shard_steps`` steps each, through the pipeline of
+        ``encode_streamed``: embeddings larger than host RAM (configuration C5 is 629 GB,
+        ``experiments/run_largescale_sgp.py:208-212``).  The host holds at most two pinned shard-sized slots (the
+        pipeline's double buffer) plus the copy of the shard being written.  The reservoir state is carried on the
+        device, the propagation is independent per step: the shards are bit-identical to slices of one pass.
+        Returns a ``sgp_amd.datasets.ShardedEmbedding`` (``load_steps(t0, t1)`` reads any time range back)."""
         import os
         from ...datasets.sharded import ShardedEmbedding
         hip.require_gpu()
         T, N, F = x.shape
         os.makedirs(shard_dir, exist_ok=True)
         dev = torch.device("cuda", torch.cuda.current_device())
-        L, R = len(self.reservoir.reservoir_layers), self.reservoir.hidden_size
         D = self.output_size
         per_step = N * (F + D) * 4
-        ts = max(1, min(int(shard_steps), T, self._budget() // max(1, 2 * per_step)))
-        state = torch.zeros(L, N, R, dtype=torch.float32, device=dev)
-        hip.mark_unit_bounded(state)                          # starts at zero (see _state_bound)
-        buf = torch.empty(ts, N, D, dtype=torch.float32, device=dev)
-        pin = torch.empty(ts, N, D, dtype=torch.float32, pin_memory=True)
+        ts = max(1, min(int(shard_steps), T, self._budget() // max(1, 2 * per_step)))    # two slots each way
+        state = self.zero_state(N, dev)
         paths = []
-        for t0 in range(0, T, ts):
-            n = min(ts, T - t0)
-            xs = x[t0:t0 + n].float().to(dev)
-            self.encode_device(xs if xs.stride(2) == 1 else xs.contiguous(), ops, out=buf[:n], state=state)
-            pin[:n].copy_(buf[:n])                                # (synchronous: the shard is complete on the host)
-            path = os.path.join(shard_dir, f"embedding_t{t0:08d}.pt")
-            torch.save(dict(t0=t0, steps=n, rows=None, embedding=pin[:n].clone()), path)
-            paths.append(path)
+
+        def sink(t0, n, emb):
+            paths.append(os.path.join(shard_dir, f"embedding_t{t0:08d}.pt"))
+            ShardedEmbedding.write_shard(paths[-1], t0, n, None, emb)
+
+        hostpipe.run_chunks(x, T, ts, lambda xs, oc: self.encode_device(xs, ops, out=oc, state=state),
+                            dev, N, D, sink=sink)
         ShardedEmbedding.write_index(shard_dir, paths, (T, N, D))
         return ShardedEmbedding(paths, T, N, D)
+
+    def zero_state(self, n_nodes, device):
+        """Reservoir state ``[L, n_nodes, R]`` carried across time chunks: zero, hence marked unit-bounded
+        (see ``_state_bound``)."""
+        state = torch.zeros(len(self.reservoir.reservoir_layers), n_nodes, self.reservoir.hidden_size,
+                            dtype=torch.float32, device=device)
+        hip.mark_unit_bounded(state)
+        return state
 
     # D2H straight into the (registered) result tensor; False = pinned bounce slots + host memcpy
     register_output = True

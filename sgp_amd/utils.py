@@ -30,9 +30,10 @@ def encode_dataset(dataset, encoder_class, encoder_kwargs, encode_exogenous=True
     node-partitions the graph over N GPUs behind the same single-process call (``sgp_amd/multigpu.py``:
     one rank per GPU is started and joined inside, the embedding comes back as one host tensor in the
     dataset's node order); ``shard_steps=S`` with ``save_path`` a DIRECTORY streams the embedding to disk in
-    time shards of S steps (never holding more than one on the host: embeddings larger than host RAM, the
-    629 GB of ``run_largescale_sgp.py:208-212``) instead of the reference's single ``torch.save``
-    (lib/utils.py:34-35); ``encoded_x`` is then a ``sgp_amd.datasets.ShardedEmbedding``."""
+    time shards of S steps (the host holds at most two pinned shard-sized slots and the copy being
+    written: embeddings larger than host RAM, the 629 GB of ``run_largescale_sgp.py:208-212``)
+    instead of the reference's single ``torch.save`` (lib/utils.py:34-35); ``encoded_x`` is then a
+    ``sgp_amd.datasets.ShardedEmbedding``."""
     exo_keys = _exogenous_to_encode(dataset, encode_exogenous)
     x, _ = dataset.get_tensors(['data'] + exo_keys, preprocess=True, cat_dim=-1)
     encoder = encoder_class(**encoder_kwargs)
