@@ -407,6 +407,19 @@ int sgp_reservoir_pieces_f32(const float* x, int64_t x_row_stride, int64_t x_ste
                              int32_t N, int32_t F, int32_t R,
                              const int32_t* pred, int32_t run_if, sgp_stream_t stream);
 
+/* Which kernels the two entries above launch for such a call, from the planner they run (plan_reservoir,
+ * csrc/reservoir.hip); host only, no device pointers.  has_state / has_pred: h_state / pred would be non-NULL
+ * (n_pieces = 1, no_store = 0, has_pred = 0: sgp_reservoir_f32); x_align / out_align: the pointers' address modulo 16.
+ * Writes one JSON object per line into text, in launch order: {"kernel": name} for every weight pack and the
+ * initial-state test, then per layer-kernel launch its name with template arguments, node range, grid (x, y), workgroup
+ * size, dynamic LDS bytes, predicate (none / caller / state_inside / state_outside: the word "some initial state lies
+ * outside [-1, 1]" == 0 / == 1) and lane (main / side).  A request the entries refuse returns their error. */
+int sgp_reservoir_describe(int32_t F, int32_t R, int32_t N, int32_t T, int32_t act, double alpha, int32_t has_state,
+                           int32_t n_pieces, int32_t no_store, int32_t has_pred,
+                           int64_t x_row_stride, int64_t x_step_stride, int32_t x_align,
+                           int64_t out_row_stride, int64_t out_step_stride, int32_t out_align,
+                           char* text, int64_t capacity);
+
 /* All L layers of a narrow stacked reservoir in ONE launch (lib/nn/reservoir/reservoir.py:170-180:
  * the reference steps every layer inside one time step, layer l consuming layer l-1's new state).
  * The layers are pipelined as a wavefront over the waves of a workgroup (layer l on step t while

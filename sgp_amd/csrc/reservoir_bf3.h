@@ -29,26 +29,6 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-__host__ __device__ constexpr int bf3_kbh(int JT) { return (JT + 1) / 2; }
-__host__ __device__ constexpr int bf3_kbx(int NKX) { return (NKX + 7) / 8; }
-__host__ __device__ constexpr long long bf3_packed_bytes(int JT, int NKX) {
-    return (long long)JT * 64 + (long long)JT * (bf3_kbh(JT) + bf3_kbx(NKX)) * 3 * 1024;
-}
-
-// narrow reservoirs and inputs: the state (16 JT), the input rows (4 NKX values per node) and the pieces of one
-// k-block fit the 128 registers of four waves per SIMD
-__host__ __device__ constexpr bool bf3_supported(int JT, int NKX) {
-    return (JT == 2 || JT == 4) && (NKX == 4 || NKX == 8 || NKX == 16) && bf3_packed_bytes(JT, NKX) <= 64 * 1024;
-}
-
-
-// wide reservoirs (reservoir_layer_stream_bf3, reservoir_impl.h): bias [256] fp32, then per (k-block, half of the
-// output tiles) 8 tiles x 3 pieces x 64 lanes x 16 bytes -- the order the kernel streams them through the LDS
-__host__ __device__ constexpr bool sbf3_supported(int JT, int NKX) { return JT == 16 && NKX % 8 == 0 && NKX <= 32; }
-__host__ __device__ constexpr long long sbf3_packed_bytes(int JT, int NKX) {
-    return 1024 + 2ll * (JT / 2 + NKX / 8) * 8 * 3 * 1024;
-}
-
 // input feature held by lane group q in its register ks
 __host__ __device__ constexpr int bf3_feature(int NKX, int q, int ks) {
     return NKX % 4 == 0 ? 16 * (ks >> 2) + 4 * q + (ks & 3) : q * NKX + ks;
@@ -150,7 +130,7 @@ __device__ __forceinline__ f32x4 sj16_mfma(const u32x4& w, const u32x4& v, f32x4
 // (s_waitcnt vmcnt(4) for the input rows with the four stores behind them still in flight).  With a branch around any
 // of them -- an exec-masked store, a wave-uniform `tile exists` test -- it falls back to vmcnt(0) at the top of every
 // tile and step, and the step waits for its own stores to reach memory (measured: 5360 cycles per tile and step).
-// N is a multiple of 16 here: the nodes of a ragged last tile go to the exact-fp32 kernel (launch_layer).
+// N is a multiple of 16 here: the nodes of a ragged last tile go to the exact-fp32 kernel (plan_reservoir).
 // PAIR (NT = 2, at most three waves per SIMD: 170 registers, 162-168 used): a wave multiplies its two tiles TOGETHER --
 // every weight fragment read from the LDS serves both (24 instead of 48 KB of LDS reads per tile and step), four
 // accumulators take turns behind every pair of fragments.  Measured N = 100 000, 256 steps: 3.46 -> 3.36 ms.  (The
@@ -201,7 +181,8 @@ __global__ __launch_bounds__(PAIR ? 768 : 1024, PAIR ? 3 : 4) void reservoir_lay
     }
     {
         const f32x4* src = reinterpret_cast<const f32x4*>(H16 ? a.wp_h16l : a.wp_bf3);
-        const int total4 = (int)((bf3_packed_bytes(JT, NKX) + (H16 ? JT * 64 : 0)) / 16);
+        constexpr ResLayout L(JT, NKX);                    // (H16: + the row scales behind the fragments)
+        const int total4 = (int)((H16 ? L.bf3h_state - L.bf3h : bf3_packed_bytes(JT, NKX)) / 16);
         for (int i = threadIdx.x; i < total4; i += blockDim.x) reinterpret_cast<f32x4*>(lds)[i] = src[i];
         __syncthreads();
     }
@@ -331,7 +312,8 @@ __global__ __launch_bounds__(PAIR ? 768 : 1024, PAIR ? 3 : 4) void reservoir_lay
                 });
                 if constexpr (H16) {
                     // the rows' sums carry 2^(e_j + 14) (bias and input fragments were scaled to match): back, exactly
-                    const float* rsc_t = bias_t + (int)(bf3_packed_bytes(JT, NKX) / 4);
+                    constexpr ResLayout L(JT, NKX);
+                    const float* rsc_t = bias_t + (int)((L.bf3h_scales - L.bf3h) / 4);
 #pragma unroll
                     for (int jt = 0; jt < JT; ++jt) {
                         const f32x4 rs = *reinterpret_cast<const f32x4*>(rsc_t + jt * 16 + q * 4);

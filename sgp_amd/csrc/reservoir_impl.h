@@ -34,6 +34,57 @@ __host__ __device__ constexpr long long packed_floats(int JT, int NKX) {
     return (long long)JT * 16 + (long long)JT * NKX * 64 + (long long)JT * JT * 256;
 }
 
+// sizes and shape classes of the other packs (their layouts: reservoir_bf3.h, reservoir_splitj_bf3.h)
+__host__ __device__ constexpr int bf3_kbh(int JT) { return (JT + 1) / 2; }
+__host__ __device__ constexpr int bf3_kbx(int NKX) { return (NKX + 7) / 8; }
+__host__ __device__ constexpr long long bf3_packed_bytes(int JT, int NKX) {
+    return (long long)JT * 64 + (long long)JT * (bf3_kbh(JT) + bf3_kbx(NKX)) * 3 * 1024;
+}
+// narrow reservoirs and inputs: the state (16 JT), the input rows (4 NKX values per node) and the pieces of one
+// k-block fit the 128 registers of four waves per SIMD
+__host__ __device__ constexpr bool bf3_supported(int JT, int NKX) {
+    return (JT == 2 || JT == 4) && (NKX == 4 || NKX == 8 || NKX == 16) && bf3_packed_bytes(JT, NKX) <= 64 * 1024;
+}
+// wide reservoirs (reservoir_layer_stream_bf3): bias [256] fp32, then per (k-block, half of the
+// output tiles) 8 tiles x 3 pieces x 64 lanes x 16 bytes -- the order the kernel streams them through the LDS
+__host__ __device__ constexpr bool sbf3_supported(int JT, int NKX) { return JT == 16 && NKX % 8 == 0 && NKX <= 32; }
+__host__ __device__ constexpr long long sbf3_packed_bytes(int JT, int NKX) {
+    return 1024 + 2ll * (JT / 2 + NKX / 8) * 8 * 3 * 1024;
+}
+__host__ __device__ constexpr bool sjbf3_supported(int JT, int NKX) { return (JT == 4 || JT == 8) && (NKX <= 8 || NKX == 16); }
+// fp16 fragments of the recurrent blocks: [JT x 16 row scales 2^(-e_j - 14)] [JT][KBH][2 pieces][64 lanes][16 B]
+__host__ __device__ constexpr long long sj16_packed_bytes(int JT) { return JT * 64ll + (long long)JT * bf3_kbh(JT) * 2 * 1024; }
+
+// ---- workspace layout (bytes) ---------------------------------------------------------------
+// Every region of the sgp_reservoir_workspace_bytes(F, R) scratch buffer, for the host, the pack kernels and the layer
+// kernels alike (a region a shape class has no use for stays 0).  A kernel that holds a pack's base pointer reaches the
+// regions behind it by the difference of two members.
+struct ResLayout {
+    long long fp32 = 0;                                  // exact-fp32 fragments (pack_weights)
+    long long bf3 = 0, sj16 = 0;                         // bf16-piece fragments; split-J two-piece fp16 pack of W_hh
+    long long bf3h = 0, bf3h_scales = 0, bf3h_state = 0; // large-N fp16 pack, its JT x 16 row scales (contiguous: one LDS copy), state-test word
+    long long sbf3 = 0, sbf3_dump = 0;                   // streamed bf16 pack + the kernel's dump KB
+    long long sbf3h = 0, sbf3h_dump = 0, sbf3h_scales = 0, sbf3h_state = 0;   // its fp16 copy, dump KB, row scales, state-test word
+    long long splitj_dump = 0, total = 0;                // the split-J bf16-piece kernel's dump KB (last)
+    __host__ __device__ constexpr ResLayout(int jt, int nkx) {
+        long long at = (packed_floats(jt, nkx) * 4 + 255) / 256 * 256;
+        if (bf3_supported(jt, nkx) || sjbf3_supported(jt, nkx)) { bf3 = at; at += bf3_packed_bytes(jt, nkx); }
+        if (sjbf3_supported(jt, nkx)) { sj16 = at; at += sj16_packed_bytes(jt); }
+        if (bf3_supported(jt, nkx)) {
+            bf3h = at; bf3h_scales = bf3h + bf3_packed_bytes(jt, nkx); bf3h_state = bf3h_scales + jt * 64;
+            at = bf3h_state + 256;
+        }
+        if (sbf3_supported(jt, nkx)) {
+            sbf3 = at; sbf3_dump = sbf3 + sbf3_packed_bytes(jt, nkx);
+            sbf3h = sbf3_dump + 1024; sbf3h_dump = sbf3h + sbf3_packed_bytes(jt, nkx);
+            sbf3h_scales = sbf3h_dump + 1024; sbf3h_state = sbf3h_scales + 1024;
+            at = sbf3h_state + 256;
+        }
+        splitj_dump = (at + 255) / 256 * 256;
+        total = splitj_dump + 1024;
+    }
+};
+
 // tanh(x) = 1 - 2 r(x), r(x) = 1 / (1 + e^{2x}): mul, v_exp_f32, add, v_rcp_f32 (two of them quarter-rate) + one fma --
 // and the fma disappears into the leak,
 //     h' = (1-a) h + a tanh(x) = fma(-2a, r, fma(1-a, h, a)),
@@ -92,7 +143,29 @@ struct ResArgs {
     int n_pieces, t_last, no_store;
     long long px, po, ps;
 };
-inline bool wants_pieces(const ResArgs& a) { return a.n_pieces > 1 || a.no_store || a.pred != nullptr; }
+
+// ---- launch plan (built by plan_reservoir, reservoir.hip; shown by sgp_reservoir_describe) ----------------------
+enum ResForm { kFormLayer, kFormBf3, kFormSplitj, kFormSplitjBf3, kFormStream, kFormStream8, kFormStreamBf3 };
+enum ResPack { kPackFp32 = 1, kPackBf3 = 2, kPackSj16 = 4, kPackBf3h = 8, kPackSbf3 = 16, kPackSbf3h = 32 };
+// launch predicate of a part: none, the caller's (pieces entry), or the state-test word "some initial state lies outside
+// [-1, 1] (or is NaN)" == 0 / == 1 (the instance whose predicate fails exits at its first instruction)
+enum ResPred { kPredNone, kPredCaller, kPredStateInside, kPredStateOutside };
+struct ResPart {
+    int form, nt;                         // kernel form; tiles per wave of the instance (kFormLayer / kFormBf3)
+    bool pair, h16, xvec, ovec, act_tanh; // instance flags: two-tile pair form, two-piece fp16 state, 16-byte x loads /
+                                          // out stores, activation compiled in (split-J bf16-piece form)
+    long long n0; int n;                  // node range [n0, n0 + n)
+    int tiles_per_wave;                   // exact deal: tiles per SIMD (streamed forms: full workgroups), else 0
+    unsigned grid, grid_y, block; int lds;
+    int pred; bool side;                  // ResPred; runs on the side lane beside the parts after it
+};
+struct ResPlan {
+    int jt, nkx;
+    unsigned packs;                       // ResPack bits: exactly what the parts read
+    bool state_test;                      // exactly when a part is predicated on the state word
+    int n_parts; ResPart part[4];
+};
+using ResKernel = void (*)(ResArgs);
 
 // waves per SIMD the register budget is sized for (more co-resident waves = the MFMA pipe
 // stays busy while another wave runs its activation / loads / stores)
@@ -123,7 +196,7 @@ __global__ __launch_bounds__(JT <= 4 ? 1024 : 256, min_waves(JT, NT)) void reser
     if (a.tiles_per_wave > 0) {
         // exact deal (16-wave workgroups, one per CU): waves w, w + 4, w + 8, w + 12 share a SIMD and
         // together own `per` consecutive tiles, as evenly as NT allows -- every SIMD of the chip carries
-        // the same number of tiles (launch_layer; the tiles beyond 1024 x per go to the split-J kernel)
+        // the same number of tiles (plan_reservoir; the tiles beyond 1024 x per go to the split-J kernel)
         const int per = a.tiles_per_wave;
         const int wl = threadIdx.x >> 6, c = wl & 3, k = wl >> 2;
         const int base = per >> 2, extra = per & 3;
@@ -344,7 +417,7 @@ __global__ __launch_bounds__(256, 1) void reservoir_layer_stream(ResArgs a) {
     const int lane = threadIdx.x & 63;
     const int n_in = lane & 15, q = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // tile assignment (host: launch_stream): full workgroups own 8 tiles, the tail ones 4
+    // tile assignment (host: plan_reservoir): full workgroups own 8 tiles, the tail ones 4
     const int full = a.tiles_per_wave;                   // number of workgroups with 2 tiles per wave
     int tile0, tile1;
     if ((int)blockIdx.x < full) { tile0 = ((int)blockIdx.x * 4 + wv) * 2; tile1 = tile0 + 2; }
@@ -553,7 +626,7 @@ __global__ __launch_bounds__(512, 2) void reservoir_layer_stream8(ResArgs a) {
     const int lane = threadIdx.x & 63;
     const int n_in = lane & 15, q = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // tile assignment (host: launch_stream): one tile per wave; full workgroups own 8 tiles (two waves per SIMD:
+    // tile assignment (host: plan_reservoir): one tile per wave; full workgroups own 8 tiles (two waves per SIMD:
     // one multiplies while the other requests weight pieces, loads its input row or evaluates tanh), the tail
     // ones 4 (waves 0-3, one per SIMD; waves 4-7 only carry their share of the weight pieces)
     const int full = a.tiles_per_wave;                   // number of workgroups with 8 tiles
@@ -772,10 +845,11 @@ __global__ __launch_bounds__(512, 2) void reservoir_layer_stream_bf3(ResArgs a) 
     static_assert(NSB >= JT && 2 * KBX + NXL <= NSB, "one store / one load per sub-block");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* bias_l = lds + RING * SLOT / 4;               // after the ring slots (H16: + the rows' way back behind it)
+    constexpr ResLayout L(JT, NKX);
     const char* wpb = static_cast<const char*>(H16 ? a.wp_h16s : a.wp_bf3);
     for (int i = threadIdx.x; i < JT * 16; i += 512) {
         bias_l[i] = reinterpret_cast<const float*>(wpb)[i];
-        if constexpr (H16) bias_l[JT * 16 + i] = reinterpret_cast<const float*>(wpb + sbf3_packed_bytes(JT, NKX) + 1024)[i];
+        if constexpr (H16) bias_l[JT * 16 + i] = reinterpret_cast<const float*>(wpb + (L.sbf3h_scales - L.sbf3h))[i];
     }
     float hscale = kSj16StateScale;
     if constexpr (H16) asm("" : "+s"(hscale));
@@ -792,7 +866,7 @@ __global__ __launch_bounds__(512, 2) void reservoir_layer_stream_bf3(ResArgs a) 
     const bool busy = tile0 < tile1;                     // wave-uniform: this wave owns a tile
     const int node = tile0 * 16 + n_in;
     const bool ok = busy && node < a.N;
-    float* const dump = reinterpret_cast<float*>(const_cast<char*>(wpb) + sbf3_packed_bytes(JT, NKX)) + lane * 4;
+    float* const dump = reinterpret_cast<float*>(const_cast<char*>(wpb) + (H16 ? L.sbf3h_dump - L.sbf3h : L.sbf3_dump - L.sbf3)) + lane * 4;
     const float* const xrow = a.x + (long long)(ok ? node : 0) * a.xrs + 4 * q;
     float* const orow = a.out + (long long)(ok ? node : 0) * a.ors + 4 * q;
 
@@ -986,45 +1060,14 @@ __global__ __launch_bounds__(512, 2) void reservoir_layer_stream_bf3(ResArgs a) 
 }
 
 template <int JT, int NKX>
-int launch_stream(ResArgs a, hipStream_t s) {
-    a.n_tiles = (a.N + 15) / 16;
-    // full rounds of 256 workgroups x 8 tiles; what is left gets one tile per wave if that is
-    // enough to hold it, so the last (partial) round costs half a round
-    const int per_round = 256 * 8;
-    int full = (a.n_tiles / per_round) * 256;
-    int rest = a.n_tiles - full * 8;
-    int tail_wgs;
-    if (rest > 1024) { full += (rest + 7) / 8; tail_wgs = 0; }
-    else tail_wgs = (rest + 3) / 4;
-    a.tiles_per_wave = full;
-    // 8 waves x 1 tile (two waves per SIMD) unless SGP_TUNE=res_stream8=0 asks for round 3's 4 waves x 2 tiles
-    static const int eight = (int)sgp::tune("res_stream8", 1);
-    void (*kern)(ResArgs) = eight ? reservoir_layer_stream8<JT, NKX, true, true> : reservoir_layer_stream<JT, NKX, true, true>;
-    int bytes = 4 * JT * 1024 + JT * 16 * 4;                 // RING slots + bias
-    bool bf3 = false;
-    a.pred = nullptr; a.pred_want = 0;
+ResKernel resolve_stream(const ResPart& p) {
+    if (p.form == kFormStream) return reservoir_layer_stream<JT, NKX, true, true>;
+    if (p.form == kFormStream8) return reservoir_layer_stream8<JT, NKX, true, true>;
     if constexpr (sbf3_supported(JT, NKX)) {
-        if (a.wp_bf3) { kern = reservoir_layer_stream_bf3<JT, NKX>; bytes = 4 * 8 * 3 * 1024 + 2 * JT * 16 * 4; bf3 = true; }
-        if (a.wp_bf3 && a.wp_h16s) {
-            // tanh: the two-piece fp16 instance, alone or under the initial-state word == 0 with the three-piece one behind it
-            void (*kern16)(ResArgs) = reservoir_layer_stream_bf3<JT, NKX, true>;
-            hipError_t e16 = hipFuncSetAttribute(reinterpret_cast<const void*>(kern16),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e16 != hipSuccess) return sgp::fail((int)e16, "reservoir: LDS opt-in: %s", hipGetErrorString(e16));
-            a.pred = a.bad_state; a.pred_want = 0;
-            hipLaunchKernelGGL(kern16, dim3(full + tail_wgs), dim3(512), (size_t)bytes, s, a);
-            int rc16 = sgp::check_launch("reservoir_layer_stream_bf3 (fp16 pieces)");
-            if (rc16 || !a.bad_state) return rc16;
-            a.pred_want = 1;
-        }
+        if (p.form == kFormStreamBf3) return p.h16 ? reservoir_layer_stream_bf3<JT, NKX, true> : reservoir_layer_stream_bf3<JT, NKX>;
     }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return sgp::fail((int)e, "reservoir: LDS opt-in: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(kern, dim3(full + tail_wgs), dim3(eight || bf3 ? 512 : 256), (size_t)bytes, s, a);
-    return sgp::check_launch("reservoir_layer_stream");
+    return nullptr;
 }
-
 
 #endif  // SGP_RES_STREAM_TU
 
@@ -1260,212 +1303,67 @@ __global__ __launch_bounds__(256) void reservoir_layer_splitj(ResArgs a) {
     }
 }
 
-template <int JT, int NKX>
-constexpr long long splitj_lds_bytes() {
+constexpr long long splitj_lds_bytes(int JT, int NKX) {
     return splitj_fixed_bytes(JT, NKX) + (long long)splitj_ring(JT, NKX) * NKX * 64 * 4;
 }
-
-template <int JT, int NKX, int NT>
-int launch_layer(ResArgs a, hipStream_t s) {
-    const long long wbytes = packed_floats(JT, NKX) * 4;
-    a.n_tiles = (a.N + 15) / 16;
-    // Small problems: one single-tile wave per workgroup (every wave gets its own CU).
-    // Large problems: a wave count that is a multiple of 1024 SIMDs, tiles dealt evenly,
-    // so every SIMD carries the same number of waves and (almost) of tiles.
-    int wpw = 1, grid = a.n_tiles;
-    if (a.tiles_per_wave > 0) {                  // exact deal: one 16-wave workgroup per CU
-        wpw = 16;
-        grid = 256;
-    } else if (a.n_tiles > 1024) {
-        const int rounds = (a.n_tiles + 1024 * NT - 1) / (1024 * NT);
-        const int n_waves = 1024 * rounds;
-        // Narrow reservoirs (<= 128 VGPRs): ONE 16-wave workgroup per CU, so that the waves that
-        // share a SIMD (w, w+4, w+8, w+12 of a workgroup) are consecutive in the tile deal and the
-        // busiest SIMD carries ceil(tiles per CU / 4) tiles.  With 4-wave workgroups the four
-        // co-resident workgroups of a CU are unrelated and some SIMD ends up with 4 x NT tiles
-        // (8 against an average of 6.1 on the target line).
-        wpw = JT <= 4 ? 16 : 4;
-        grid = n_waves / wpw;
-    }
-    const bool xv = (NKX % 4 == 0) && (a.F % 4 == 0) && (a.xrs % 4 == 0) && (a.xss % 4 == 0) && sgp::aligned16(a.x);
-    const bool ov = (a.R % 4 == 0) && (a.ors % 4 == 0) && (a.oss % 4 == 0) && sgp::aligned16(a.out);
-    void (*kern)(ResArgs);
-    if constexpr (bf3_supported(JT, NKX)) {
-        // three-piece bf16 products (reservoir_bf3.h): 3/8 of the matrix time of the exact-fp32 kernel
-        // exact widths, 16-byte rows, row offsets in 32 bits; the nodes of a ragged last tile (N % 16) go to the
-        // exact-fp32 kernel in a second launch
-        const long long n16 = a.N / 16 * 16;
-        if (a.wp_bf3 && ov && xv && a.R == 16 * JT && a.F == 4 * NKX && n16 > 0 &&
-            n16 * a.xrs * 4 < (1ll << 32) && n16 * a.ors * 4 < (1ll << 32)) {
-            void (*kern16)(ResArgs) = reservoir_layer_bf3<JT, NKX, NT, false, true>;     // two fp16 pieces for the bounded state
-            kern = reservoir_layer_bf3<JT, NKX, NT>;
-            if constexpr (NT == 2) {
-                // exact deal with at most three two-tile waves per SIMD (5 or 6 tiles): the two tiles share every
-                // fragment read (res_pair = 0, SGP_TUNE: one tile after the other)
-                static const bool pair = sgp::tune("res_pair", 1) != 0;
-                if (pair && a.tiles_per_wave > 0 && (a.tiles_per_wave + NT - 1) / NT <= 3) {
-                    kern = reservoir_layer_bf3<JT, NKX, NT, true>;
-                    kern16 = reservoir_layer_bf3<JT, NKX, NT, true, true>;
-                }
-            }
-            const int bytes = (int)bf3_packed_bytes(JT, NKX) + JT * 64;       // (+ the row scales of the two-piece fp16 form)
-            for (auto k : {kern, kern16}) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-                if (e != hipSuccess) return sgp::fail((int)e, "reservoir: LDS opt-in: %s", hipGetErrorString(e));
-            }
-            ResArgs m = a;
-            m.N = (int)n16;
-            m.n_tiles = (int)(n16 / 16);
-            if (a.tiles_per_wave <= 0 && m.n_tiles <= 1024) grid = m.n_tiles;
-            // as many waves per SIMD as share its tiles evenly (6 tiles: 3 waves of 2; same time as 2 + 2 + 1 + 1 on 4)
-            if (a.tiles_per_wave > 0) wpw = 4 * ((a.tiles_per_wave + NT - 1) / NT);
-            // tanh with packed fp16 fragments: the two-piece instance -- alone when the recurrence starts from zero, else under
-            // the device word "some initial state lies outside [-1, 1]" == 0 with the three-piece instance under == 1
-            // behind it (no host round trip; the instance whose predicate fails exits at its first instruction)
-            m.pred = nullptr; m.pred_want = 0;
-            if (a.wp_h16l) {
-                m.pred = a.bad_state; m.pred_want = 0;
-                hipLaunchKernelGGL(kern16, dim3(grid), dim3(64 * wpw), (size_t)bytes, s, m);
-                int rc16 = sgp::check_launch("reservoir_layer_bf3 (fp16 pieces)");
-                if (rc16) return rc16;
-                m.pred_want = 1;
-            }
-            if (!a.wp_h16l || a.bad_state) hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpw), (size_t)bytes, s, m);
-            int rc = sgp::check_launch("reservoir_layer_bf3");
-            if (rc || n16 == a.N) return rc;
-            ResArgs r = a;                                   // the last, ragged tile
-            r.wp_bf3 = nullptr; r.wp_h16l = nullptr;
-            r.tiles_per_wave = 0;
-            r.x = a.x + n16 * a.xrs;
-            r.out = a.out + n16 * a.ors;
-            if (a.h_state) r.h_state = a.h_state + n16 * a.R;
-            r.N = a.N - (int)n16;
-            return launch_layer<JT, NKX, 1>(r, s);
-        }
-    }
-    constexpr bool kLds = packed_floats(JT, NKX) * 4 <= kLdsLimit;
-    if (xv && ov) kern = reservoir_layer<JT, NKX, NT, kLds, true, true>;
-    else if (ov) kern = reservoir_layer<JT, NKX, NT, kLds, false, true>;
-    else kern = reservoir_layer<JT, NKX, NT, kLds, false, false>;
-    if constexpr (kLds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)wbytes);
-        if (e != hipSuccess) return sgp::fail((int)e, "reservoir: LDS opt-in: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpw), (size_t)wbytes, s, a);
-    } else {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpw), 0, s, a);
-    }
-    return sgp::check_launch("reservoir_layer");
-}
-
-template <int JT, int NKX> int launch_stream_ool(const ResArgs& a, hipStream_t s);   // reservoir_stream.hip
+// shapes the split-J kernels are built for, and those whose fp32 fragments exceed the LDS and stream from the workspace
+constexpr bool splitj_built(int JT, int NKX) { return JT % 4 == 0 && splitj_lds_bytes(JT, NKX) <= kLdsLimit; }
+constexpr bool stream_built(int JT, int NKX) { return packed_floats(JT, NKX) * 4 > kLdsLimit && JT % 4 == 0 && NKX % 4 == 0; }
 
 #include "reservoir_splitj_bf3.h"
 
-// experiment knobs (SGP_TUNE, read once): res_splitj_max = largest tile count served by the split-J kernel
-// alone, res_tail = 0 disables the exact deal + split-J tail of large problems
+template <int JT, int NKX> ResKernel resolve_stream_ool(const ResPart& p);   // reservoir_stream.hip
 
-template <int JT, int NKX>
-int launch_splitj(const ResArgs& a, int n_tiles, hipStream_t s) {
-    ResArgs b = a;
-    b.n_tiles = n_tiles;
-    const bool ov = (a.R % 4 == 0) && (a.ors % 4 == 0) && (a.oss % 4 == 0) && sgp::aligned16(a.out);
-    if constexpr (sjbf3_supported(JT, NKX) && sjbf3_lds_bytes(JT, NKX) <= kLdsLimit) {
-        // three-piece bf16 products (reservoir_splitj_bf3.h): the step is no longer bound by the fp32 matrix pipe
-        if (a.wp_bf3) {
-            void (*kern)(ResArgs);
-            if (a.act == SGP_ACT_TANH) kern = ov ? reservoir_layer_splitj_bf3<JT, NKX, true, SGP_ACT_TANH> : reservoir_layer_splitj_bf3<JT, NKX, false, SGP_ACT_TANH>;
-            else kern = ov ? reservoir_layer_splitj_bf3<JT, NKX, true, -1> : reservoir_layer_splitj_bf3<JT, NKX, false, -1>;
-            const int bytes = (int)sjbf3_lds_bytes(JT, NKX);
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return sgp::fail((int)e, "reservoir: LDS opt-in: %s", hipGetErrorString(e));
-            hipLaunchKernelGGL(kern, dim3(n_tiles, a.n_pieces > 1 ? a.n_pieces : 1), dim3(256), (size_t)bytes, s, b);
-            return sgp::check_launch("reservoir_layer_splitj_bf3");
+// The kernel instance of one plan part.  plan_reservoir only asks for what is built (the same conditions select it);
+// nullptr = it did not, which the caller reports.
+template <int JT, int NKX, int NT>
+ResKernel resolve_layer(const ResPart& p) {
+    if constexpr (bf3_supported(JT, NKX)) {
+        if (p.form == kFormBf3) {
+            if constexpr (NT == 2) {
+                if (p.pair) return p.h16 ? reservoir_layer_bf3<JT, NKX, NT, true, true> : reservoir_layer_bf3<JT, NKX, NT, true>;
+            }
+            return p.h16 ? reservoir_layer_bf3<JT, NKX, NT, false, true> : reservoir_layer_bf3<JT, NKX, NT>;
         }
     }
-    if (wants_pieces(a)) return sgp::fail(SGP_EUNSUP, "reservoir: time pieces / predicate need the split-J bf16-piece kernel");
-    auto kern = ov ? reservoir_layer_splitj<JT, NKX, true> : reservoir_layer_splitj<JT, NKX, false>;
-    const int bytes = (int)splitj_lds_bytes<JT, NKX>();
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return sgp::fail((int)e, "reservoir: LDS opt-in: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(256), (size_t)bytes, s, b);
-    return sgp::check_launch("reservoir_layer_splitj");
+    if (p.form != kFormLayer) return nullptr;
+    constexpr bool kLds = packed_floats(JT, NKX) * 4 <= kLdsLimit;
+    if (p.xvec && p.ovec) return reservoir_layer<JT, NKX, NT, kLds, true, true>;
+    return p.ovec ? reservoir_layer<JT, NKX, NT, kLds, false, true> : reservoir_layer<JT, NKX, NT, kLds, false, false>;
 }
 
 template <int JT, int NKX>
-int launch_nt(const ResArgs& a, hipStream_t s) {
-    const int n_tiles = (a.N + 15) / 16;
-    constexpr bool kSplitj = JT % 4 == 0 && splitj_lds_bytes<JT, NKX>() <= kLdsLimit;
-    if constexpr (kSplitj) {
-        // up to 2 workgroups per CU.  (Three per CU -- 513-768 tiles in one round, which the 3-deep ring
-        // makes possible at F = R = 64 -- measured slower than one single-tile wave per SIMD: N = 10 000,
-        // 1.53 vs 1.37 ms per 512 steps; SGP_RES_SPLITJ_MAX=768 selects it.)
-        static const int splitj_max = (int)sgp::tune("res_splitj_max", 512);
-        if (n_tiles <= splitj_max)
-            return launch_splitj<JT, NKX>(a, n_tiles, s);
-    }
-    if (wants_pieces(a)) return sgp::fail(SGP_EUNSUP, "reservoir: time pieces / predicate serve graphs of <= 512 node tiles");
-    if constexpr (JT <= 4 && kSplitj) {
-        // Large N: 1024 SIMDs x `per` tiles exactly (reservoir_layer's exact deal), and the L < 1024
-        // tiles that are left as a split-J tail: 4 SIMDs share a tile there, a workgroup steps through
-        // T in ~0.7 us per step -- a fraction of the per + 1'th tile that the busiest SIMDs would
-        // otherwise carry while the others idle (N = 100k: 6250 tiles = 6.1 per SIMD, 7 on the busiest).
-        static const int tail = (int)sgp::tune("res_tail", 1);
-        const int per = n_tiles / 1024, left = n_tiles - per * 1024;
-        if (tail && per >= 1 && per <= 8 && left <= 512) {
-            ResArgs m = a;
-            m.N = left ? per * 1024 * 16 : a.N;
-            m.tiles_per_wave = per;
-            if (!left) return per > 4 ? launch_layer<JT, NKX, 2>(m, s) : launch_layer<JT, NKX, 1>(m, s);
-            ResArgs t = a;
-            const long long n0 = (long long)per * 1024 * 16;
-            t.x = a.x + n0 * a.xrs;
-            t.out = a.out + n0 * a.ors;
-            if (a.h_state) t.h_state = a.h_state + n0 * a.R;
-            t.N = a.N - (int)n0;
-            // the tail is a chain of T short steps on `left` <= 512 workgroups (1.3 ms per 1024 steps whatever their
-            // number): it goes onto a side lane and runs beside the main part (its workgroups fit next to the main
-            // part's one workgroup per CU: 4 waves and ~50 KB of LDS each)
-            static const int beside = (int)sgp::tune("res_tail_beside", 1);
-            sgp::SideLane* lane = beside ? sgp::side_lane() : nullptr;
-            if (lane && lane->fork(s)) {
-                int rc_t = launch_splitj<JT, NKX>(t, left, lane->stream);
-                int rc = per > 4 ? launch_layer<JT, NKX, 2>(m, s) : launch_layer<JT, NKX, 1>(m, s);
-                if (!lane->join(s)) return sgp::fail(SGP_EINVAL, "reservoir: side lane join failed");
-                return rc ? rc : rc_t;
+ResKernel resolve(const ResPart& p) {
+    if constexpr (splitj_built(JT, NKX)) {
+        if (p.form == kFormSplitj) return p.ovec ? reservoir_layer_splitj<JT, NKX, true> : reservoir_layer_splitj<JT, NKX, false>;
+        if constexpr (sjbf3_supported(JT, NKX) && sjbf3_lds_bytes(JT, NKX) <= kLdsLimit) {
+            if (p.form == kFormSplitjBf3) {
+                if (p.act_tanh) return p.ovec ? reservoir_layer_splitj_bf3<JT, NKX, true, SGP_ACT_TANH> : reservoir_layer_splitj_bf3<JT, NKX, false, SGP_ACT_TANH>;
+                return p.ovec ? reservoir_layer_splitj_bf3<JT, NKX, true, -1> : reservoir_layer_splitj_bf3<JT, NKX, false, -1>;
             }
-            int rc = per > 4 ? launch_layer<JT, NKX, 2>(m, s) : launch_layer<JT, NKX, 1>(m, s);
-            if (rc) return rc;
-            return launch_splitj<JT, NKX>(t, left, s);
         }
     }
+    if constexpr (stream_built(JT, NKX)) {
+        if (p.form == kFormStream || p.form == kFormStream8 || p.form == kFormStreamBf3) return resolve_stream_ool<JT, NKX>(p);
+    }
     if constexpr (JT <= 4) {
-        if (n_tiles > 4096) return launch_layer<JT, NKX, 2>(a, s);
+        if (p.nt == 2) return resolve_layer<JT, NKX, 2>(p);
     }
-    if constexpr (packed_floats(JT, NKX) * 4 > kLdsLimit && JT % 4 == 0 && NKX % 4 == 0) {
-        // (exact widths: the stream kernel carries no feature masks)
-        const bool vec = (a.xrs % 4 == 0) && (a.xss % 4 == 0) && sgp::aligned16(a.x) &&
-                         (a.ors % 4 == 0) && (a.oss % 4 == 0) && sgp::aligned16(a.out);
-        if (n_tiles >= 2048 && a.F == 4 * NKX && a.R == 16 * JT && vec) return launch_stream_ool<JT, NKX>(a, s);
-    }
-    return launch_layer<JT, NKX, 1>(a, s);
+    return p.nt == 1 ? resolve_layer<JT, NKX, 1>(p) : nullptr;
 }
 
 template <int JT>
-int launch_nkx(const ResArgs& a, int nkx, hipStream_t s) {
+ResKernel resolve_nkx(const ResPart& p, int nkx) {
     switch (nkx) {
-        case 1: return launch_nt<JT, 1>(a, s);
-        case 2: return launch_nt<JT, 2>(a, s);
-        case 4: return launch_nt<JT, 4>(a, s);
-        case 8: return launch_nt<JT, 8>(a, s);
-        case 16: return launch_nt<JT, 16>(a, s);
-        case 32: return launch_nt<JT, 32>(a, s);
-        case 64: return launch_nt<JT, 64>(a, s);
+        case 1: return resolve<JT, 1>(p);
+        case 2: return resolve<JT, 2>(p);
+        case 4: return resolve<JT, 4>(p);
+        case 8: return resolve<JT, 8>(p);
+        case 16: return resolve<JT, 16>(p);
+        case 32: return resolve<JT, 32>(p);
+        case 64: return resolve<JT, 64>(p);
     }
-    return sgp::fail(SGP_EUNSUP, "reservoir: input size not supported");
+    return nullptr;
 }
 
 

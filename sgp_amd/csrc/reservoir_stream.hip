@@ -4,12 +4,10 @@
 #define SGP_RES_STREAM_TU
 #include "reservoir_impl.h"
 namespace sgp_res {
-template <> int launch_stream_ool<8, 64>(const ResArgs& a, hipStream_t s) { return launch_stream<8, 64>(a, s); }
-template <> int launch_stream_ool<16, 1>(const ResArgs&, hipStream_t) { return sgp::fail(SGP_EUNSUP, "unreachable"); }
-template <> int launch_stream_ool<16, 2>(const ResArgs&, hipStream_t) { return sgp::fail(SGP_EUNSUP, "unreachable"); }
-template <> int launch_stream_ool<16, 4>(const ResArgs& a, hipStream_t s) { return launch_stream<16, 4>(a, s); }
-template <> int launch_stream_ool<16, 8>(const ResArgs& a, hipStream_t s) { return launch_stream<16, 8>(a, s); }
-template <> int launch_stream_ool<16, 16>(const ResArgs& a, hipStream_t s) { return launch_stream<16, 16>(a, s); }
-template <> int launch_stream_ool<16, 32>(const ResArgs& a, hipStream_t s) { return launch_stream<16, 32>(a, s); }
-template <> int launch_stream_ool<16, 64>(const ResArgs& a, hipStream_t s) { return launch_stream<16, 64>(a, s); }
+template <> ResKernel resolve_stream_ool<8, 64>(const ResPart& p) { return resolve_stream<8, 64>(p); }
+template <> ResKernel resolve_stream_ool<16, 4>(const ResPart& p) { return resolve_stream<16, 4>(p); }
+template <> ResKernel resolve_stream_ool<16, 8>(const ResPart& p) { return resolve_stream<16, 8>(p); }
+template <> ResKernel resolve_stream_ool<16, 16>(const ResPart& p) { return resolve_stream<16, 16>(p); }
+template <> ResKernel resolve_stream_ool<16, 32>(const ResPart& p) { return resolve_stream<16, 32>(p); }
+template <> ResKernel resolve_stream_ool<16, 64>(const ResPart& p) { return resolve_stream<16, 64>(p); }
 }

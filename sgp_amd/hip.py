@@ -6,6 +6,7 @@ tested on a CPU box), but the first call that needs a kernel raises
 ``RuntimeError`` if the shared object is missing or no MI355X is visible.
 """
 import ctypes
+import json
 import os
 import subprocess
 
@@ -72,6 +73,10 @@ SIGNATURES = {
                                                 c_p, c_p,
                                                 c_i32, c_i32, c_i32, c_i64, c_i64, c_i32,
                                                 c_i32, c_i32, c_i32, c_p, c_i32, c_p]),
+    "sgp_reservoir_describe": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_i32,
+                                              c_i32, c_i32, c_i32,
+                                              c_i64, c_i64, c_i32, c_i64, c_i64, c_i32,
+                                              c_p, c_i64]),
     "sgp_reservoir_fused_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "sgp_reservoir_fused_supported": (c_i32, [c_i32, c_i32, c_i32]),
     "sgp_reservoir_fused_f32": (ctypes.c_int, [c_p, c_i64, c_i64,
@@ -581,6 +586,15 @@ def _workspace(device, nbytes):
     return ws
 
 
+def _layer_weights(weights, F, R, stacked=False):
+    """Every layer's ``(w_ih, w_hh, b)``: contiguous float32 CUDA ``[R, F]`` (deeper layers of a stack: ``[R, R]``),
+    ``[R, R]``, ``[R]``."""
+    for l, layer in enumerate(weights):
+        for name, w, shape in zip(("w_ih", "w_hh", "b"), layer, ((R, F if l == 0 else R), (R, R), (R,))):
+            if tuple(w.shape) != shape or w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous():
+                raise ValueError(f"{f'layer {l} ' if stacked else ''}{name}: expected contiguous float32 CUDA {shape}")
+
+
 def reservoir_fused_supported(F, R, L):
     """True when all L layers fit the fused multi-layer kernel (sgp_reservoir_fused_f32)."""
     return bool(load().sgp_reservoir_fused_supported(F, R, L))
@@ -598,11 +612,7 @@ def reservoir_stack(x, weights, alphas, activation, out, h_state=None, col_sums=
     op, ors, oss = _view3(out, "out")
     T, N, F = x.shape
     L, R = len(weights), weights[0][1].shape[0]
-    for l, (w_ih, w_hh, b) in enumerate(weights):
-        for name, w, shape in (("w_ih", w_ih, (R, F if l == 0 else R)), ("w_hh", w_hh, (R, R)), ("b", b, (R,))):
-            if tuple(w.shape) != shape or w.dtype != torch.float32 or not w.is_cuda \
-                    or not w.is_contiguous():
-                raise ValueError(f"layer {l} {name}: expected contiguous float32 CUDA {shape}")
+    _layer_weights(weights, F, R, stacked=True)
     if out.shape[0] != T or out.shape[1] != N or out.shape[2] != L * R:
         raise ValueError("out: expected [T, N, L*R]")
     if h_state is not None and (tuple(h_state.shape) != (L, N, R) or not h_state.is_contiguous()):
@@ -628,33 +638,14 @@ def reservoir_stack(x, weights, alphas, activation, out, h_state=None, col_sums=
     return out
 
 
-@_on_device
 def reservoir_layer(x, w_ih, w_hh, b, alpha, activation, out, h_state=None):
-    """One leaky-ESN layer over all T steps: x[T, N, F] -> out[T, N, R] (views allowed)."""
-    lib = require_gpu()
-    xp, xrs, xss = _view3(x, "x")
-    op, ors, oss = _view3(out, "out")
-    T, N, F = x.shape
-    R = w_hh.shape[0]
-    for name, w, shape in (("w_ih", w_ih, (R, F)), ("w_hh", w_hh, (R, R)), ("b", b, (R,))):
-        if tuple(w.shape) != shape or w.dtype != torch.float32 or not w.is_cuda \
-                or not w.is_contiguous():
-            raise ValueError(f"{name}: expected contiguous float32 CUDA {shape}")
-    if out.shape[0] != T or out.shape[1] != N or out.shape[2] != R:
+    """One leaky-ESN layer over all T steps: x[T, N, F] -> out[T, N, R] (views allowed): one time piece."""
+    T, N, R = x.shape[0], x.shape[1], w_hh.shape[0]
+    if out.dim() == 3 and (out.shape[0] != T or out.shape[1] != N or out.shape[2] != R):
         raise ValueError("out: expected [T, N, R]")
-    wsb = lib.sgp_reservoir_workspace_bytes(F, R)
-    if wsb < 0:
-        raise NotImplementedError(f"reservoir kernel supports input/hidden sizes <= 256 "
-                                  f"(got F={F}, R={R})")
-    ws = _workspace(x.device, wsb)
     if h_state is not None and (tuple(h_state.shape) != (N, R) or not h_state.is_contiguous()):
         raise ValueError("h_state: expected contiguous [N, R]")
-    _check(lib.sgp_reservoir_f32(
-        xp, xrs, xss, w_ih.data_ptr(), w_hh.data_ptr(), b.data_ptr(),
-        float(alpha), ACT_CODES[activation], op, ors, oss,
-        h_state.data_ptr() if h_state is not None else None, ws.data_ptr(),
-        T, N, F, R, _stream(x)), "sgp_reservoir_f32")
-    return out
+    return reservoir_pieces(x, w_ih, w_hh, b, alpha, activation, out, h_state, T, T, 0, 0)
 
 
 @_on_device
@@ -662,15 +653,14 @@ def reservoir_pieces(x, w_ih, w_hh, b, alpha, activation, out, states, t_piece, 
                      no_store=False, pred=None):
     """``sgp_reservoir_pieces_f32``: ``states[P, N, R]`` (contiguous) holds every piece's initial state and receives its
     final one; piece p reads ``x`` / writes ``out`` at p times the piece strides (in floats) from the given views'
-    first element.  ``states[N, R]`` or None with one piece: the sequential layer, optionally under ``pred``."""
+    first element.  ``states[N, R]`` or None with one piece: the sequential layer, optionally under ``pred``.
+    Which kernels a call runs: ``reservoir_plan``."""
     lib = require_gpu()
     xp, xrs, xss = _view3(x, "x")
     op, ors, oss = _view3(out, "out")
     N, F = x.shape[1], x.shape[2]
     R = w_hh.shape[0]
-    for name, w, shape in (("w_ih", w_ih, (R, F)), ("w_hh", w_hh, (R, R)), ("b", b, (R,))):
-        if tuple(w.shape) != shape or w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous():
-            raise ValueError(f"{name}: expected contiguous float32 CUDA {shape}")
+    _layer_weights([(w_ih, w_hh, b)], F, R)
     P = 1 if states is None or states.dim() == 2 else states.shape[0]
     if states is not None and (not states.is_contiguous() or tuple(states.shape[-2:]) != (N, R)):
         raise ValueError("states: expected contiguous [P, N, R] (or [N, R])")
@@ -684,6 +674,23 @@ def reservoir_pieces(x, w_ih, w_hh, b, alpha, activation, out, states, t_piece, 
         int(t_piece), int(t_last), P, int(x_piece_stride), int(out_piece_stride), int(bool(no_store)),
         N, F, R, *_pred(pred), _stream(x)), "sgp_reservoir_pieces_f32")
     return out
+
+
+def reservoir_plan(F, R, N, T=2, activation="tanh", alpha=0.9, state=False, n_pieces=1, no_store=False, pred=False,
+                   x_strides=None, x_align=0, out_strides=None, out_align=0):
+    """What ``reservoir_layer`` / ``reservoir_pieces`` launch for such a call, in launch order, from the library's one
+    planner (``plan_reservoir``, csrc/reservoir.hip; no GPU needed): a list of dicts, ``{"kernel": name}`` for the weight
+    packs and the initial-state test, then one per layer-kernel launch with ``kernel`` (template arguments included),
+    ``nodes`` (range), ``grid`` (x, y), ``block``, ``lds`` (dynamic bytes), ``pred`` (none / caller / state_inside /
+    state_outside) and ``lane`` (main / side).  ``x_strides`` / ``out_strides``: (row, step) strides in floats, default
+    contiguous; ``*_align``: the first element's address modulo 16.  Requests the library refuses raise as the call does."""
+    xrs, xss = x_strides or (F, N * F)
+    ors, oss = out_strides or (R, N * R)
+    buf = ctypes.create_string_buffer(4096)
+    _check(load().sgp_reservoir_describe(F, R, N, T, ACT_CODES[activation], float(alpha), int(bool(state)), int(n_pieces),
+                                         int(bool(no_store)), int(bool(pred)), xrs, xss, x_align, ors, oss, out_align,
+                                         buf, len(buf)), "sgp_reservoir_describe")
+    return [json.loads(line) for line in buf.value.decode().splitlines()]
 
 
 # ---------------------------------------------------------------- DynGESN

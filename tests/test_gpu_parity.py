@@ -328,7 +328,7 @@ def test_reservoir_wide_streamed_weights(act, f, r):
 @pytest.mark.parametrize("n,f,r", [(20007, 5, 64), (40000, 64, 64), (16384 + 16 * 600, 3, 32), (131072, 4, 16)])
 def test_reservoir_exact_deal_and_split_j_tail(n, f, r):
     """Large N: 1024 SIMDs x per tiles in the main kernel (one 16-wave workgroup per CU) + the tiles that
-    are left in the split-J kernel (launch_nt, reservoir_impl.h) -- against the oracle, ragged last
+    are left in the split-J kernel (plan_reservoir, reservoir.hip) -- against the oracle, ragged last
     tile included, and the state carried across two calls (main part and tail share h_state)."""
     torch.manual_seed(n % 97)
     t = 5
