@@ -458,6 +458,42 @@ int sgp_reservoir_fused_sums_f32(const float* x, int64_t x_row_stride, int64_t x
                                  int32_t T, int32_t N, int32_t F, int32_t R, int32_t L,
                                  sgp_stream_t stream);
 
+/* Windowed reservoir, LAST STATE ONLY: the call shape of the echo-state baseline (lib/nn/models/esn_model.py:41-43:
+ * maybe_cat_exog, then lib/nn/reservoir/reservoir.py:158-186 with return_last_state=True).  For M = B * N independent
+ * sequences of S steps and L layers
+ *     h_l[t] = (1 - a_l) h_l[t-1] + a_l act(W_ih,l x_l[t] + b_l + W_hh,l h_l[t-1]),  x_0[t] = [x[t] | u[t]],  x_l[t] = h_{l-1}[t]
+ * only h_l[S-1] is written: out[(b * N + n) * out_row_stride + l * R + j] (the layer-major order of reservoir.py:181-183).
+ *   x: element (b, t, n, k) at x[b * x_batch_stride + (start_b + t) * x_step_stride + n * x_node_stride + k], k < Fx
+ *      (the reference's [b, s, n, f] batch is read where it lies; no `s (b n) f` copy)
+ *   u: optional second source with its own strides: features Fx .. Fx + Fu - 1 of layer 0 (NULL with Fu = 0: none).
+ *      Node stride 0 is the global exogenous series of maybe_cat_exog (tsl/nn/utils/utils.py:56-75, u [b, s, f]);
+ *      no concatenated tensor is built.
+ *   step_start: optional [B] int32, start_b above (NULL: 0).  With batch stride 0 the windows of a resident series
+ *      [T, N, F] are read in place, for x and u alike; the caller keeps start_b + S <= T.
+ *   w_ih / w_hh / b / alpha: HOST arrays of length L as for sgp_reservoir_fused_f32 (w_ih[0]: [R, Fx + Fu])
+ *   h0: optional [L, M, R] contiguous initial states, read only; NULL = zeros (reservoir.py:162-164)
+ *   workspace: sgp_reservoir_window_workspace_bytes(Fx + Fu, R, L, S, M) bytes, 16-byte aligned.  Its head is the
+ *      weights in fragment order: packed != 0 says an earlier call with the same weights and (Fx + Fu, R, L) left them
+ *      there and skips the packing (w_ih / w_hh / b may then be NULL).
+ * sgp_reservoir_window_supported: 0 = outside the domain (Fx + Fu <= 256, R <= 256, L <= 8: SGP_EUNSUP, run the
+ * sequence entries); 1 = all layers in ONE launch, every state in registers for the whole window, nothing of size
+ * S * M * R in memory (always when L * R <= 256, and for any single layer); 2 = layer by layer with one [S, M, R]
+ * intermediate in the workspace that layer l + 1 overwrites row by row with its own states (L > 1 with L * R > 256
+ * beyond 24 register tiles of 16 features).
+ * A wave owns 16 sequences; weights in LDS for R <= 64 while the pack fits it, else streamed from the packed buffer
+ * through L2.  Any M, S >= 1,
+ * every activation code, any alpha.  Arithmetic: exact fp32 products (v_mfma_f32_16x16x4_f32), fp32 accumulation. */
+int32_t sgp_reservoir_window_supported(int32_t F, int32_t R, int32_t L);
+int64_t sgp_reservoir_window_workspace_bytes(int32_t F, int32_t R, int32_t L, int32_t S, int64_t M);
+int sgp_reservoir_window_f32(const float* x, int64_t x_batch_stride, int64_t x_step_stride, int64_t x_node_stride, int32_t Fx,
+                             const float* u, int64_t u_batch_stride, int64_t u_step_stride, int64_t u_node_stride, int32_t Fu,
+                             const int32_t* step_start,
+                             const float* const* w_ih, const float* const* w_hh, const float* const* b,
+                             const double* alpha, int32_t act,
+                             const float* h0, float* out, int64_t out_row_stride,
+                             void* workspace, int32_t packed,
+                             int32_t B, int32_t N, int32_t S, int32_t R, int32_t L, sgp_stream_t stream);
+
 /* --------------------------------------------------------------- DynGESN ---
  * The graph echo-state baseline (lib/nn/reservoir/graph_reservoir.py:85-93, stepped by
  * tsl/nn/blocks/encoders/gcrnn.py:67-93):

@@ -91,6 +91,15 @@ SIGNATURES = {
                                                     c_p, c_i64, c_i64,
                                                     c_p, c_p, c_p,
                                                     c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
+    "sgp_reservoir_window_supported": (c_i32, [c_i32, c_i32, c_i32]),
+    "sgp_reservoir_window_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i64]),
+    "sgp_reservoir_window_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_i32,
+                                                c_p, c_i64, c_i64, c_i64, c_i32,
+                                                c_p,
+                                                c_p, c_p, c_p, c_p, c_i32,
+                                                c_p, c_p, c_i64,
+                                                c_p, c_i32,
+                                                c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sgp_gesn_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "sgp_gesn_tune": (ctypes.c_int, [c_i32]),
     "sgp_gesn_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i32,
@@ -691,6 +700,81 @@ def reservoir_plan(F, R, N, T=2, activation="tanh", alpha=0.9, state=False, n_pi
                                          int(bool(no_store)), int(bool(pred)), xrs, xss, x_align, ors, oss, out_align,
                                          buf, len(buf)), "sgp_reservoir_describe")
     return [json.loads(line) for line in buf.value.decode().splitlines()]
+
+
+def reservoir_window_mode(F, R, L):
+    """0: outside ``sgp_reservoir_window_f32``'s domain; 1: all layers in one launch, no ``[S, M, R]`` anywhere;
+    2: layer by layer over one ``[S, M, R]`` intermediate in the workspace (no GPU needed)."""
+    return int(load().sgp_reservoir_window_supported(int(F), int(R), int(L)))
+
+
+def reservoir_window_workspace_bytes(F, R, L, S, M):
+    return int(load().sgp_reservoir_window_workspace_bytes(int(F), int(R), int(L), int(S), int(M)))
+
+
+def _view_bsn(t, name, B, S, windows):
+    """(ptr, batch, step, node strides, features) of ``[b, s, n, f]`` / ``[b, s, f]`` (node stride 0), or -- ``windows``
+    -- of a series ``[T, n, f]`` / ``[T, f]`` (batch stride 0)."""
+    if t.dtype != torch.float32 or not t.is_cuda or t.dim() not in ((2, 3) if windows else (3, 4)):
+        raise ValueError(f"{name}: expected a float32 CUDA tensor, got {tuple(t.shape)} {t.dtype} {t.device}")
+    if t.shape[-1] > 1 and t.stride(-1) != 1:
+        raise ValueError(f"{name}: feature stride must be 1")
+    per_node = t.dim() == (3 if windows else 4)
+    ns = t.stride(-2) if per_node else 0
+    if windows:
+        return t.data_ptr(), 0, t.stride(0), ns, t.shape[-1]
+    if t.shape[0] != B or t.shape[1] != S:
+        raise ValueError(f"{name}: expected [{B}, {S}, ...], got {tuple(t.shape)}")
+    return t.data_ptr(), t.stride(0), t.stride(1), ns, t.shape[-1]
+
+
+@_on_device
+def reservoir_window(x, weights, alphas, activation, out, u=None, h0=None, step_start=None, window=None,
+                     workspace=None, packed=False):
+    """``sgp_reservoir_window_f32``: the last state of every layer for each of the ``b * n`` windows, ``out [b, n, L*R]``
+    (contiguous).  ``x [b, s, n, f]`` (any batch / step / node strides) with ``u [b, s, (n,) f]``; or, with
+    ``step_start [b]`` (int32) and ``window``, a series ``x [T, n, f]`` with ``u [T, (n,) f]`` whose windows are read in
+    place.  ``weights``: per layer ``(w_ih, w_hh, b)`` on the device; ``h0 [L, b*n, R]``.  ``workspace``: a float32
+    tensor of at least ``reservoir_window_workspace_bytes`` (default: the per-stream scratch); ``packed``: it already
+    holds these weights' pack from an earlier call.  With ``step_start`` the CALLER owns the range:
+    every ``step_start[b] + window <= T`` (``Reservoir.last_state`` checks it); here only ``window <= T``."""
+    lib = require_gpu()
+    L, R = len(weights), weights[0][1].shape[0]
+    windows = step_start is not None
+    if windows:
+        if step_start.dtype != torch.int32 or not step_start.is_cuda or not step_start.is_contiguous():
+            raise ValueError("step_start: expected a contiguous int32 CUDA tensor")
+        B, S, N = step_start.numel(), int(window), x.shape[1]
+        if not 1 <= S <= x.shape[0] or (u is not None and u.shape[0] != x.shape[0]):
+            raise ValueError(f"window must lie in [1, {x.shape[0]}] and u must have x's steps")
+    else:
+        B, S, N = x.shape[0], x.shape[1], x.shape[2]
+    xp, xbs, xss, xns, Fx = _view_bsn(x, "x", B, S, windows)
+    if (x.dim() == 2) if windows else (x.dim() == 3):
+        raise ValueError("x: the node axis is required")
+    up, ubs, uss, uns, Fu = (None, 0, 0, 0, 0) if u is None else _view_bsn(u, "u", B, S, windows)
+    if u is not None and uns and u.shape[-2] != N:
+        raise ValueError(f"u: expected {N} nodes, got {u.shape[-2]}")
+    F, M = Fx + Fu, B * N
+    _layer_weights(weights, F, R, stacked=True)
+    if tuple(out.shape) != (B, N, L * R) or not out.is_contiguous() or out.dtype != torch.float32 or not out.is_cuda:
+        raise ValueError(f"out: expected contiguous float32 CUDA [{B}, {N}, {L * R}]")
+    if h0 is not None and (tuple(h0.shape) != (L, M, R) or not h0.is_contiguous() or h0.dtype != torch.float32):
+        raise ValueError(f"h0: expected contiguous float32 [{L}, {M}, {R}]")
+    wsb = lib.sgp_reservoir_window_workspace_bytes(F, R, L, S, M)
+    if wsb < 0:
+        raise NotImplementedError(f"windowed reservoir kernel: F={F}, R={R}, L={L} not supported")
+    ws = workspace if workspace is not None else _workspace(x.device, wsb)
+    if ws.numel() * ws.element_size() < wsb:
+        raise ValueError(f"workspace: {wsb} bytes needed")
+    ptrs = lambda k: (ctypes.c_void_p * L)(*[w[k].data_ptr() for w in weights])
+    al = (ctypes.c_double * L)(*[float(a) for a in alphas])
+    _check(lib.sgp_reservoir_window_f32(
+        xp, xbs, xss, xns, Fx, up, ubs, uss, uns, Fu, step_start.data_ptr() if windows else None,
+        ptrs(0), ptrs(1), ptrs(2), al, ACT_CODES[activation],
+        h0.data_ptr() if h0 is not None else None, out.data_ptr(), L * R, ws.data_ptr(), int(bool(packed)),
+        B, N, S, R, L, _stream(x)), "sgp_reservoir_window_f32")
+    return out
 
 
 # ---------------------------------------------------------------- DynGESN

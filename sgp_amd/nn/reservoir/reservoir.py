@@ -320,6 +320,116 @@ class Reservoir(nn.Module):
             return out[:, -1].to(dev)
         return out.contiguous().to(dev)
 
+    # ---- windows: the last state only (the ESN baseline's call, lib/nn/models/esn_model.py:41-43)
+    # "auto": the window kernel where it measured at least as fast as the sequence path (``_window_pays``);
+    # "kernel": wherever it is built (tests, tools/probe_esn_model.py); "sequence": never.
+    window_dispatch = "auto"
+    last_window_path = None          # "kernel" / "sequence": what the last ``last_state`` call ran
+
+    def _window_pack(self, device, F):
+        """Device weights, activation code and their fragment-order pack (``[pack bytes]`` float32), per (parameter
+        versions, device); ``fresh`` says the kernel still has to fill the pack (first call after a change).  Only the
+        pack is kept: a layer-by-layer call takes its ``[S, M, R]`` intermediate from the per-stream scratch."""
+        L, R = len(self.reservoir_layers), self.hidden_size
+        params = [p for layer in self.reservoir_layers for p in (layer.w_ih, layer.w_hh, layer.b_ih) if p is not None]
+        key = tuple((p.data_ptr(), p._version) for p in params) + (str(device), F)
+        hit = getattr(self, "_win_cache", None)
+        fresh = hit is None or hit[0] != key
+        if fresh:
+            weights = [layer._device_weights(device) for layer in self.reservoir_layers]
+            act = ("tanh_rel" if any(l.kernel_activation() == "tanh_rel" for l in self.reservoir_layers)
+                   else self.reservoir_layers[0].activation_name)
+            pack = torch.empty(hip.reservoir_window_workspace_bytes(F, R, L, 0, 0) // 4 + 4, dtype=torch.float32,
+                               device=device)
+            hit = self._win_cache = (key, weights, act, pack)
+        return hit[1], hit[2], hit[3], fresh
+
+    @staticmethod
+    def _window_pays(R, L, M):
+        """Shape classes where the sequence path measured faster than the window kernel beyond run-to-run spread keep it
+        under ``window_dispatch = "auto"`` (tools/probe_esn_model.py; table, mechanisms and which bounds are
+        extrapolated: DESIGN 4.1e).  By register tiles of 16 features per layer, the unit the kernels are built in."""
+        jt = (R + 15) // 16
+        if jt > 8:                      # wider than 128: a single layer loses 6-13 %, stacks win 2.1-2.6x
+            return L > 1
+        if jt > 4:                      # 64 < R <= 128: one wave per SIMD -- wins while the 1 024 SIMDs hold all tiles
+            return 4096 < M <= 16384
+        if jt > 2 and L >= 3:           # 32 < R <= 64, deep: few sequences cannot pay for each workgroup's LDS fill
+            return M > 4096
+        return True
+
+    def last_state(self, x, u=None, h0=None, step_start=None, window=None):
+        """``forward(cat([x, u]), h0, return_last_state=True)`` -> ``[b, n, L*R]`` without the sequence: one launch of
+        ``sgp_reservoir_window_f32`` reads ``x [b, s, n, f]`` (any batch / step / node strides) and ``u [b, s, f]`` or
+        ``[b, s, n, f]`` where they lie, keeps every layer's state on the compute unit for the whole window and stores
+        the last one (``L * R <= 256`` and any single layer; deeper-and-wider stacks run layer by layer over one
+        ``[s, b n, R]`` intermediate -- ``hip.reservoir_window_mode``).  With ``step_start [b]`` and ``window``, ``x`` is
+        a series ``[T, n, f]`` (``u``: ``[T, f]`` or ``[T, n, f]``) resident on the device and batch item ``b`` is its
+        steps ``step_start[b] .. + window - 1``, read in place; starts outside ``[0, T - window]`` raise ``IndexError``
+        here, before any launch (one host sync).  Outside the kernel's domain (more than 8 layers; more than
+        256 input or hidden features are outside the sequence kernels too) and, under ``window_dispatch = "auto"``, for the shapes of ``_window_pays`` the sequence path
+        runs instead (it allocates the ``[s, b n, L R]`` sequence); ``last_window_path`` says which one ran."""
+        windows = step_start is not None
+        dev = x.device
+        if not x.is_cuda:
+            hip.require_gpu()
+        to = lambda t: None if t is None else t.to("cuda" if not x.is_cuda else dev, torch.float32)
+        xg, ug = to(x), to(u)
+        if xg.shape[-1] > 1 and xg.stride(-1) != 1:
+            xg = xg.contiguous()
+        if ug is not None and ug.shape[-1] > 1 and ug.stride(-1) != 1:
+            ug = ug.contiguous()
+        L, R = len(self.reservoir_layers), self.hidden_size
+        F = xg.shape[-1] + (0 if ug is None else ug.shape[-1])
+        if F != self.input_size:
+            raise ValueError(f"expected {self.input_size} input features (x and u together), got {F}")
+        if windows:
+            T, S = xg.shape[0], int(window)
+            if ug is not None and ug.shape[0] != T:
+                raise ValueError(f"u has {ug.shape[0]} steps, x {T}")
+            if not 1 <= S <= T:
+                raise ValueError(f"window must lie in [1, {T}], got {window}")
+            step_start = torch.as_tensor(step_start).reshape(-1)
+            if step_start.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+                raise IndexError(f"step_start: tensors used as indices must be integer, got {step_start.dtype}")
+            if step_start.numel():
+                lo, hi = torch.stack(torch.aminmax(step_start.to(torch.int64))).tolist()
+                if lo < 0 or hi > T - S:
+                    raise IndexError(f"step_start out of range for windows of {S} in {T} steps (min {lo}, max {hi})")
+            st = step_start.to(xg.device, torch.int32).contiguous()
+            B, N = st.numel(), xg.shape[1]
+        else:
+            B, S, N = xg.shape[0], xg.shape[1], xg.shape[2]
+        if self.window_dispatch not in ("auto", "kernel", "sequence"):
+            raise ValueError(f"window_dispatch: 'auto', 'kernel' or 'sequence', got {self.window_dispatch!r}")
+        mode = hip.reservoir_window_mode(F, R, L) if S >= 1 else 0
+        if not mode or self.window_dispatch == "sequence" or \
+                (self.window_dispatch == "auto" and not self._window_pays(R, L, B * N)):
+            if windows:
+                idx = st.long()[:, None] + torch.arange(S, device=xg.device)[None]
+                xg = xg[idx]
+                ug = None if ug is None else ug[idx]
+            if ug is not None:
+                xg = torch.cat([xg, (ug if ug.dim() == 4 else ug[:, :, None]).expand(B, S, N, -1)], -1)
+            self.last_window_path = "sequence"
+            return self.forward(xg, h0, return_last_state=True).to(dev)
+        weights, act, pack, fresh = self._window_pack(xg.device, F)
+        ws = pack
+        if mode == 2:
+            # per-stream scratch [pack | S M R]: the cached pack is copied to its head (about 1 MB beside milliseconds)
+            ws = hip._workspace(xg.device, hip.reservoir_window_workspace_bytes(F, R, L, S, B * N))
+            if not fresh:
+                ws[:pack.numel() - 4].copy_(pack[:pack.numel() - 4])
+        state = None if h0 is None else h0.to(xg.device, torch.float32).reshape(L, B * N, R).contiguous()
+        out = torch.empty(B, N, L * R, dtype=torch.float32, device=xg.device)
+        hip.reservoir_window(xg, weights, [layer.alpha for layer in self.reservoir_layers], act, out, u=ug, h0=state,
+                             step_start=st if windows else None, window=S, workspace=ws,
+                             packed=not fresh)
+        if mode == 2 and fresh:
+            pack[:pack.numel() - 4].copy_(ws[:pack.numel() - 4])
+        self.last_window_path = "kernel"
+        return out.to(dev)
+
     def forward_prealloc(self, x, h0=None, return_last_state=False):
         """The reference's ``forward_prealloc`` (reservoir.py:131-156) is dead code that
         reads a not-yet-written slot as the previous state; the name is kept and mapped to

@@ -1,0 +1,149 @@
+"""ESNModel without a GPU (lib/nn/models/esn_model.py:9-59): seeded construction against the reference's recorded
+``state_dict`` (tests/golden/g11_esn_model_*.npz), parameter names / shapes / flags, checkpoints both ways, parser flags,
+argument errors, and the C ABI of the windowed reservoir entry."""
+import argparse
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, ROOT, golden_files
+from sgp_amd import hip
+from sgp_amd.nn.models import ESNModel
+
+FIXTURES = golden_files("g11_esn_model_")
+ENTRIES = ["sgp_reservoir_window_workspace_bytes", "sgp_reservoir_window_supported", "sgp_reservoir_window_f32"]
+
+
+def load(name):
+    z = np.load(f"{GOLDEN}/{name}", allow_pickle=False)
+    cfg = json.loads(str(z["config"]))
+    sd = {k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("sd/")}
+    return z, cfg, sd
+
+
+def test_fixtures_cover_the_three_cases():
+    assert FIXTURES == ["g11_esn_model_deep.npz", "g11_esn_model_noexog.npz", "g11_esn_model_traffic.npz"]
+    largest = max(os.path.getsize(f"{GOLDEN}/{f}") for f in golden_files("g10_"))
+    assert all(os.path.getsize(f"{GOLDEN}/{f}") < largest for f in FIXTURES)
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_seeded_construction_reproduces_reference_state_dict(name):
+    z, cfg, sd = load(name)
+    torch.manual_seed(int(z["seed"]))
+    m = ESNModel(**cfg)
+    got = m.state_dict()
+    assert list(got.keys()) == list(sd.keys())
+    for k, v in sd.items():
+        assert got[k].dtype == v.dtype and torch.equal(got[k], v), k
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_parameter_names_shapes_and_flags(name):
+    _, cfg, _ = load(name)
+    m = ESNModel(**cfg)
+    R, L, F = cfg["hidden_size"], cfg["rec_layers"], cfg["input_size"] + cfg["exog_size"]
+    want = {}
+    for i in range(L):
+        want[f"reservoir.reservoir_layers.{i}.w_ih"] = ((R, F if i == 0 else R), False)
+        want[f"reservoir.reservoir_layers.{i}.w_hh"] = ((R, R), False)
+        want[f"reservoir.reservoir_layers.{i}.b_ih"] = ((R,), False)
+    want["readout.readout.0.weight"] = ((cfg["output_size"] * cfg["horizon"], R * L), True)
+    want["readout.readout.0.bias"] = ((cfg["output_size"] * cfg["horizon"],), True)
+    got = {k: (tuple(p.shape), p.requires_grad) for k, p in m.named_parameters()}
+    assert got == want
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_load_state_dict_both_ways(name):
+    _, cfg, sd = load(name)
+    torch.manual_seed(99)
+    m = ESNModel(**cfg)
+    m.load_state_dict(sd)                                  # reference checkpoint -> this model (strict)
+    for k, v in m.state_dict().items():
+        assert torch.equal(v, sd[k]), k
+    torch.manual_seed(7)
+    other = ESNModel(**cfg)
+    keys = other.load_state_dict(m.state_dict())           # and back: the keys are exactly the reference's
+    assert not keys.missing_keys and not keys.unexpected_keys
+    assert set(m.state_dict()) == set(sd)
+
+
+def test_parser_flags_and_defaults():
+    p = ESNModel.add_model_specific_args(argparse.ArgumentParser())
+    a = p.parse_args([])
+    assert (a.hidden_size, a.rec_layers, a.spectral_radius, a.leaking_rate, a.density) == (32, 1, 0.9, 0.9, 0.7)
+    a = p.parse_args("--hidden-size 64 --rec-layers 3 --spectral-radius 0.8 --leaking-rate 0.7 --density 0.9".split())
+    assert (a.hidden_size, a.rec_layers, a.spectral_radius, a.leaking_rate, a.density) == (64, 3, 0.8, 0.7, 0.9)
+
+    class Tube(argparse.ArgumentParser):                   # a test_tube-like parser keeps options / tunable
+        seen = {}
+
+        def opt_list(self, *args, options=None, tunable=False, **kw):
+            self.seen[args[0]] = (options, tunable, kw["default"])
+            self.add_argument(*args, **kw)
+
+    ESNModel.add_model_specific_args(Tube())
+    assert Tube.seen == {"--hidden-size": ([16, 32, 64, 128, 256], True, 32), "--rec-layers": ([1, 2, 3], True, 1),
+                         "--spectral-radius": ([0.7, 0.8, 0.9], True, 0.9),
+                         "--leaking-rate": ([0.7, 0.8, 0.9], True, 0.9), "--density": ([0.7, 0.8, 0.9], True, 0.7)}
+
+
+def test_argument_errors():
+    kw = dict(input_size=2, hidden_size=16, output_size=1, rec_layers=1, horizon=3)
+    with pytest.raises(TypeError):
+        ESNModel(exog_size=None, **kw)                     # the reference cannot add None to input_size either
+    with pytest.raises(ValueError):
+        ESNModel(exog_size=0, activation="identity", **kw)   # the reference's quirk: identity raises
+    with pytest.raises(AssertionError):
+        ESNModel(exog_size=0, activation="gelu", **kw)
+    with pytest.raises(ValueError):
+        ESNModel(exog_size=0, **{**kw, "rec_layers": 0})
+    m = ESNModel(exog_size=2, **kw)
+    with pytest.raises(ValueError):
+        m(torch.zeros(2, 4, 5, 3))                         # wrong feature count (checked before any device work)
+    with pytest.raises(ValueError):
+        m(torch.zeros(2, 4, 5, 2))                         # exogenous input missing
+    with pytest.raises(ValueError):
+        m(torch.zeros(2, 4, 5, 2), torch.zeros(2, 4, 3))   # wrong exogenous width
+    with pytest.raises(RuntimeError, match="requires grad"):
+        m(torch.zeros(2, 4, 5, 2, requires_grad=True), torch.zeros(2, 4, 2))
+
+
+def test_header_declares_and_library_exports_the_window_entries():
+    header = open(os.path.join(ROOT, "include", "sgp_amd.h")).read()
+    lib = hip.load()
+    for name in ENTRIES:
+        assert re.search(rf"\b{name}\s*\(", header), name
+        assert name in hip.SIGNATURES and hasattr(lib, name)
+    for cite in ("esn_model.py:41-43", "reservoir.py:158-186"):
+        assert cite in header
+    assert lib.sgp_abi_version() == 3
+
+
+def test_window_planner_domain():
+    """1: one launch, nothing of size S M R; 2: layer by layer over one intermediate; 0: the sequence path."""
+    for R, L in [(16, 1), (32, 1), (32, 3), (48, 2), (64, 3), (64, 4), (128, 2), (16, 8), (256, 1), (200, 1)]:
+        assert hip.reservoir_window_mode(3, R, L) == 1, (R, L)
+        assert L * R > 256 or L == 1 or hip.reservoir_window_mode(3, R, L) == 1
+    for R, L in [(256, 2), (256, 3), (128, 4), (64, 7)]:
+        assert hip.reservoir_window_mode(3, R, L) == 2, (R, L)
+    for F, R, L in [(257, 32, 1), (3, 257, 1), (3, 32, 9), (0, 32, 1)]:
+        assert hip.reservoir_window_mode(F, R, L) == 0
+        assert hip.reservoir_window_workspace_bytes(F, R, L, 12, 100) == -1
+    # every L R <= 256 stack runs in one launch, behind the narrowest and the widest input alike
+    for F in (1, 17, 256):
+        for R in range(1, 257):
+            for L in range(1, 9):
+                if L * R <= 256:
+                    assert hip.reservoir_window_mode(F, R, L) == 1, (F, R, L)
+                    assert hip.reservoir_window_workspace_bytes(F, R, L, 24, 10 ** 5) == \
+                        hip.reservoir_window_workspace_bytes(F, R, L, 0, 0)
+    # the one-launch workspace holds weights only; the layered one adds exactly one [S, M, R]
+    assert hip.reservoir_window_workspace_bytes(3, 64, 3, 24, 10 ** 6) == hip.reservoir_window_workspace_bytes(3, 64, 3, 1, 1)
+    d = hip.reservoir_window_workspace_bytes(3, 256, 2, 24, 1000) - hip.reservoir_window_workspace_bytes(3, 256, 2, 0, 0)
+    assert 24 * 1000 * 256 * 4 <= d < 24 * 1000 * 256 * 4 + 256
