@@ -702,6 +702,14 @@ def reservoir_plan(F, R, N, T=2, activation="tanh", alpha=0.9, state=False, n_pi
     return [json.loads(line) for line in buf.value.decode().splitlines()]
 
 
+def reservoir_plan_of(x, out, w_hh, **request):
+    """``reservoir_plan`` for the views ``x[T, N, F]`` / ``out[T, N, R]`` as they lie in memory (any device): sizes, strides
+    and alignment are the tensors', ``request`` the remaining arguments (activation, alpha, state, n_pieces, ...)."""
+    return reservoir_plan(x.shape[2], w_hh.shape[0], x.shape[1], x.shape[0], x_strides=(x.stride(1), x.stride(0)),
+                          x_align=x.data_ptr() % 16, out_strides=(out.stride(1), out.stride(0)),
+                          out_align=out.data_ptr() % 16, **request)
+
+
 def reservoir_window_mode(F, R, L):
     """0: outside ``sgp_reservoir_window_f32``'s domain; 1: all layers in one launch, no ``[S, M, R]`` anywhere;
     2: layer by layer over one ``[S, M, R]`` intermediate in the workspace (no GPU needed)."""
