@@ -729,6 +729,53 @@ int sgp_masked_mae_bwd_f32(const float* y_hat, const float* y, const uint8_t* ma
                            const float* grad_out, const double* count, float* grad, sgp_stream_t stream);
 
 
+/* ------------------------------------------------ Gated graph network: edges -----
+ * The per-edge MLP, gate and sum of a GatedGraphNetwork layer (gated_gn.hip), forward and backward, for the same
+ * edge list in every batch item.  EXACT-FP32 contract as above: every product is a v_mfma_f32_16x16x4_f32.
+ * H = the layer's output width (even, 16..256), Hm = H / 2; act: 1 relu, 2 silu.  PQ [b * n, 2 Hm] holds the node
+ * projection P = X Wa^T + b1 | Q = X Wb^T of msg_mlp.0's weight W1 = [Wa | Wb] (sgp_dense_f32).  An edge (j -> i) is
+ *   z1 = P[i] + Q[j], a1 = act(z1), z2 = W2 a1 + b2, m = act(z2), g = sigmoid(wg . m + bg), agg[i] += g m.
+ * Edge tables (int32, device), built once per edge list (sgp_amd/nn/layers/gated_gn.py, edge_plan):
+ *   src[n_edges]      source of every edge, edges stably sorted by target
+ *   chunks[n_chunks][4] = (target, first edge, end edge, partial row or -1): at most sgp_gated_gn_chunk_edges() edges
+ *                     of one target; every target has at least one chunk (an empty one when nothing enters it), a
+ *                     target with more edges has several, which write partial rows (n_parts in all, per batch item)
+ *   fix[n_fix][3]     = (target, first partial row, count) of the split targets: their partials are added in chunk order
+ *   src_ptr[n + 1], src_pos[n_edges]   the inverted index: positions in the target-sorted list of the edges OUT OF
+ *                     each node, edges stably sorted by source
+ * w2_packed / w2t_packed: sgp_dense_pack_f32 of msg_mlp.2's weight [H, Hm] with transpose = 0 (n_out = H, k = Hm) / 1
+ * (n_out = Hm, k = H); b2 [H]; wg [H], bg [1] = gate_mlp.0 (device pointers).  Sizes outside the domain: SGP_EUNSUP;
+ * sgp_gated_gn_supported returns 0 for them and leaves the reason in sgp_last_error.
+ * Workspace bytes (-1 on a bad size): forward b * n_parts * H floats; backward the dz1 rows of a slice of batch items
+ * (at most SGP_TUNE gated_gn_ws_mb = 256 MiB, one item at least) + partial rows + per-workgroup weight partials. */
+int32_t sgp_gated_gn_supported(int32_t H, int32_t act);
+int32_t sgp_gated_gn_chunk_edges(void);
+int64_t sgp_gated_gn_workspace_bytes(int32_t backward, int64_t b, int64_t n_edges, int64_t n_chunks, int32_t n_parts,
+                                     int32_t H);
+
+/* agg [b * n, H]: every row written (no incoming edge: zeros); nothing of size n_edges is written.
+ *   replaces propagate() of tsl/nn/layers/graph_convs/gated_gn.py:56 = message() of lines 62-64 (cat([x_i, x_j]),
+ *   msg_mlp.1-3, gate_mlp, the product) and torch_geometric's gather and scatter-add around it */
+int sgp_gated_gn_edge_f32(const float* PQ, int64_t pq_row_stride, int32_t b, int32_t n, int32_t H, int32_t act,
+                          const int32_t* chunks, int32_t n_chunks, const int32_t* src, int64_t n_edges,
+                          const int32_t* fix, int32_t n_fix, int32_t n_parts,
+                          const float* w2_packed, const float* b2, const float* wg, const float* bg,
+                          float* agg, int64_t agg_row_stride, void* work, int64_t work_bytes, sgp_stream_t stream);
+
+/* Recomputes z1 .. g per edge from PQ; with dm = dAgg[i] g + (dAgg[i] . m) g (1 - g) wg, dz2 = dm act'(z2),
+ * dz1 = (W2^T dz2) act'(z1):  dPQ[i, 0 .. Hm) = sum of dz1 over the edges INTO i, dPQ[j, Hm .. 2 Hm) = over the edges
+ * OUT OF j, dW2 [H, Hm] = sum dz2 a1^T, db2 [H] = sum dz2, dwg [H] = sum (dAgg[i] . m) g (1 - g) m, dbg [1].
+ * No float atomics; bit-identical from run to run.
+ *   replaces what autograd derives for the lines above (the saved [b, E, .] tensors of message() included) */
+int sgp_gated_gn_edge_bwd_f32(const float* PQ, int64_t pq_row_stride, const float* dAgg, int64_t dagg_row_stride,
+                              int32_t b, int32_t n, int32_t H, int32_t act,
+                              const int32_t* chunks, int32_t n_chunks, const int32_t* src, int64_t n_edges,
+                              const int32_t* fix, int32_t n_fix, int32_t n_parts,
+                              const int32_t* src_ptr, const int32_t* src_pos,
+                              const float* w2_packed, const float* w2t_packed, const float* b2, const float* wg,
+                              const float* bg, float* dPQ, int64_t dpq_row_stride, float* dW2, float* db2, float* dwg,
+                              float* dbg, void* work, int64_t work_bytes, sgp_stream_t stream);
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

@@ -173,6 +173,15 @@ SIGNATURES = {
     "sgp_row_segsum_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i32, c_p, c_p, c_i32, c_p, c_p]),
     "sgp_masked_mae_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p]),
     "sgp_masked_mae_bwd_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p]),
+    "sgp_gated_gn_supported": (c_i32, [c_i32, c_i32]),
+    "sgp_gated_gn_chunk_edges": (c_i32, []),
+    "sgp_gated_gn_workspace_bytes": (c_i64, [c_i32, c_i64, c_i64, c_i64, c_i32, c_i32]),
+    "sgp_gated_gn_edge_f32": (ctypes.c_int, [c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_p, c_i64,
+                                             c_p, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p]),
+    "sgp_gated_gn_edge_bwd_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_i32, c_i32,
+                                                 c_p, c_i32, c_p, c_i64, c_p, c_i32, c_i32, c_p, c_p,
+                                                 c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p,
+                                                 c_p, c_i64, c_p]),
     "sgp_event_create": (ctypes.c_int, [ctypes.POINTER(c_p)]),
     "sgp_event_destroy": (ctypes.c_int, [c_p]),
     "sgp_event_record": (ctypes.c_int, [c_p, c_p]),
@@ -1123,6 +1132,66 @@ def masked_mae_bwd(y_hat, y, mask, mask_nans, grad_out, count):
                                       grad_out.data_ptr(), count.data_ptr(), grad.data_ptr(), _stream(grad)),
            "sgp_masked_mae_bwd_f32")
     return grad
+
+
+# ---------------------------------------------------------------- gated graph network edges (gated_gn.hip)
+def gated_gn_supported(H, activation):
+    """Whether the edge kernels cover a layer of output width ``H`` with this activation (no GPU needed)."""
+    return bool(load().sgp_gated_gn_supported(int(H), GL_ACT_CODES.get(activation, -1)))
+
+
+def gated_gn_workspace_bytes(plan, b, H, backward=False):
+    return int(load().sgp_gated_gn_workspace_bytes(int(backward), b, plan.n_edges, plan.n_chunks, plan.n_parts, H))
+
+
+def _gg_work(plan, b, H, backward, device):
+    nbytes = gated_gn_workspace_bytes(plan, b, H, backward)
+    if nbytes < 0:
+        raise ValueError("gated_gn: bad size")
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
+@_on_device
+def gated_gn_edge(pq, plan, b, H, activation, w2_packed, b2, wg, bg, out=None):
+    """agg [b * n, H] of include/sgp_amd.h, sgp_gated_gn_edge_f32.  ``pq``: [b * n, 2 (H // 2)] node projection;
+    ``plan``: the edge tables of ``sgp_amd.nn.layers.gated_gn.edge_plan`` (on pq's device); ``out``: a view with unit
+    column stride to write into (default a fresh [b * n, H])."""
+    lib = require_gpu()
+    pp, prs = _rows2(pq, "pq", 2 * (H // 2))
+    if pq.shape[0] != b * plan.n:
+        raise ValueError(f"pq: {pq.shape[0]} rows, b * n = {b * plan.n} expected")
+    if out is None:
+        out = torch.empty(b * plan.n, H, dtype=torch.float32, device=pq.device)
+    op, ors = _rows2(out, "out", H)
+    work = _gg_work(plan, b, H, False, pq.device)
+    _check(lib.sgp_gated_gn_edge_f32(pp, prs, b, plan.n, H, GL_ACT_CODES.get(activation, -1), plan.chunks.data_ptr(),
+                                     plan.n_chunks, _ptr(plan.src), plan.n_edges, _ptr(plan.fix), plan.n_fix,
+                                     plan.n_parts, w2_packed.data_ptr(), b2.data_ptr(), wg.data_ptr(), bg.data_ptr(),
+                                     op, ors, work.data_ptr(), work.numel(), _stream(out)), "sgp_gated_gn_edge_f32")
+    return out
+
+
+@_on_device
+def gated_gn_edge_bwd(pq, dagg, plan, b, H, activation, w2_packed, w2t_packed, b2, wg, bg):
+    """(dPQ [b * n, 2 Hm], dW2 [H, Hm], db2 [H], dwg [H], dbg [1]) of sgp_gated_gn_edge_bwd_f32; deterministic."""
+    lib = require_gpu()
+    hm = H // 2
+    pp, prs = _rows2(pq, "pq", 2 * hm)
+    dp, drs = _rows2(dagg, "dagg", H)
+    dev = pq.device
+    dpq = torch.empty(b * plan.n, 2 * hm, dtype=torch.float32, device=dev)
+    dw2 = torch.empty(H, hm, dtype=torch.float32, device=dev)
+    db2, dwg = (torch.empty(H, dtype=torch.float32, device=dev) for _ in range(2))
+    dbg = torch.empty(1, dtype=torch.float32, device=dev)
+    work = _gg_work(plan, b, H, True, dev)
+    _check(lib.sgp_gated_gn_edge_bwd_f32(pp, prs, dp, drs, b, plan.n, H, GL_ACT_CODES.get(activation, -1),
+                                         plan.chunks.data_ptr(), plan.n_chunks, _ptr(plan.src), plan.n_edges,
+                                         _ptr(plan.fix), plan.n_fix, plan.n_parts, plan.src_ptr.data_ptr(),
+                                         _ptr(plan.src_pos), w2_packed.data_ptr(), w2t_packed.data_ptr(),
+                                         b2.data_ptr(), wg.data_ptr(), bg.data_ptr(), dpq.data_ptr(), dpq.stride(0),
+                                         dw2.data_ptr(), db2.data_ptr(), dwg.data_ptr(), dbg.data_ptr(),
+                                         work.data_ptr(), work.numel(), _stream(dpq)), "sgp_gated_gn_edge_bwd_f32")
+    return dpq, dw2, db2, dwg, dbg
 
 
 class Event:

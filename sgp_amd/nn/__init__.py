@@ -1,1 +1,1 @@
-from . import encoders, models, reservoir
+from . import encoders, layers, models, reservoir

@@ -39,6 +39,8 @@ Library (integers)
                             128 the two waves of a SIMD take the phases in opposite order, 256 per-wave timeline of workgroup 0)
     res_splitj_max=512, res_tail=1, res_stream8=1   reservoir experiments: most node tiles the split-J kernel serves alone, exact deal +
                             split-J tail at large N, 8-wave streamed kernel (all seven res_* switches: res_tune, csrc/reservoir.hip)
+    gated_gn_ws_mb=256      gated graph network backward: byte cap (MiB) of the per-edge dz1 workspace; batch items go through
+                            the edge kernel in slices under it (one item at least)
     gesn_persistent=1, gesn_dbg=0, stack_debug=0   DynGESN / fused-stack experiments
 """
 import os
