@@ -776,6 +776,41 @@ int sgp_gated_gn_edge_bwd_f32(const float* PQ, int64_t pq_row_stride, const floa
                               const float* bg, float* dPQ, int64_t dpq_row_stride, float* dW2, float* db2, float* dwg,
                               float* dbg, void* work, int64_t work_bytes, sgp_stream_t stream);
 
+/* ------------------------------------------------ Trained recurrent baselines: LSTM / GRU window -----
+ * The gated recurrence of one torch.nn.LSTM / torch.nn.GRU layer (batch_first = False, zero initial state) over a
+ * window of S steps for M independent sequences (rnn_window.hip), forward and backward through time.  EXACT-FP32
+ * contract as above: every product is a v_mfma_f32_16x16x4_f32; no float atomics, bit-identical from run to run.
+ * cell: 0 lstm (gates i, f, g, o), 1 gru (gates r, z, n; n = tanh(W_in x + b_in + r (W_hn h + b_hn)),
+ * h' = (1 - z) n + z h).  H: a multiple of 16 in 16 .. 256; S, M >= 1; anything else returns SGP_EUNSUP with the reason
+ * in sgp_last_error (sgp_rnn_window_supported answers without a GPU).
+ * gates [S][M][4 H] (sgp_rnn_window_workspace_bytes): on entry the input projection W_ih x_t + b_ih (+ b_hh; GRU:
+ * blocks 0 .. 2, with b_hr and b_hz but NOT b_hn folded in), one sgp_dense_f32 launch for all S M rows.
+ * packed: sgp_rnn_window_packed_floats floats, W_hh [G H, H] in the fragment order of both directions. */
+int32_t sgp_rnn_window_supported(int32_t cell, int32_t H);
+int64_t sgp_rnn_window_packed_floats(int32_t cell, int32_t H);
+int64_t sgp_rnn_window_workspace_bytes(int32_t cell, int32_t H, int32_t S, int64_t M);
+int sgp_rnn_window_pack_f32(const float* w_hh, int32_t cell, int32_t H, float* packed, sgp_stream_t stream);
+
+/* One launch for the whole window.  save != 0 (training): the gate buffer is overwritten with what backward reads
+ * (LSTM: the activated i, f, g, o; GRU: r, z, n and W_hn h + b_hn in block 3), h_seq [S][M][H] and, for the LSTM,
+ * c_seq [S][M][H] are stored.  h_seq (any mode, may be NULL): every step's state; h_last (may be NULL) [M][H]: the
+ * last one.  h_drop (may be NULL) [S][M][H]: h times the Philox dropout factor of decoder.hip at flat index
+ * (t M + m) H + column (0 < dropout_p <= 1; p = 1: zeros), the next layer's input.
+ *   replaces self.rnn(x) of tsl/nn/blocks/encoders/rnn.py:57 (torch.nn.LSTM / GRU: the recurrent half of every cell
+ *   step, the cell update and the dropout between layers) and x[:, -1] of line 61 */
+int sgp_rnn_window_fwd_f32(int32_t cell, int32_t H, int32_t S, int64_t M, float* gates, const float* packed,
+                           const float* b_hn, float* h_seq, float* c_seq, float* h_drop, double dropout_p, uint64_t seed,
+                           float* h_last, int32_t save, sgp_stream_t stream);
+
+/* Time reversed; dh and dc never leave the chip.  dy: the cotangent of h, [M][H] for the last step only
+ * (dy_full = 0) or [S][M][H] (dy_full = 1).  The saved gates are overwritten in place with the gradients of the
+ * pre-activations: LSTM the 4 blocks; GRU [dr, dz, dn, dn r] -- the input side (dW_ih, db_ih, dx) reads blocks 0 .. 2,
+ * the hidden side (dW_hh, db_hh) blocks 0, 1 and 3.  Weight gradients: sgp_dense_wgrad_f32 on slices of this buffer.
+ *   replaces what autograd derives for the lines above (cuDNN-style BPTT of torch.nn.LSTM / GRU) */
+int sgp_rnn_window_bwd_f32(int32_t cell, int32_t H, int32_t S, int64_t M, float* gates, const float* packed,
+                           const float* h_seq, const float* c_seq, const float* dy, int32_t dy_full,
+                           sgp_stream_t stream);
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

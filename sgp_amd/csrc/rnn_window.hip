@@ -1,0 +1,371 @@
+// Trained recurrent baselines: the gated recurrence of an LSTM / GRU layer over a short window, forward and backward
+// through time (reference: tsl/nn/blocks/encoders/rnn.py:41-62 -> torch.nn.LSTM / torch.nn.GRU, batch_first=False, zero
+// initial state; selected by `--model-name rnn / fc_rnn` of experiments/run_traffic_baselines.py:28-31).
+//
+//   LSTM   a = W_ih x_t + b_ih + W_hh h + b_hh,  (i, f, g, o) = (s(a_i), s(a_f), tanh(a_g), s(a_o)),
+//          c' = f c + i g,  h' = o tanh(c')
+//   GRU    r = s(W_ir x + b_ir + W_hr h + b_hr),  z likewise,  n = tanh(W_in x + b_in + r (W_hn h + b_hn)),
+//          h' = (1 - z) n + z h
+//
+// for M = B * N independent sequences of S = 12 .. 24 steps.  The input part of all S * M rows is one sgp_dense_f32
+// launch into the gate buffer [S][M][4 H] (GRU: blocks 0 .. 2); this file is the part that is sequential in time.
+//
+// Mapping.  A workgroup owns ONE tile of 16 sequences for the whole window; its waves split the H hidden columns
+// (CT column tiles of 16 per wave, all gates of a column in the same wave, so the cell update is local to a lane).
+// Every product is a v_mfma_f32_16x16x4_f32 with the weight as the A operand (rows = output features) and the state as
+// the B operand (columns = sequences): a lane (n = lane & 15, q = lane >> 4) then holds features 16 jt + 4 q + 0..3 of
+// sequence n -- 16 contiguous bytes of every [.., M, H] buffer, so gates, h, c and the cotangent move as float4.
+// h (backward: the gate gradients) passes between the waves through LDS, one barrier per step (backward: two); h, c,
+// dh and dc themselves stay in registers from the first step to the last.
+// W_hh (256 KB at H = 128, 1 MB at H = 256) does not fit LDS: it is read every step from a packed copy in fragment
+// order (one coalesced 1 KB read per wave feeds 4 MFMAs), resident in L2 because every workgroup reads the same bytes.
+// Arithmetic: exact fp32 products, fp32 accumulation, one k-ordered chain per output; no atomics anywhere, so forward
+// and backward are bit-identical from run to run and independent of which tile a sequence falls into.
+#include "common.h"
+#include "decoder_ops.h"
+#include "reservoir_impl.h"
+
+namespace {
+using sgp::f32x4;
+
+constexpr int CELL_LSTM = 0, CELL_GRU = 1;
+constexpr int kPad = 4;                                     // floats of padding per LDS row (keeps rows 16-byte aligned)
+
+__device__ __forceinline__ float sigmoid_f32(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
+__device__ __forceinline__ f32x4 sigmoid4(f32x4 v) { return f32x4{sigmoid_f32(v[0]), sigmoid_f32(v[1]), sigmoid_f32(v[2]), sigmoid_f32(v[3])}; }
+__device__ __forceinline__ f32x4 tanh4(f32x4 v) {
+    return f32x4{sgp_res::tanh_f32(v[0]), sgp_res::tanh_f32(v[1]), sgp_res::tanh_f32(v[2]), sgp_res::tanh_f32(v[3])};
+}
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+
+// ---- packed W_hh (floats): forward part, then backward part, G H H each ---------------------------------------
+//   fwd [G JT row tiles][JT kb][64 lanes][4 s] = W_hh[16 rt + (l & 15)][16 kb + 4 (l >> 4) + s]
+//   bwd [JT col tiles][G JT kb][64 lanes][4 s] = W_hh[16 kb + 4 (l >> 4) + s][16 jt + (l & 15)]
+__global__ void rnn_pack(const float* w, int G, int H, float* out) {
+    const long long GHH = (long long)G * H * H;
+    const int JT = H / 16;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * GHH; i += (long long)gridDim.x * blockDim.x) {
+        const bool bwd = i >= GHH;
+        const long long e = bwd ? i - GHH : i;
+        const int s = (int)(e & 3), l = (int)((e >> 2) & 63);
+        const long long tk = e >> 8;
+        const int KB = bwd ? G * JT : JT;
+        const int kb = (int)(tk % KB), t = (int)(tk / KB);
+        const int a = 16 * t + (l & 15), k = 16 * kb + 4 * (l >> 4) + s;
+        out[i] = bwd ? w[(long long)k * H + a] : w[(long long)a * H + k];
+    }
+}
+
+struct RnnArgs {
+    float* gates;             // [S][M][4 H]: in the input projection, out (save) what backward reads; backward: dgates in place
+    const float* wp;          // packed W_hh (this direction's part)
+    const float* bhn;         // GRU: b_hn [H]
+    float* hseq;              // [S][M][H] (null: not stored)
+    float* cseq;              // LSTM, [S][M][H] (null: not stored)
+    float* hdrop;             // [S][M][H] dropped copy for the next layer (null: none)
+    float* hlast;             // [M][H] (null: not stored)
+    const float* dy;          // backward: cotangent of h, [M][H] (last step) or [S][M][H]
+    long long M;
+    int S, H, save, dy_full;
+    unsigned thresh, k0, k1;
+    float scale;
+};
+
+template <int CELL, int CT>
+__global__ __launch_bounds__(256) void rnn_fwd(RnnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int G = CELL == CELL_LSTM ? 4 : 3;
+    const int H = a.H, JT = H / 16, LDH = H + kPad;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = lane & 15, q = lane >> 4;
+    const long long m = (long long)blockIdx.x * 16 + n;
+    const bool ok = m < a.M;
+    const long long mc = ok ? m : a.M - 1;                  // lanes past the end compute on a valid row, store nothing
+    int jt[CT]; bool tv[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+        tv[c] = wave * CT + c < JT;                         // wave-uniform
+        jt[c] = tv[c] ? wave * CT + c : JT - 1;
+    }
+    f32x4 h[CT], cst[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) h[c] = cst[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 bn[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c)
+        bn[c] = (CELL == CELL_GRU && a.bhn) ? ld4(a.bhn + 16 * jt[c] + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+    int cur = 0;
+    for (int t = 0; t < a.S; ++t) {
+        const long long row = (long long)t * a.M + mc;
+        float* grow = a.gates + row * 4 * H;
+        f32x4 acc[CT][G], gxn[CT];
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            const int col = 16 * jt[c] + 4 * q;
+#pragma unroll
+            for (int g = 0; g < G; ++g) acc[c][g] = ld4(grow + g * H + col);
+            if constexpr (CELL == CELL_GRU) { gxn[c] = acc[c][2]; acc[c][2] = bn[c]; }
+        }
+        if (t > 0) {
+            const float* hb = lds + cur * 16 * LDH + n * LDH + 4 * q;
+            for (int kb = 0; kb < JT; ++kb) {
+                const f32x4 b = ld4(hb + 16 * kb);
+#pragma unroll
+                for (int c = 0; c < CT; ++c)
+#pragma unroll
+                    for (int g = 0; g < G; ++g) {
+                        const f32x4 w = ld4(a.wp + (((long long)(g * JT + jt[c]) * JT + kb) * 64 + lane) * 4);
+#pragma unroll
+                        for (int s = 0; s < 4; ++s)
+                            acc[c][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[s], b[s], acc[c][g], 0, 0, 0);
+                    }
+            }
+        }
+        float* hnext = lds + (cur ^ 1) * 16 * LDH + n * LDH;
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            const int col = 16 * jt[c] + 4 * q;
+            const bool st = ok && tv[c];
+            if constexpr (CELL == CELL_LSTM) {
+                const f32x4 gi = sigmoid4(acc[c][0]), gf = sigmoid4(acc[c][1]), gg = tanh4(acc[c][2]), go = sigmoid4(acc[c][3]);
+                cst[c] = gf * cst[c] + gi * gg;
+                h[c] = go * tanh4(cst[c]);
+                if (a.save && st) {
+                    st4(grow + col, gi); st4(grow + H + col, gf); st4(grow + 2 * H + col, gg); st4(grow + 3 * H + col, go);
+                    st4(a.cseq + row * H + col, cst[c]);
+                }
+            } else {
+                const f32x4 r = sigmoid4(acc[c][0]), z = sigmoid4(acc[c][1]), hn = acc[c][2];
+                const f32x4 nn = tanh4(gxn[c] + r * hn);
+                h[c] = (1.f - z) * nn + z * h[c];
+                if (a.save && st) {
+                    st4(grow + col, r); st4(grow + H + col, z); st4(grow + 2 * H + col, nn); st4(grow + 3 * H + col, hn);
+                }
+            }
+            if (st) {
+                if (a.hseq) st4(a.hseq + row * H + col, h[c]);
+                if (a.hdrop) {
+                    f32x4 d;
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+                        d[s] = h[c][s] * keep_factor((unsigned long long)(row * H + col + s), a.thresh, a.k0, a.k1, a.scale);
+                    st4(a.hdrop + row * H + col, d);
+                }
+            }
+            if (tv[c]) st4(hnext + col, h[c]);
+        }
+        __syncthreads();                                    // h of this step is complete; the other buffer is free again
+        cur ^= 1;
+    }
+    if (a.hlast && ok) {
+#pragma unroll
+        for (int c = 0; c < CT; ++c)
+            if (tv[c]) st4(a.hlast + m * H + 16 * jt[c] + 4 * q, h[c]);
+    }
+}
+
+// Backward through time.  Per step: dh += the step's cotangent; the gate gradients (with respect to the pre-activations)
+// from the saved gates; they overwrite the saved gates in place -- LSTM the 4 blocks; GRU [dr, dz, dn, dn r], of which
+// the input side reads blocks 0 .. 2 and the hidden side 0, 1, 3 -- and go to LDS, where every wave reads all of them
+// for its columns of dh_{t-1} = dgates W_hh (+ dh z for the GRU).
+template <int CELL, int CT>
+__global__ __launch_bounds__(256) void rnn_bwd(RnnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int G = CELL == CELL_LSTM ? 4 : 3;
+    const int H = a.H, JT = H / 16, LDG = G * H + kPad, KB = G * JT;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = lane & 15, q = lane >> 4;
+    const long long m = (long long)blockIdx.x * 16 + n;
+    const bool ok = m < a.M;
+    const long long mc = ok ? m : a.M - 1;
+    int jt[CT]; bool tv[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+        tv[c] = wave * CT + c < JT;
+        jt[c] = tv[c] ? wave * CT + c : JT - 1;
+    }
+    f32x4 dh[CT], dc[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) dh[c] = dc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float* dgl = lds + n * LDG;
+    for (int t = a.S - 1; t >= 0; --t) {
+        const long long row = (long long)t * a.M + mc;
+        float* grow = a.gates + row * 4 * H;
+        f32x4 keep[CT];                                     // GRU: dh z, the direct path to dh_{t-1}
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            const int col = 16 * jt[c] + 4 * q;
+            const bool st = ok && tv[c];
+            if (a.dy_full) dh[c] += ld4(a.dy + row * H + col);
+            else if (t == a.S - 1) dh[c] += ld4(a.dy + mc * H + col);
+            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (CELL == CELL_LSTM) {
+                const f32x4 gi = ld4(grow + col), gf = ld4(grow + H + col), gg = ld4(grow + 2 * H + col), go = ld4(grow + 3 * H + col);
+                const f32x4 tc = tanh4(ld4(a.cseq + row * H + col));
+                const f32x4 cp = t > 0 ? ld4(a.cseq + (row - a.M) * H + col) : zero;
+                const f32x4 dcv = dc[c] + dh[c] * go * (1.f - tc * tc);
+                const f32x4 dai = dcv * gg * gi * (1.f - gi), daf = dcv * cp * gf * (1.f - gf);
+                const f32x4 dag = dcv * gi * (1.f - gg * gg), dao = dh[c] * tc * go * (1.f - go);
+                dc[c] = dcv * gf;
+                keep[c] = zero;
+                if (st) { st4(grow + col, dai); st4(grow + H + col, daf); st4(grow + 2 * H + col, dag); st4(grow + 3 * H + col, dao); }
+                if (tv[c]) { st4(dgl + col, dai); st4(dgl + H + col, daf); st4(dgl + 2 * H + col, dag); st4(dgl + 3 * H + col, dao); }
+            } else {
+                const f32x4 r = ld4(grow + col), z = ld4(grow + H + col), nn = ld4(grow + 2 * H + col), hn = ld4(grow + 3 * H + col);
+                const f32x4 hp = t > 0 ? ld4(a.hseq + (row - a.M) * H + col) : zero;
+                const f32x4 dan = dh[c] * (1.f - z) * (1.f - nn * nn);
+                const f32x4 daz = dh[c] * (hp - nn) * z * (1.f - z);
+                const f32x4 dar = dan * hn * r * (1.f - r), dhn = dan * r;
+                keep[c] = dh[c] * z;
+                if (st) { st4(grow + col, dar); st4(grow + H + col, daz); st4(grow + 2 * H + col, dan); st4(grow + 3 * H + col, dhn); }
+                if (tv[c]) { st4(dgl + col, dar); st4(dgl + H + col, daz); st4(dgl + 2 * H + col, dhn); }
+            }
+        }
+        if (t == 0) break;                                  // uniform: nothing is carried past the first step
+        __syncthreads();
+        f32x4 acc[CT];
+#pragma unroll
+        for (int c = 0; c < CT; ++c) acc[c] = keep[c];
+        const float* gb = dgl + 4 * q;
+        for (int kb = 0; kb < KB; ++kb) {
+            const f32x4 b = ld4(gb + 16 * kb);
+#pragma unroll
+            for (int c = 0; c < CT; ++c) {
+                const f32x4 w = ld4(a.wp + (((long long)jt[c] * KB + kb) * 64 + lane) * 4);
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[s], b[s], acc[c], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CT; ++c) dh[c] = acc[c];
+        __syncthreads();                                    // all reads of this step's gate gradients are done
+    }
+}
+
+const char* domain_error(int cell, int H) {
+    if (cell != CELL_LSTM && cell != CELL_GRU) return "cell must be 0 (lstm) or 1 (gru)";
+    if (H < 16 || H > 256 || H % 16) return "hidden size must be a multiple of 16 in 16 .. 256";
+    return nullptr;
+}
+int ct_of(int H) { const int jt = H / 16; return jt <= 4 ? 1 : (jt <= 8 ? 2 : (jt <= 12 ? 3 : 4)); }
+
+// The backward kernel of the LSTM at H = 256 needs 64.25 KB of LDS: the limit is raised once per instantiation (and
+// device), and a refusal is reported here instead of at the launch that would follow.
+template <int CELL, int CT>
+int raise_lds_limit(size_t shm) {
+    static int done[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (done[dev]) return 0;
+    const int cap = 16 * (4 * 256 + kPad) * 4;                         // the largest this file asks for
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_bwd<CELL, CT>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, cap);
+    if (e != hipSuccess) return sgp::fail((int)e, "rnn_bwd: %zu bytes of LDS refused: %s", shm, hipGetErrorString(e));
+    done[dev] = 1;
+    return 0;
+}
+
+template <int CELL>
+int launch(bool bwd, const RnnArgs& a, hipStream_t s) {
+    constexpr int G = CELL == CELL_LSTM ? 4 : 3;
+    const int JT = a.H / 16, ct = ct_of(a.H), nw = (JT + ct - 1) / ct;
+    const dim3 grid((unsigned)((a.M + 15) / 16)), block(64 * nw);
+    const size_t shm = bwd ? (size_t)16 * (G * a.H + kPad) * 4 : (size_t)2 * 16 * (a.H + kPad) * 4;
+#define SGP_RNN_LAUNCH(CT_)                                                                   \
+    if (bwd) {                                                                                \
+        if (shm > 48 * 1024)                                                                  \
+            if (int rc = raise_lds_limit<CELL, CT_>(shm)) return rc;                          \
+        hipLaunchKernelGGL((rnn_bwd<CELL, CT_>), grid, block, shm, s, a);                     \
+    } else hipLaunchKernelGGL((rnn_fwd<CELL, CT_>), grid, block, shm, s, a)
+    switch (ct) {
+        case 1: SGP_RNN_LAUNCH(1); break;
+        case 2: SGP_RNN_LAUNCH(2); break;
+        case 3: SGP_RNN_LAUNCH(3); break;
+        default: SGP_RNN_LAUNCH(4); break;
+    }
+#undef SGP_RNN_LAUNCH
+    return 0;
+}
+
+int check_shape(const char* what, int cell, int H, int S, int64_t M) {
+    if (const char* e = domain_error(cell, H)) return sgp::fail(SGP_EUNSUP, "%s: %s (cell %d, H %d)", what, e, cell, H);
+    SGP_REQUIRE(S >= 1 && M >= 1 && M <= ((int64_t)1 << 31) * 16 - 16, "%s: bad size (S %d, M %lld)", what, S, (long long)M);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t sgp_rnn_window_supported(int32_t cell, int32_t H) {
+    if (const char* e = domain_error(cell, H)) {
+        sgp::fail(SGP_EUNSUP, "sgp_rnn_window_supported: %s (cell %d, H %d)", e, cell, H);
+        return 0;
+    }
+    return 1;
+}
+
+int64_t sgp_rnn_window_packed_floats(int32_t cell, int32_t H) {
+    if (domain_error(cell, H)) return -1;
+    return (int64_t)2 * (cell == CELL_LSTM ? 4 : 3) * H * H;
+}
+
+int64_t sgp_rnn_window_workspace_bytes(int32_t cell, int32_t H, int32_t S, int64_t M) {
+    if (domain_error(cell, H) || S < 1 || M < 1) return -1;
+    return (int64_t)S * M * 4 * H * 4;
+}
+
+int sgp_rnn_window_pack_f32(const float* w_hh, int32_t cell, int32_t H, float* packed, sgp_stream_t stream) {
+    if (const char* e = domain_error(cell, H)) return sgp::fail(SGP_EUNSUP, "sgp_rnn_window_pack_f32: %s (cell %d, H %d)", e, cell, H);
+    SGP_REQUIRE(w_hh && packed, "sgp_rnn_window_pack_f32: null pointer");
+    SGP_REQUIRE(sgp::aligned16(packed), "sgp_rnn_window_pack_f32: packed must be 16-byte aligned");
+    const int G = cell == CELL_LSTM ? 4 : 3;
+    const long long total = 2ll * G * H * H;
+    hipLaunchKernelGGL(rnn_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_hh, G, H, packed);
+    return sgp::check_launch("sgp_rnn_window_pack_f32");
+}
+
+int sgp_rnn_window_fwd_f32(int32_t cell, int32_t H, int32_t S, int64_t M, float* gates, const float* packed,
+                           const float* b_hn, float* h_seq, float* c_seq, float* h_drop, double dropout_p, uint64_t seed,
+                           float* h_last, int32_t save, sgp_stream_t stream) {
+    int rc = check_shape("sgp_rnn_window_fwd_f32", cell, H, S, M);
+    if (rc) return rc;
+    SGP_REQUIRE(gates && packed, "sgp_rnn_window_fwd_f32: null pointer");
+    SGP_REQUIRE(cell != CELL_GRU || b_hn, "sgp_rnn_window_fwd_f32: the GRU needs b_hn");
+    SGP_REQUIRE(h_seq || h_last, "sgp_rnn_window_fwd_f32: nothing to store (h_seq and h_last are null)");
+    SGP_REQUIRE(!save || (h_seq && (cell != CELL_LSTM || c_seq)), "sgp_rnn_window_fwd_f32: save needs h_seq (and c_seq for the LSTM)");
+    SGP_REQUIRE(!h_drop || (dropout_p > 0. && dropout_p <= 1.), "sgp_rnn_window_fwd_f32: h_drop needs 0 < dropout_p <= 1");
+    SGP_REQUIRE(sgp::aligned16(gates) && sgp::aligned16(packed) && sgp::aligned16(b_hn) && sgp::aligned16(h_seq) &&
+                sgp::aligned16(c_seq) && sgp::aligned16(h_drop) && sgp::aligned16(h_last),
+                "sgp_rnn_window_fwd_f32: buffers must be 16-byte aligned");
+    RnnArgs a{};
+    a.gates = gates; a.wp = packed; a.bhn = b_hn; a.hseq = h_seq; a.cseq = c_seq; a.hdrop = h_drop; a.hlast = h_last;
+    a.M = M; a.S = S; a.H = H; a.save = save;
+    set_dropout(a.thresh, a.k0, a.k1, a.scale, h_drop ? dropout_p : 0., seed);
+    if (h_drop && dropout_p >= 1.) { a.thresh = 0xFFFFFFFFu; a.scale = 0.f; }
+    rc = cell == CELL_LSTM ? launch<CELL_LSTM>(false, a, (hipStream_t)stream) : launch<CELL_GRU>(false, a, (hipStream_t)stream);
+    return rc ? rc : sgp::check_launch("sgp_rnn_window_fwd_f32");
+}
+
+int sgp_rnn_window_bwd_f32(int32_t cell, int32_t H, int32_t S, int64_t M, float* gates, const float* packed,
+                           const float* h_seq, const float* c_seq, const float* dy, int32_t dy_full,
+                           sgp_stream_t stream) {
+    int rc = check_shape("sgp_rnn_window_bwd_f32", cell, H, S, M);
+    if (rc) return rc;
+    SGP_REQUIRE(gates && packed && dy, "sgp_rnn_window_bwd_f32: null pointer");
+    SGP_REQUIRE(cell == CELL_LSTM ? c_seq != nullptr : h_seq != nullptr,
+                "sgp_rnn_window_bwd_f32: the saved sequence is missing (c_seq for the LSTM, h_seq for the GRU)");
+    SGP_REQUIRE(sgp::aligned16(gates) && sgp::aligned16(packed) && sgp::aligned16(h_seq) && sgp::aligned16(c_seq) &&
+                sgp::aligned16(dy), "sgp_rnn_window_bwd_f32: buffers must be 16-byte aligned");
+    const int G = cell == CELL_LSTM ? 4 : 3;
+    RnnArgs a{};
+    a.gates = gates; a.wp = packed + (int64_t)G * H * H; a.hseq = const_cast<float*>(h_seq);
+    a.cseq = const_cast<float*>(c_seq); a.dy = dy; a.dy_full = dy_full;
+    a.M = M; a.S = S; a.H = H;
+    rc = cell == CELL_LSTM ? launch<CELL_LSTM>(true, a, (hipStream_t)stream) : launch<CELL_GRU>(true, a, (hipStream_t)stream);
+    return rc ? rc : sgp::check_launch("sgp_rnn_window_bwd_f32");
+}
+
+}  // extern "C"

@@ -182,6 +182,13 @@ SIGNATURES = {
                                                  c_p, c_i32, c_p, c_i64, c_p, c_i32, c_i32, c_p, c_p,
                                                  c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p,
                                                  c_p, c_i64, c_p]),
+    "sgp_rnn_window_supported": (c_i32, [c_i32, c_i32]),
+    "sgp_rnn_window_packed_floats": (c_i64, [c_i32, c_i32]),
+    "sgp_rnn_window_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i64]),
+    "sgp_rnn_window_pack_f32": (ctypes.c_int, [c_p, c_i32, c_i32, c_p, c_p]),
+    "sgp_rnn_window_fwd_f32": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_u64,
+                                              c_p, c_i32, c_p]),
+    "sgp_rnn_window_bwd_f32": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i64, c_p, c_p, c_p, c_p, c_p, c_i32, c_p]),
     "sgp_event_create": (ctypes.c_int, [ctypes.POINTER(c_p)]),
     "sgp_event_destroy": (ctypes.c_int, [c_p]),
     "sgp_event_record": (ctypes.c_int, [c_p, c_p]),
@@ -1192,6 +1199,62 @@ def gated_gn_edge_bwd(pq, dagg, plan, b, H, activation, w2_packed, w2t_packed, b
                                          dw2.data_ptr(), db2.data_ptr(), dwg.data_ptr(), dbg.data_ptr(),
                                          work.data_ptr(), work.numel(), _stream(dpq)), "sgp_gated_gn_edge_bwd_f32")
     return dpq, dw2, db2, dwg, dbg
+
+
+# ---------------------------------------------------------------- LSTM / GRU window (rnn_window.hip)
+RNN_CELLS = {"lstm": 0, "gru": 1}
+RNN_GATES = {"lstm": 4, "gru": 3}
+
+
+def rnn_window_supported(cell, H):
+    """Whether the recurrent kernels cover ``cell`` ('lstm' / 'gru') at hidden size ``H`` (no GPU needed)."""
+    return bool(load().sgp_rnn_window_supported(RNN_CELLS.get(cell, -1), int(H)))
+
+
+def rnn_window_require(cell, H):
+    if not rnn_window_supported(cell, H):
+        raise NotImplementedError("rnn_window: " + load().sgp_last_error().decode())
+
+
+def rnn_window_workspace_bytes(cell, H, S, M):
+    """Bytes of the gate buffer [S, M, 4 H] of one layer."""
+    return int(load().sgp_rnn_window_workspace_bytes(RNN_CELLS.get(cell, -1), int(H), int(S), int(M)))
+
+
+@_on_device
+def rnn_window_pack(w_hh, cell):
+    """``weight_hh_l*`` [G H, H] (CUDA) -> its packed copy for both directions (sgp_rnn_window_pack_f32)."""
+    lib = require_gpu()
+    w = w_hh.detach().float().contiguous()
+    H = w.shape[1]
+    rnn_window_require(cell, H)
+    if w.shape[0] != RNN_GATES[cell] * H:
+        raise ValueError(f"weight_hh: expected [{RNN_GATES[cell] * H}, {H}], got {tuple(w.shape)}")
+    packed = torch.empty(lib.sgp_rnn_window_packed_floats(RNN_CELLS[cell], H), dtype=torch.float32, device=w.device)
+    _check(lib.sgp_rnn_window_pack_f32(w.data_ptr(), RNN_CELLS[cell], H, packed.data_ptr(), _stream(w)),
+           "sgp_rnn_window_pack_f32")
+    return packed
+
+
+@_on_device
+def rnn_window_fwd(gates, cell, H, S, M, packed, b_hn=None, h_seq=None, c_seq=None, h_drop=None, dropout_p=0., seed=0,
+                   h_last=None, save=False):
+    """One layer's recurrence over the window (sgp_rnn_window_fwd_f32); ``gates`` [S M, 4 H] holds the input
+    projection and, with ``save``, is overwritten with what the backward pass reads."""
+    lib = require_gpu()
+    _check(lib.sgp_rnn_window_fwd_f32(RNN_CELLS.get(cell, -1), H, S, M, gates.data_ptr(), packed.data_ptr(), _ptr(b_hn),
+                                      _ptr(h_seq), _ptr(c_seq), _ptr(h_drop), float(dropout_p), int(seed),
+                                      _ptr(h_last), int(bool(save)), _stream(gates)), "sgp_rnn_window_fwd_f32")
+
+
+@_on_device
+def rnn_window_bwd(gates, cell, H, S, M, packed, h_seq, c_seq, dy, dy_full):
+    """Backward through time of one layer (sgp_rnn_window_bwd_f32): the saved gates become the pre-activation
+    gradients in place."""
+    lib = require_gpu()
+    _check(lib.sgp_rnn_window_bwd_f32(RNN_CELLS.get(cell, -1), H, S, M, gates.data_ptr(), packed.data_ptr(),
+                                      _ptr(h_seq), _ptr(c_seq), dy.data_ptr(), int(bool(dy_full)), _stream(gates)),
+           "sgp_rnn_window_bwd_f32")
 
 
 class Event:

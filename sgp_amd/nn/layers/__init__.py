@@ -1,3 +1,4 @@
 from .gated_gn import GatedGraphNetwork, edge_plan
+from .rnn import RNN
 
-__all__ = ["GatedGraphNetwork", "edge_plan"]
+__all__ = ["GatedGraphNetwork", "edge_plan", "RNN"]

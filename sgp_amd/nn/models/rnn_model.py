@@ -1,0 +1,187 @@
+"""The recurrent baselines on the GPU: ``RNNModel`` and ``FCRNNModel`` (``tsl/nn/models/rnn_model.py:12-154``, what
+``--model-name rnn / fc_rnn`` of ``experiments/run_traffic_baselines.py:28-31`` builds).
+
+``input_encoder`` (a ``ConditionalBlock``, ``tsl/nn/blocks/encoders/conditional.py:43-67``, or ``Linear + ReLU``) ->
+``RNN`` (``sgp_amd.nn.layers.rnn``: LSTM / GRU over the window, last state) -> ``MLPDecoder``
+(``tsl/nn/blocks/decoders/mlp_decoder.py:38-46``: MLP, linear readout, ``'b n (h c) -> b h n c'`` in the store).  Every
+matrix product is a HIP kernel, forward and backward (``sgp_dense_f32`` / ``sgp_dense_wgrad_f32`` of the SGP decoder,
+``sgp_rnn_window_fwd_f32`` / ``_bwd_f32`` for the recurrence); torch adds the two branches of the conditional block
+(``u`` is projected once per ``(b, s)`` and broadcast over the nodes by that add) and applies its ReLU.  Parameters keep
+the reference's module paths, shapes and construction order.
+"""
+import torch
+from torch import nn
+
+from ... import hip
+from ..encoders._args import opt_list
+from ..layers import rnn as _rnn_layer
+from .sgp_model import _DenseFn, _dev, _Linear, _MLP, _PackCache, _seed, _TrunkFn
+
+
+class _ConditionalBlock(nn.Module):
+    """Parameter holder of tsl ``ConditionalBlock(dropout=0, skip_connection=False)``."""
+
+    def __init__(self, input_size, exog_size, output_size):
+        super().__init__()
+        self.input_affinity = _Linear(input_size, output_size)
+        self.condition_affinity = _Linear(exog_size, output_size)
+        self.out_inputs_affinity = _Linear(output_size, output_size)
+        self.out_cond_affinity = _Linear(output_size, output_size, bias=False)
+        self.register_parameter('skip_conn', None)
+
+
+class _MLPReadout(_MLP):
+    """tsl ``MLP(output_size=...)``: the Dense layers, then ``readout`` (mlp.py:43-44)."""
+
+    def __init__(self, input_size, hidden_size, output_size, n_layers):
+        super().__init__(input_size, hidden_size, None, n_layers)
+        self.readout = _Linear(hidden_size, output_size)
+
+
+class _MLPDecoder(nn.Module):
+    """tsl ``MLPDecoder(receptive_field=1)``: ``readout.0`` is the MLP, ``readout.1`` the Rearrange."""
+
+    def __init__(self, input_size, hidden_size, output_size, horizon, n_layers):
+        super().__init__()
+        self.readout = nn.Sequential(_MLPReadout(input_size, hidden_size, output_size * horizon, n_layers),
+                                     nn.Identity())
+
+
+_ACTS = ('relu', 'silu', 'linear', 'identity')
+
+
+class RNNModel(nn.Module):
+    """``tsl/nn/models/rnn_model.py:12-99``.  ``forward(x [b, s, n, input_size], u=None)`` with ``u [b, s, exog]`` or
+    ``[b, s, n, exog]`` -> ``[b, horizon, n, output_size]``.  CPU inputs go to the GPU and the result comes back."""
+
+    def __init__(self, input_size, hidden_size, output_size, ff_size, exog_size, rec_layers, ff_layers, rec_dropout,
+                 ff_dropout, horizon, cell_type='gru', activation='relu'):
+        super().__init__()
+        act = activation.lower() if isinstance(activation, str) else activation
+        if act not in _ACTS:
+            raise NotImplementedError(f"activation '{activation}': the HIP kernels have relu, silu and linear")
+        for name, v in (("rec_dropout", rec_dropout), ("ff_dropout", ff_dropout)):
+            if not 0. <= float(v) <= 1.:
+                raise ValueError(f"{name}: dropout probability has to be between 0 and 1, but got {v}")
+        if ff_layers < 1 or rec_layers < 1:
+            raise ValueError("rec_layers and ff_layers must be at least 1")
+        self.input_size, self.hidden_size = int(input_size), int(hidden_size)
+        self.exog_size = int(exog_size or 0)
+        self.output_size, self.horizon = int(output_size), int(horizon)
+        self.ff_size, self.ff_layers, self.ff_dropout = int(ff_size), int(ff_layers), float(ff_dropout)
+        self.activation = None if act in ('linear', 'identity') else act
+        if self.exog_size > 0:
+            self.input_encoder = _ConditionalBlock(input_size, exog_size, hidden_size)
+        else:
+            self.input_encoder = nn.Sequential(_Linear(input_size, hidden_size), nn.Identity())
+        self.rnn = _rnn_layer.RNN(input_size=hidden_size, hidden_size=hidden_size, n_layers=rec_layers,
+                                  dropout=rec_dropout, cell=cell_type)
+        self.readout = _MLPDecoder(hidden_size, ff_size, output_size, horizon, ff_layers)
+        self._packs = _PackCache()
+
+    # -------------------------------------------------------------- pieces
+    def _lin(self, name, lin, rows, activation=None):
+        dev = rows.device
+
+        def build():
+            wd = _dev(lin.weight, dev)
+            bias = _dev(lin.bias, dev).contiguous() if lin.bias is not None else \
+                torch.zeros(lin.weight.shape[0], dtype=torch.float32, device=dev)
+            return hip.dense_pack(wd), hip.dense_pack(wd, transpose=True), bias
+        ps = (lin.weight,) if lin.bias is None else (lin.weight, lin.bias)
+        packs = self._packs.get(name, ps, dev, build)
+        bias = lin.bias if lin.bias is not None else packs[2]         # no bias: a constant zero vector, no gradient
+        return _DenseFn.apply(rows, lin.weight, bias, None, rows.shape[0], activation, 0., 0, packs)
+
+    def _encode(self, x, u):
+        b, s, n, f = x.shape
+        rows = x.reshape(b * s * n, f)
+        enc = self.input_encoder
+        if self.exog_size == 0:
+            if u is not None:
+                raise ValueError("u given, but the model was built with exog_size = 0")
+            return self._lin("input", enc[0], rows, 'relu')           # nn.ReLU whatever `activation` (rnn_model.py:53)
+        if u is None:
+            raise ValueError(f"the model needs u with {self.exog_size} exogenous features")
+        u = u.to(x.device, torch.float32)
+        if u.dim() == 3:
+            u = u[:, :, None]                                          # 'b s f -> b s 1 f'
+        if u.dim() != 4 or u.shape[-1] != self.exog_size or u.shape[:2] != x.shape[:2] or u.shape[2] not in (1, n):
+            raise ValueError(f"u: expected [{b}, {s}, (n,) {self.exog_size}], got {tuple(u.shape)}")
+        nu = u.shape[2]
+        urows = u.contiguous().reshape(b * s * nu, self.exog_size)
+        act = self.activation
+        out = self._lin("in", enc.input_affinity, rows, act)
+        cond = self._lin("cond", enc.condition_affinity, urows, act)  # once per (b, s) when u has no node axis
+        a = self._lin("out_in", enc.out_inputs_affinity, out)
+        c = self._lin("out_cond", enc.out_cond_affinity, cond)
+        z = a.reshape(b * s, n, -1) + c.reshape(b * s, nu, -1)
+        if act == 'relu':
+            z = torch.relu(z)
+        elif act == 'silu':
+            z = torch.nn.functional.silu(z)
+        return z.reshape(b * s * n, -1)
+
+    def _decode(self, h, b, n):
+        dev = h.device
+        mlp = self.readout.readout[0]
+        packs, params = [], []
+        lins = [d.layer[0] for d in mlp.mlp] + [mlp.readout]
+        for i, lin in enumerate(lins):
+            def build(lin=lin):
+                wd = _dev(lin.weight, dev)
+                return hip.dense_pack(wd), hip.dense_pack(wd, transpose=True), _dev(lin.bias, dev).contiguous()
+            packs.append(self._packs.get(f"ff{i}", (lin.weight, lin.bias), dev, build))
+            params += [lin.weight, lin.bias]
+        p = self.ff_dropout if self.training else 0.
+        seeds = tuple(_seed() if p > 0. else 0 for _ in range(self.ff_layers))
+        spec = (False, self.ff_layers, self.ff_size, self.activation, p, self.horizon, self.output_size, b, n)
+        return _TrunkFn.apply(h, spec, packs, seeds, *params)
+
+    def forward(self, x, u=None, **kwargs):
+        if x.dim() != 4 or x.shape[-1] != self.input_size:
+            raise ValueError(f"x: expected [b, s, n, {self.input_size}], got {tuple(x.shape)}")
+        hip.rnn_window_require(self.rnn.cell, self.hidden_size)       # the reason, before any launch
+        on_cpu = not x.is_cuda
+        if on_cpu:
+            hip.require_gpu()
+            x = x.cuda()
+        x = x.float().contiguous()
+        b, s, n, _ = x.shape
+        h = self._encode(x, u).reshape(b, s, n, self.hidden_size)
+        h = self.rnn(h, return_last_state=True)                        # [b, n, H]
+        y = self._decode(h.reshape(b * n, self.hidden_size), b, n)
+        return y.cpu() if on_cpu else y
+
+    @staticmethod
+    def add_model_specific_args(parser):
+        # tsl/nn/models/rnn_model.py:88-97
+        opt_list(parser, '--hidden-size', type=int, default=32, tunable=True, options=[16, 32, 64, 128, 256])
+        opt_list(parser, '--ff-size', type=int, default=64, tunable=True, options=[32, 64, 128, 256, 512, 1024])
+        opt_list(parser, '--rec-layers', type=int, default=1, tunable=True, options=[1, 2, 3])
+        opt_list(parser, '--ff-layers', type=int, default=1, tunable=True, options=[1, 2, 3])
+        opt_list(parser, '--rec-dropout', type=float, default=0., tunable=True, options=[0., 0.1, 0.2])
+        opt_list(parser, '--ff-dropout', type=float, default=0., tunable=True, options=[0., 0.1, 0.25, 0.5])
+        opt_list(parser, '--cell-type', type=str, default='gru', tunable=True, options=['gru', 'lstm'])
+        return parser
+
+
+class FCRNNModel(RNNModel):
+    """``tsl/nn/models/rnn_model.py:102-154``: the nodes flattened into the features, one sequence per batch item."""
+
+    def __init__(self, input_size, hidden_size, output_size, ff_size, exog_size, rec_layers, ff_layers, rec_dropout,
+                 ff_dropout, horizon, n_nodes, cell_type='gru', activation='relu'):
+        super().__init__(input_size=input_size * n_nodes, hidden_size=hidden_size,
+                         output_size=output_size * n_nodes, ff_size=ff_size, exog_size=exog_size,
+                         rec_layers=rec_layers, ff_layers=ff_layers, rec_dropout=rec_dropout, ff_dropout=ff_dropout,
+                         horizon=horizon, cell_type=cell_type, activation=activation)
+
+    def forward(self, x, u=None, **kwargs):
+        if x.dim() != 4:
+            raise ValueError(f"x: expected [b, s, n, f], got {tuple(x.shape)}")
+        b, s, n, _ = x.shape
+        x = x.reshape(b, s, 1, -1)                                     # 'b s n f -> b s 1 (n f)'
+        if u is not None and u.dim() == 4:
+            u = u.reshape(b, s, 1, -1)
+        y = super().forward(x, u, **kwargs)
+        return y.reshape(b, self.horizon, n, -1)                       # 'b h 1 (n f) -> b h n f'
