@@ -245,6 +245,16 @@ def require_gpu():
     return lib
 
 
+def to_gpu(x):
+    """``(x on the GPU, was_cpu)``: a CPU tensor moves to the current device (after ``require_gpu``), a device
+    tensor stays where it is; the caller brings its result back with ``y.cpu() if was_cpu else y``."""
+    was_cpu = not x.is_cuda
+    if was_cpu:
+        require_gpu()
+        x = x.cuda()
+    return x, was_cpu
+
+
 _masked_streams = {}
 
 

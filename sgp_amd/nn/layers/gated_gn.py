@@ -16,13 +16,7 @@ import torch
 from torch import nn
 
 from ... import hip
-
-
-def _holders():
-    """The SGP decoder's parameter holders (``_Linear``, ``_PackCache``, ``_dev``), imported on first use: this module
-    is a leaf at import time, so ``sgp_amd.nn.models`` can import it in any order."""
-    from ..models import sgp_model
-    return sgp_model
+from .. import dense
 
 
 class EdgePlan:
@@ -197,14 +191,14 @@ class GatedGraphNetwork(nn.Module):
             raise ValueError("output_size must be at least 2")
         self.in_channels, self.out_channels, self.activation = int(input_size), int(output_size), act
         hm = output_size // 2
-        _Linear = _holders()._Linear
+        _Linear = dense.Linear
         self.msg_mlp = nn.Sequential(_Linear(2 * input_size, hm), nn.Identity(), _Linear(hm, output_size),
                                      nn.Identity())
         self.gate_mlp = nn.Sequential(_Linear(output_size, 1), nn.Identity())
         self.update_mlp = nn.Sequential(_Linear(input_size + output_size, output_size), nn.Identity(),
                                         _Linear(output_size, output_size))
         self.skip_conn = _Linear(input_size, output_size) if input_size != output_size else nn.Identity()
-        self._packs = _holders()._PackCache()
+        self._packs = dense.PackCache()
 
     def _params(self):
         ps = [self.msg_mlp[0].weight, self.msg_mlp[0].bias, self.msg_mlp[2].weight, self.msg_mlp[2].bias,
@@ -215,26 +209,22 @@ class GatedGraphNetwork(nn.Module):
         return ps
 
     def _device_packs(self, device):
-        F, H = self.in_channels, self.out_channels
-        hm = H // 2
-        ps = self._params()
-        _dev = _holders()._dev
-
-        def lin(w, bias):
-            wd = _dev(w, device)
-            return hip.dense_pack(wd), hip.dense_pack(wd, transpose=True), _dev(bias, device).contiguous()
+        """``(msg_mlp.0 stacked, edge MLP + gate, update_mlp.0, update_mlp.2, skip or None)`` on ``device``."""
+        F, hm = self.in_channels, self.out_channels // 2
+        ps = self._params()[:6]
 
         def build():
-            wc = _w1_stacked(_dev(ps[0], device), F)
+            w1, b1, w2, b2, wg, bg = [dense.dev(q, device) for q in ps]
+            wc = _w1_stacked(w1, F)
             bc = torch.zeros(2 * hm, dtype=torch.float32, device=device)
-            bc[:hm].copy_(_dev(ps[1], device))
-            w2 = _dev(ps[2], device)
-            edge = (hip.dense_pack(w2), hip.dense_pack(w2, transpose=True), _dev(ps[3], device).contiguous(),
-                    _dev(ps[4], device).reshape(-1).contiguous(), _dev(ps[5], device).reshape(1).contiguous())
-            skip = lin(ps[10], ps[11]) if len(ps) > 10 else None
-            return ((hip.dense_pack(wc), hip.dense_pack(wc, transpose=True), bc), edge, lin(ps[6], ps[7]),
-                    lin(ps[8], ps[9]), skip)
-        return self._packs.get("layer", ps, device, build)
+            bc[:hm].copy_(b1)
+            edge = (hip.dense_pack(w2), hip.dense_pack(w2, transpose=True), b2.contiguous(),
+                    wg.reshape(-1).contiguous(), bg.reshape(1).contiguous())
+            return (hip.dense_pack(wc), hip.dense_pack(wc, transpose=True), bc), edge
+        msg, edge = self._packs.get("msg", ps, device, build)
+        skip = None if isinstance(self.skip_conn, nn.Identity) else self._packs.linear("skip", self.skip_conn, device)
+        return (msg, edge, self._packs.linear("update0", self.update_mlp[0], device),
+                self._packs.linear("update2", self.update_mlp[2], device), skip)
 
     def _rows(self, x, plan, b):
         """The layer on rows ``x [b n, input_size]`` (float32, on the GPU) with a ready plan."""
@@ -247,10 +237,7 @@ class GatedGraphNetwork(nn.Module):
     def forward(self, x, edge_index=None):
         if x.dim() < 2 or x.shape[-1] != self.in_channels:
             raise ValueError(f"expected [..., n, {self.in_channels}], got {tuple(x.shape)}")
-        on_cpu = not x.is_cuda
-        if on_cpu:
-            hip.require_gpu()
-            x = x.cuda()
+        x, on_cpu = hip.to_gpu(x)
         n = x.shape[-2]
         lead = x.shape[:-2]
         plan = plan_for(edge_index, n, x.device)

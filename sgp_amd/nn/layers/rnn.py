@@ -20,12 +20,7 @@ import torch
 from torch import nn
 
 from ... import hip
-
-
-def _sm():
-    """The SGP decoder's pieces this layer reuses (imported late: the models import this package)."""
-    from ..models import sgp_model
-    return sgp_model
+from .. import dense
 
 
 def _window_index(b, s, n, device):
@@ -154,10 +149,10 @@ class RNN(nn.Module):
         self.input_size, self.dropout = int(input_size), float(dropout)
         self.rnn = holder(input_size=input_size, hidden_size=hidden_size, num_layers=n_layers, dropout=dropout)
         if output_size is not None:
-            self.readout = _sm()._Linear(hidden_size, output_size)
+            self.readout = dense.Linear(hidden_size, output_size)
         else:
             self.register_parameter('readout', None)
-        self._packs = _sm()._PackCache()
+        self._packs = dense.PackCache()
         self._idx = {}
 
     def _layer_params(self, l):
@@ -166,12 +161,11 @@ class RNN(nn.Module):
     def _layer_packs(self, l, device):
         w_ih, w_hh, b_ih, b_hh = ps = self._layer_params(l)
         H, cell = self.hidden_size, self.cell
-        _dev = _sm()._dev
 
         def build():
-            wi = _dev(w_ih, device)
-            bias = _dev(b_ih, device).clone()
-            bh = _dev(b_hh, device)
+            wi = dense.dev(w_ih, device)
+            bias = dense.dev(b_ih, device).clone()
+            bh = dense.dev(b_hh, device)
             if cell == "lstm":
                 bias += bh
                 bhn = None
@@ -179,7 +173,7 @@ class RNN(nn.Module):
                 bias[:2 * H] += bh[:2 * H]                            # b_hn stays inside r * (W_hn h + b_hn)
                 bhn = bh[2 * H:].clone()
             return (hip.dense_pack(wi), hip.dense_pack(wi, transpose=True), bias,
-                    hip.rnn_window_pack(_dev(w_hh, device), cell), bhn)
+                    hip.rnn_window_pack(dense.dev(w_hh, device), cell), bhn)
         return self._packs.get(f"l{l}", ps, device, build)
 
     def _index(self, b, s, n, device):
@@ -198,10 +192,7 @@ class RNN(nn.Module):
         if x.shape[-1] != self.input_size:
             raise ValueError(f"x: expected {self.input_size} input features, got {x.shape[-1]}")
         hip.rnn_window_require(self.cell, self.hidden_size)            # the reason, before any launch
-        on_cpu = not x.is_cuda
-        if on_cpu:
-            hip.require_gpu()
-            x = x.cuda()
+        x, on_cpu = hip.to_gpu(x)
         dev = x.device
         b, s, n, f = x.shape
         x2 = x.float().contiguous().reshape(b * s * n, f)
@@ -209,7 +200,7 @@ class RNN(nn.Module):
         p = self.dropout if (self.training and L > 1) else 0.
         spec = (self.cell, H, L, s, M, p, bool(return_last_state))
         packs = [self._layer_packs(l, dev) for l in range(L)]
-        seeds = tuple(_sm()._seed() if p > 0. else 0 for _ in range(L - 1)) + (0,)
+        seeds = tuple(dense.seed() if p > 0. else 0 for _ in range(L - 1)) + (0,)
         idx = self._index(b, s, n, dev)
         params = [q for l in range(L) for q in self._layer_params(l)]
         if torch.is_grad_enabled() and (x2.requires_grad or any(q.requires_grad for q in params)):
@@ -221,13 +212,6 @@ class RNN(nn.Module):
         else:
             y = out.reshape(s, b, n, H).permute(1, 0, 2, 3)
         if self.readout is not None:
-            lin = self.readout
-            _dev = _sm()._dev
-
-            def build():
-                wd = _dev(lin.weight, dev)
-                return hip.dense_pack(wd), hip.dense_pack(wd, transpose=True), _dev(lin.bias, dev).contiguous()
-            pk = self._packs.get("readout", (lin.weight, lin.bias), dev, build)
-            rows = y.reshape(-1, H)
-            y = _sm()._DenseFn.apply(rows, lin.weight, lin.bias, None, rows.shape[0], None, 0., 0, pk).reshape(*y.shape[:-1], -1)
+            packs = self._packs.linear("readout", self.readout, dev)
+            y = dense.linear(y.reshape(-1, H), self.readout, packs).reshape(*y.shape[:-1], -1)
         return y.cpu() if on_cpu else y

@@ -5,8 +5,8 @@ tsl/nn/utils/utils.py:56-75), run the ``Reservoir`` over each sample's window, k
 train a ``LinearReadout`` on it.  Here the reservoir is one launch of ``sgp_reservoir_window_f32``
 (``Reservoir.last_state``: ``x`` and ``u`` read where they lie, every layer's state on the compute unit for the
 whole window, one store) and the readout is the decoder's dense kernel with the ``b n (h c) -> b h n c`` store map,
-trained through ``sgp_dense_wgrad_f32`` (``_TrunkFn`` with no MLP in front).  No torch GEMM, no concatenated or
-permuted copy of the batch, nothing of the size of the state sequence.
+trained through ``sgp_dense_wgrad_f32`` (``dense.readout``: ``TrunkFn`` with no MLP in front).  No torch GEMM, no
+concatenated or permuted copy of the batch, nothing of the size of the state sequence.
 
 Module paths, shapes and construction order are the reference's: ``reservoir.reservoir_layers.{i}.{w_ih, w_hh,
 b_ih}`` (frozen) and ``readout.readout.0.{weight, bias}``, so ``torch.manual_seed(k); ESNModel(...)`` draws the
@@ -17,9 +17,9 @@ import torch
 from torch import nn
 
 from ... import hip
+from .. import dense
 from ..encoders._args import opt_list
 from ..reservoir import Reservoir
-from .sgp_model import _LinearReadout, _PackCache, _TrunkFn, _dev
 
 
 class ESNModel(nn.Module):
@@ -36,22 +36,16 @@ class ESNModel(nn.Module):
         self.reservoir = Reservoir(input_size=input_size + exog_size, hidden_size=hidden_size, num_layers=rec_layers,
                                    leaking_rate=leaking_rate, spectral_radius=spectral_radius, density=density,
                                    activation=activation)                           # esn_model.py:23-29
-        self.readout = _LinearReadout(hidden_size * rec_layers, output_size, horizon)   # esn_model.py:31-35
-        self._packs = _PackCache()
+        self.readout = dense.LinearReadout(hidden_size * rec_layers, output_size, horizon)   # esn_model.py:31-35
+        self._packs = dense.PackCache()
 
     # -------------------------------------------------------------- readout
     def _readout(self, state):
         """``state [b, n, L*R]`` (device) -> ``[b, horizon, n, output_size]``."""
         b, n, k = state.shape
         lin = self.readout.readout[0]
-        dev = state.device
-
-        def build():
-            wd = _dev(lin.weight, dev)
-            return hip.dense_pack(wd), hip.dense_pack(wd, transpose=True), _dev(lin.bias, dev).contiguous()
-        packs = [self._packs.get("readout", (lin.weight, lin.bias), dev, build)]
-        spec = (False, 0, k, None, 0., self.horizon, self.output_size, b, n)
-        return _TrunkFn.apply(state.reshape(b * n, k), spec, packs, (), lin.weight, lin.bias)
+        packs = self._packs.linear("readout", lin, state.device)
+        return dense.readout(state.reshape(b * n, k), lin, packs, b, n, self.horizon, self.output_size)
 
     @staticmethod
     def _no_grad_input(x, name):
@@ -74,10 +68,7 @@ class ESNModel(nn.Module):
         self._check_features(x, u, 2)
         self._no_grad_input(x, "x")
         self._no_grad_input(u, "u")
-        on_cpu = not x.is_cuda
-        if on_cpu:
-            hip.require_gpu()
-            x = x.cuda()
+        x, on_cpu = hip.to_gpu(x)
         with torch.no_grad():
             state = self.reservoir.last_state(x, None if u is None else u.to(x.device))
         y = self._readout(state)

@@ -5,8 +5,8 @@ and ``GatedGraphNetworkMLPModel`` (``lib/nn/models/gated_gn_model.py:83-159``, `
 window's last ``input_window_size`` steps flattened per node, a linear input encoder, residual MLP encoder layers, a
 node embedding, ``GatedGraphNetwork`` layers, ``decoder(x) + x`` and a linear readout.  Every matrix product and every
 per-edge operation is a HIP kernel, forward and backward (``sgp_dense_f32`` / ``sgp_dense_wgrad_f32`` /
-``sgp_row_segsum_f32`` of the SGP decoder, ``sgp_gated_gn_edge_f32`` / ``_bwd_f32`` for the edges); torch adds the
-residuals.  Parameters keep the reference's module paths, shapes and construction order.
+``sgp_row_segsum_f32`` through ``sgp_amd.nn.dense``, ``sgp_gated_gn_edge_f32`` / ``_bwd_f32`` for the edges); torch
+adds the residuals.  Parameters keep the reference's module paths, shapes and construction order.
 
 Not offered: ``activation='elu'`` (the reference's parser lists it, none of its configs use it; the dense kernel has no
 ELU) raises ``NotImplementedError`` at construction.
@@ -15,9 +15,9 @@ import torch
 from torch import nn
 
 from ... import hip
+from .. import dense
 from ..encoders._args import opt_list, str_to_bool
 from ..layers.gated_gn import GatedGraphNetwork, plan_for
-from .sgp_model import (_checked_index, _DenseFn, _dev, _Linear, _PackCache, _StaticGraphEmbedding, _TrunkFn)
 
 
 class _EmbAddFn(torch.autograd.Function):
@@ -26,7 +26,7 @@ class _EmbAddFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, emb, gather, b, n):
-        e = emb if emb.is_cuda else _dev(emb, x.device)
+        e = emb if emb.is_cuda else dense.dev(emb, x.device)
         if gather is not None:
             e = hip.gather_nodes(e.detach().float()[None].contiguous(), gather)[0]
         ctx.save_for_backward(gather)
@@ -66,26 +66,20 @@ class GatedGraphNetworkModel(nn.Module):
         self.hidden_size, self.horizon, self.output_size = int(hidden_size), int(horizon), int(output_size)
         self.activation = act
         feat = self.input_size + self.exog_size
-        self.input_encoder = nn.Sequential(_Linear(feat * input_window_size, hidden_size))
-        self.encoder_layers = nn.ModuleList([nn.Sequential(_Linear(hidden_size, hidden_size), nn.Identity(),
-                                                           _Linear(hidden_size, hidden_size))
+        self.input_encoder = nn.Sequential(dense.Linear(feat * input_window_size, hidden_size))
+        self.encoder_layers = nn.ModuleList([nn.Sequential(dense.Linear(hidden_size, hidden_size), nn.Identity(),
+                                                           dense.Linear(hidden_size, hidden_size))
                                              for _ in range(enc_layers)])
-        self.emb = _StaticGraphEmbedding(n_tokens=n_nodes, emb_size=hidden_size)
+        self.emb = dense.StaticGraphEmbedding(n_tokens=n_nodes, emb_size=hidden_size)
         self.gcn_layers = nn.ModuleList([GatedGraphNetwork(hidden_size, hidden_size, activation=act)
                                          for _ in range(gnn_layers)])
-        self.decoder = nn.Sequential(_Linear(hidden_size, hidden_size), nn.Identity())
-        self.readout = nn.Sequential(_Linear(hidden_size, horizon * output_size), nn.Identity())
-        self._packs = _PackCache()
+        self.decoder = nn.Sequential(dense.Linear(hidden_size, hidden_size), nn.Identity())
+        self.readout = nn.Sequential(dense.Linear(hidden_size, horizon * output_size), nn.Identity())
+        self._packs = dense.PackCache()
 
     # -------------------------------------------------------------- pieces
     def _lin(self, name, lin, x, activation=None):
-        dev = x.device
-
-        def build():
-            wd = _dev(lin.weight, dev)
-            return hip.dense_pack(wd), hip.dense_pack(wd, transpose=True), _dev(lin.bias, dev).contiguous()
-        packs = self._packs.get(name, (lin.weight, lin.bias), dev, build)
-        return _DenseFn.apply(x, lin.weight, lin.bias, None, x.shape[0], activation, 0., 0, packs), packs
+        return dense.linear(x, lin, self._packs.linear(name, lin, x.device), activation)
 
     def _window_rows(self, x, u):
         """``maybe_cat_exog`` + ``'b s n f -> b n (s f)'`` of the last ``input_window_size`` steps: one node-sized
@@ -114,18 +108,14 @@ class GatedGraphNetworkModel(nn.Module):
         return None
 
     def _encode(self, rows):
-        h, _ = self._lin("input", self.input_encoder[0], rows)
+        h = self._lin("input", self.input_encoder[0], rows)
         for i, layer in enumerate(self.encoder_layers):
-            h1, _ = self._lin(f"enc{i}.0", layer[0], h, self.activation)
-            h2, _ = self._lin(f"enc{i}.2", layer[2], h1)
-            h = h2 + h
+            h1 = self._lin(f"enc{i}.0", layer[0], h, self.activation)
+            h = self._lin(f"enc{i}.2", layer[2], h1) + h
         return h
 
     def _run(self, x, edge_index, u, node_index):
-        on_cpu = not x.is_cuda
-        if on_cpu:
-            hip.require_gpu()
-            x = x.cuda()
+        x, on_cpu = hip.to_gpu(x)
         dev = x.device
         xin = x.float()
         rows, b, n = self._window_rows(xin, u)
@@ -136,16 +126,9 @@ class GatedGraphNetworkModel(nn.Module):
             h = _EmbAddFn.apply(h, self.emb.emb, gather, b, n)
         for layer in self.gcn_layers:
             h = layer._rows(h, plan, b)
-        d, _ = self._lin("decoder", self.decoder[0], h, self.activation)
-        h = d + h
+        h = self._lin("decoder", self.decoder[0], h, self.activation) + h
         lin = self.readout[0]
-
-        def build():
-            wd = _dev(lin.weight, dev)
-            return hip.dense_pack(wd), hip.dense_pack(wd, transpose=True), _dev(lin.bias, dev).contiguous()
-        packs = [self._packs.get("readout", (lin.weight, lin.bias), dev, build)]
-        spec = (False, 0, self.hidden_size, None, 0., self.horizon, self.output_size, b, n)
-        y = _TrunkFn.apply(h, spec, packs, (), lin.weight, lin.bias)
+        y = dense.readout(h, lin, self._packs.linear("readout", lin, dev), b, n, self.horizon, self.output_size)
         return y.cpu() if on_cpu else y
 
     def forward(self, x, edge_index=None, u=None, **kwargs):
@@ -179,7 +162,8 @@ class GatedGraphNetworkMLPModel(GatedGraphNetworkModel):
     def _token_index(self, node_index, b, n, dev):
         if node_index is None:
             return super()._token_index(node_index, b, n, dev)
-        idx = _checked_index(torch.as_tensor(node_index, device=dev).reshape(-1), self.emb.emb.shape[0], "node_index")
+        idx = torch.as_tensor(node_index, device=dev).reshape(-1)
+        idx = dense.checked_index(idx, self.emb.emb.shape[0], "node_index")
         if idx.numel() != n:
             raise ValueError(f"node_index has {idx.numel()} entries, the batch {n} nodes")
         return idx.to(torch.int32).contiguous()

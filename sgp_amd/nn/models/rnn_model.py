@@ -4,18 +4,18 @@
 ``input_encoder`` (a ``ConditionalBlock``, ``tsl/nn/blocks/encoders/conditional.py:43-67``, or ``Linear + ReLU``) ->
 ``RNN`` (``sgp_amd.nn.layers.rnn``: LSTM / GRU over the window, last state) -> ``MLPDecoder``
 (``tsl/nn/blocks/decoders/mlp_decoder.py:38-46``: MLP, linear readout, ``'b n (h c) -> b h n c'`` in the store).  Every
-matrix product is a HIP kernel, forward and backward (``sgp_dense_f32`` / ``sgp_dense_wgrad_f32`` of the SGP decoder,
-``sgp_rnn_window_fwd_f32`` / ``_bwd_f32`` for the recurrence); torch adds the two branches of the conditional block
-(``u`` is projected once per ``(b, s)`` and broadcast over the nodes by that add) and applies its ReLU.  Parameters keep
-the reference's module paths, shapes and construction order.
+matrix product is a HIP kernel, forward and backward (``sgp_dense_f32`` / ``sgp_dense_wgrad_f32`` through
+``sgp_amd.nn.dense``, ``sgp_rnn_window_fwd_f32`` / ``_bwd_f32`` for the recurrence); torch adds the two branches of the
+conditional block (``u`` is projected once per ``(b, s)`` and broadcast over the nodes by that add) and applies its
+ReLU.  Parameters keep the reference's module paths, shapes and construction order.
 """
 import torch
 from torch import nn
 
 from ... import hip
+from .. import dense
 from ..encoders._args import opt_list
 from ..layers import rnn as _rnn_layer
-from .sgp_model import _DenseFn, _dev, _Linear, _MLP, _PackCache, _seed, _TrunkFn
 
 
 class _ConditionalBlock(nn.Module):
@@ -23,19 +23,19 @@ class _ConditionalBlock(nn.Module):
 
     def __init__(self, input_size, exog_size, output_size):
         super().__init__()
-        self.input_affinity = _Linear(input_size, output_size)
-        self.condition_affinity = _Linear(exog_size, output_size)
-        self.out_inputs_affinity = _Linear(output_size, output_size)
-        self.out_cond_affinity = _Linear(output_size, output_size, bias=False)
+        self.input_affinity = dense.Linear(input_size, output_size)
+        self.condition_affinity = dense.Linear(exog_size, output_size)
+        self.out_inputs_affinity = dense.Linear(output_size, output_size)
+        self.out_cond_affinity = dense.Linear(output_size, output_size, bias=False)
         self.register_parameter('skip_conn', None)
 
 
-class _MLPReadout(_MLP):
+class _MLPReadout(dense.MLP):
     """tsl ``MLP(output_size=...)``: the Dense layers, then ``readout`` (mlp.py:43-44)."""
 
     def __init__(self, input_size, hidden_size, output_size, n_layers):
         super().__init__(input_size, hidden_size, None, n_layers)
-        self.readout = _Linear(hidden_size, output_size)
+        self.readout = dense.Linear(hidden_size, output_size)
 
 
 class _MLPDecoder(nn.Module):
@@ -73,25 +73,15 @@ class RNNModel(nn.Module):
         if self.exog_size > 0:
             self.input_encoder = _ConditionalBlock(input_size, exog_size, hidden_size)
         else:
-            self.input_encoder = nn.Sequential(_Linear(input_size, hidden_size), nn.Identity())
+            self.input_encoder = nn.Sequential(dense.Linear(input_size, hidden_size), nn.Identity())
         self.rnn = _rnn_layer.RNN(input_size=hidden_size, hidden_size=hidden_size, n_layers=rec_layers,
                                   dropout=rec_dropout, cell=cell_type)
         self.readout = _MLPDecoder(hidden_size, ff_size, output_size, horizon, ff_layers)
-        self._packs = _PackCache()
+        self._packs = dense.PackCache()
 
     # -------------------------------------------------------------- pieces
     def _lin(self, name, lin, rows, activation=None):
-        dev = rows.device
-
-        def build():
-            wd = _dev(lin.weight, dev)
-            bias = _dev(lin.bias, dev).contiguous() if lin.bias is not None else \
-                torch.zeros(lin.weight.shape[0], dtype=torch.float32, device=dev)
-            return hip.dense_pack(wd), hip.dense_pack(wd, transpose=True), bias
-        ps = (lin.weight,) if lin.bias is None else (lin.weight, lin.bias)
-        packs = self._packs.get(name, ps, dev, build)
-        bias = lin.bias if lin.bias is not None else packs[2]         # no bias: a constant zero vector, no gradient
-        return _DenseFn.apply(rows, lin.weight, bias, None, rows.shape[0], activation, 0., 0, packs)
+        return dense.linear(rows, lin, self._packs.linear(name, lin, rows.device), activation)
 
     def _encode(self, x, u):
         b, s, n, f = x.shape
@@ -125,27 +115,20 @@ class RNNModel(nn.Module):
     def _decode(self, h, b, n):
         dev = h.device
         mlp = self.readout.readout[0]
-        packs, params = [], []
         lins = [d.layer[0] for d in mlp.mlp] + [mlp.readout]
-        for i, lin in enumerate(lins):
-            def build(lin=lin):
-                wd = _dev(lin.weight, dev)
-                return hip.dense_pack(wd), hip.dense_pack(wd, transpose=True), _dev(lin.bias, dev).contiguous()
-            packs.append(self._packs.get(f"ff{i}", (lin.weight, lin.bias), dev, build))
-            params += [lin.weight, lin.bias]
+        packs = [self._packs.linear(f"ff{i}", lin, dev) for i, lin in enumerate(lins)]
+        params = [q for lin in lins for q in (lin.weight, lin.bias)]
         p = self.ff_dropout if self.training else 0.
-        seeds = tuple(_seed() if p > 0. else 0 for _ in range(self.ff_layers))
-        spec = (False, self.ff_layers, self.ff_size, self.activation, p, self.horizon, self.output_size, b, n)
-        return _TrunkFn.apply(h, spec, packs, seeds, *params)
+        seeds = tuple(dense.seed() if p > 0. else 0 for _ in range(self.ff_layers))
+        spec = dense.TrunkSpec(resnet=False, n_layers=self.ff_layers, hidden=self.ff_size, activation=self.activation,
+                               p=p, horizon=self.horizon, channels=self.output_size, b=b, n=n)
+        return dense.TrunkFn.apply(h, spec, packs, seeds, *params)
 
     def forward(self, x, u=None, **kwargs):
         if x.dim() != 4 or x.shape[-1] != self.input_size:
             raise ValueError(f"x: expected [b, s, n, {self.input_size}], got {tuple(x.shape)}")
         hip.rnn_window_require(self.rnn.cell, self.hidden_size)       # the reason, before any launch
-        on_cpu = not x.is_cuda
-        if on_cpu:
-            hip.require_gpu()
-            x = x.cuda()
+        x, on_cpu = hip.to_gpu(x)
         x = x.float().contiguous()
         b, s, n, _ = x.shape
         h = self._encode(x, u).reshape(b, s, n, self.hidden_size)

@@ -43,8 +43,7 @@ def encode_dataset(dataset, encoder_class, encoder_kwargs, encode_exogenous=True
     started = time()
     if return_device:                 # every encoder answers on the device of its input
         from . import hip
-        hip.require_gpu()
-        x = x.cuda()
+        x, _ = hip.to_gpu(x)
     from .multigpu import resolve_gpus
     if shard_steps is not None:
         embedding = encoder(x, edge_index=dataset.edge_index, edge_weight=dataset.edge_weight, gpus=gpus,

@@ -113,7 +113,7 @@ def test_input_checks_do_not_need_a_gpu():
     m = SGPModel(12, 3, 5, 20, 16, 1, 1, 1, True, fully_connected=True)
     with pytest.raises(ValueError, match="expected"):
         m(torch.zeros(2, 5, 13))                                                # wider input than input_size
-    from sgp_amd.nn.models.sgp_model import _checked_index
+    from sgp_amd.nn.dense import checked_index as _checked_index
     with pytest.raises(IndexError, match="out of range"):
         _checked_index(torch.tensor([0, 5]), 5, "node_index")
     with pytest.raises(IndexError, match="out of range"):
