@@ -48,10 +48,13 @@ extern "C" {
  * 2 (round 5): sgp_spmm_split_f32 takes per-column scale tables and a per-row plan array; sgp_col_stats_f32,
  * sgp_split_prepare_f32, sgp_launch_predicate added; round 4 had already removed sgp_spmm_mfma / pipe / blk_*, widened
  * sgp_spmm_colblock_f32 by the halo arguments and grown sgp_reservoir_workspace_bytes (bf16-piece fragments). */
+/* (still 3: sgp_spmm_split_banded_f32 / _wide_banded_f32 and sgp_split_plan_bands were added, and the two planner
+ * entries sgp_split_plan_deal / _fill gained `nnz` behind `col` -- their only caller is sgp_amd/splitplan.py) */
 #define SGP_ABI_VERSION 3
 
 #define SGP_EINVAL   (-1)  /* bad size / null pointer / misaligned stride */
 #define SGP_EUNSUP   (-2)  /* shape outside what the kernels are built for */
+#define SGP_ENOMEM   (-3)  /* a host-side planner ran out of memory */
 
 /* activations of lib/nn/reservoir/reservoir.py:37-41 */
 #define SGP_ACT_TANH      0
@@ -272,6 +275,25 @@ int32_t sgp_spmm_split_waves(void);
 int32_t sgp_spmm_split_rows_per_wave(void);
 int32_t sgp_spmm_split_max_feat(void);
 
+/* The same hop with the caller's choice of WALK, the mapping from workgroup to (tile, time chunk) -- the arithmetic of
+ * a result element does not depend on it, so every walk gives the same bits.  walk = 0: chosen here, exactly
+ * sgp_spmm_split_f32; 1: tile-major (an XCD walks its own tiles over all time); 2: time-major (an XCD walks ITS time
+ * chunks, chunk % 8 == xcd, over all tiles: operators whose source rows of one step fit an L2); 3: BANDED time-major
+ * (DESIGN 4.2e): band_first[n_bands + 1] (DEVICE memory; strictly increasing tile indices from 0 to n_tiles, made by
+ * sgp_split_plan_bands) cuts the plan's tile list into bands of consecutive tiles whose distinct staged rows of one step
+ * fit an L2; inside a band the XCDs walk time-major over the band's tiles, the bands follow each other in workgroup
+ * order inside the one launch, in workgroups of at most 32 steps unless t_chunk names a length.  band_first is read for
+ * walk = 3 only. */
+int sgp_spmm_split_banded_f32(const int32_t* hdr, const int32_t* rowid, const int32_t* ucol, const void* afr,
+                              const int32_t* adr, const float* rinv, int32_t n_tiles,
+                              const float* X, int64_t x_row_stride, int64_t x_batch_stride,
+                              const float* X_halo, int64_t xh_row_stride, int64_t xh_batch_stride, int32_t n_own,
+                              float* Y, int64_t y_row_stride, int64_t y_batch_stride,
+                              int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
+                              const float* x_tab, int32_t accumulate, int32_t t_chunk,
+                              int32_t walk, const int32_t* band_first, int32_t n_bands,
+                              const int32_t* pred, int32_t run_if, sgp_stream_t stream);
+
 /* The same kernel in its WIDE form (csrc/spmm_split_wide.hip): 8 waves x 16 rows x 14 chunks -- 448 columns per wave, two
  * waves per SIMD.  For operators whose rows exceed the standard form's 224 columns (the reference's full large-scale
  * graphs, config/largescale/sgp_pv.yaml / sgp_cer.yaml with experiments/run_largescale_sgp.py:167-170: ~740 / ~495
@@ -285,6 +307,15 @@ int sgp_spmm_split_wide_f32(const int32_t* hdr, const int32_t* rowid, const int3
                             float* Y, int64_t y_row_stride, int64_t y_batch_stride,
                             int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
                             const float* x_tab, int32_t accumulate, int32_t t_chunk, const int32_t* pred, int32_t run_if, sgp_stream_t stream);
+int sgp_spmm_split_wide_banded_f32(const int32_t* hdr, const int32_t* rowid, const int32_t* ucol, const void* afr,
+                                   const int32_t* adr, const float* rinv, int32_t n_tiles,
+                                   const float* X, int64_t x_row_stride, int64_t x_batch_stride,
+                                   const float* X_halo, int64_t xh_row_stride, int64_t xh_batch_stride, int32_t n_own,
+                                   float* Y, int64_t y_row_stride, int64_t y_batch_stride,
+                                   int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
+                                   const float* x_tab, int32_t accumulate, int32_t t_chunk,
+                                   int32_t walk, const int32_t* band_first, int32_t n_bands,
+                                   const int32_t* pred, int32_t run_if, sgp_stream_t stream);
 int32_t sgp_spmm_split_wide_chunks(void);
 int32_t sgp_spmm_split_wide_max_union(void);
 int32_t sgp_spmm_split_wide_waves(void);
@@ -300,17 +331,25 @@ int32_t sgp_spmm_split_wide_max_feat(void);
  * exceeds a wave's budget (no one-pass plan), -1 on a bad argument.
  * sgp_split_plan_fill: the kernel's arrays (formats: sgp_spmm_split_f32 above) for that deal, tiles in parallel on
  * `threads` host threads (0 = all); stats[8] = tiles, waves, rows per wave, rows per tile, staged rows per result row,
- * chunk fill, largest staged-row count, ||A||_inf. */
-int64_t sgp_split_plan_deal(const int64_t* rowptr, const int64_t* col, int64_t n_rows, int64_t n_cols,
+ * chunk fill, largest staged-row count, ||A||_inf.
+ * sgp_split_plan_bands: cuts the tile list (ucol[n_tiles][max_union] of a filled plan, host memory) into bands of
+ * consecutive tiles for sgp_spmm_split_banded_f32: a band closes when the next tile would take its distinct staged
+ * rows over col_budget (a tile beyond the budget on its own is a band of one).  Writes band_first (capacity
+ * n_tiles + 1): first tile of every band, then n_tiles; returns the number of bands.
+ * All three check their CSR (rowptr[0] == 0, non-decreasing, rowptr[n_rows] <= nnz = the length of col / val) and
+ * let no C++ exception out: SGP_EINVAL / SGP_ENOMEM instead. */
+int64_t sgp_split_plan_deal(const int64_t* rowptr, const int64_t* col, int64_t nnz, int64_t n_rows, int64_t n_cols,
                             const int64_t* order, int64_t n_order,
                             int32_t waves, int32_t chunks, int32_t max_union, int32_t rows_per_wave,
                             int64_t* wave_of_row, int64_t* slot_of_row, int64_t* tile_of_wave, int64_t* rows_of_wave);
-int sgp_split_plan_fill(const int64_t* rowptr, const int64_t* col, const float* val, int64_t n_rows, int64_t n_cols,
+int sgp_split_plan_fill(const int64_t* rowptr, const int64_t* col, const float* val, int64_t nnz, int64_t n_rows, int64_t n_cols,
                         const int64_t* wave_of_row, const int64_t* slot_of_row, const int64_t* tile_of_wave,
                         const int64_t* rows_of_wave, int64_t n_waves, int64_t n_tiles,
                         int32_t waves, int32_t chunks, int32_t max_union,
                         int32_t* hdr, int32_t* rowid, int32_t* ucol, void* afr, int32_t* adr, float* rinv,
                         double* stats, int32_t threads);
+int64_t sgp_split_plan_bands(const int32_t* ucol, int64_t n_tiles, int32_t max_union, int64_t n_cols,
+                             int64_t col_budget, int32_t* band_first);
 
 /* Column-blocked hop for graphs without locality (lib/sgp_preprocessing.py:202, `x = adj @ x`; plan:
  * sgp_amd/colblock.py).  The columns are cut into n_blocks blocks of consecutive columns whose source

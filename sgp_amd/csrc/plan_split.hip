@@ -10,6 +10,8 @@
 #include <string.h>
 #include <algorithm>
 #include <atomic>
+#include <new>
+#include <system_error>
 #include <thread>
 #include <vector>
 
@@ -185,15 +187,36 @@ int64_t fill_tile(const FillArgs& a, int64_t t, const int64_t* first_wave, const
     return keys;
 }
 
+// rowptr of a CSR with nnz stored entries: starts at 0, never decreases, ends within the arrays
+const char* rowptr_fault(const int64_t* rowptr, int64_t n_rows, int64_t nnz) {
+    if (nnz < 0) return "negative nnz";
+    if (n_rows > 0 && rowptr[0] != 0) return "rowptr[0] != 0";
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (rowptr[r + 1] < rowptr[r]) return "rowptr decreases";
+    if (n_rows > 0 && rowptr[n_rows] > nnz) return "rowptr[n_rows] > nnz";
+    return nullptr;
+}
+
+// the entries below are called through a C ABI: nothing may leave them as an exception (std::bad_alloc from the
+// vectors, std::system_error from std::thread)
+template <class R, class F> R guarded(const char* what, F&& body) {
+    try { return body(); }
+    catch (const std::bad_alloc&) { return (R)sgp::fail(SGP_ENOMEM, "%s: out of host memory", what); }
+    catch (const std::exception& e) { return (R)sgp::fail(SGP_EINVAL, "%s: %s", what, e.what()); }
+    catch (...) { return (R)sgp::fail(SGP_EINVAL, "%s: unknown exception", what); }
+}
+
 }  // namespace
 
-extern "C" int64_t sgp_split_plan_deal(const int64_t* rowptr, const int64_t* col, int64_t n_rows, int64_t n_cols,
+extern "C" int64_t sgp_split_plan_deal(const int64_t* rowptr, const int64_t* col, int64_t nnz, int64_t n_rows, int64_t n_cols,
                                        const int64_t* order, int64_t n_order,
                                        int32_t waves, int32_t chunks, int32_t max_union, int32_t rows_per_wave,
                                        int64_t* wave_of_row, int64_t* slot_of_row, int64_t* tile_of_wave, int64_t* rows_of_wave) {
-    if (!rowptr || (!col && n_rows > 0 && rowptr[n_rows] > 0) || !wave_of_row || !slot_of_row || !tile_of_wave || !rows_of_wave ||
+  return guarded<int64_t>("sgp_split_plan_deal", [&]() -> int64_t {
+    if (!rowptr || (!col && nnz > 0) || !wave_of_row || !slot_of_row || !tile_of_wave || !rows_of_wave ||
         n_rows < 0 || n_cols < 0 || waves < 1 || chunks < 1 || max_union < 1 || rows_per_wave < 1 || (order && n_order < 0))
         return sgp::fail(SGP_EINVAL, "sgp_split_plan_deal: bad argument");
+    if (const char* f = rowptr_fault(rowptr, n_rows, nnz)) return sgp::fail(SGP_EINVAL, "sgp_split_plan_deal: malformed CSR: %s", f);
     const int64_t cap = 32ll * chunks;
     std::vector<int64_t> wmark(n_cols, -1), tmark(n_cols, -1), c;
     for (int64_t r = 0; r < n_rows; ++r) wave_of_row[r] = slot_of_row[r] = -1;
@@ -231,18 +254,23 @@ extern "C" int64_t sgp_split_plan_deal(const int64_t* rowptr, const int64_t* col
         rows_of_wave[wave] = ++w_rows;
     }
     return wave + 1;
+  });
 }
 
-extern "C" int sgp_split_plan_fill(const int64_t* rowptr, const int64_t* col, const float* val, int64_t n_rows, int64_t n_cols,
+extern "C" int sgp_split_plan_fill(const int64_t* rowptr, const int64_t* col, const float* val, int64_t nnz, int64_t n_rows, int64_t n_cols,
                                    const int64_t* wave_of_row, const int64_t* slot_of_row, const int64_t* tile_of_wave,
                                    const int64_t* rows_of_wave, int64_t n_waves, int64_t n_tiles,
                                    int32_t waves, int32_t chunks, int32_t max_union,
                                    int32_t* hdr, int32_t* rowid, int32_t* ucol, void* afr, int32_t* adr, float* rinv,
                                    double* stats, int32_t threads) {
+  return guarded<int>("sgp_split_plan_fill", [&]() -> int {
     SGP_REQUIRE(rowptr && col && val && wave_of_row && slot_of_row && tile_of_wave && rows_of_wave && hdr && rowid && ucol &&
                 afr && adr && rinv && stats, "sgp_split_plan_fill: null pointer");
     SGP_REQUIRE(n_rows > 0 && n_cols > 0 && n_waves > 0 && n_tiles > 0 && waves >= 1 && 2 * waves < 64 && chunks >= 1 &&
                 max_union >= 1 && max_union <= 65536 / 64 * 8, "sgp_split_plan_fill: bad size");
+    if (const char* f = rowptr_fault(rowptr, n_rows, nnz)) return sgp::fail(SGP_EINVAL, "sgp_split_plan_fill: malformed CSR: %s", f);
+    for (int64_t e = 0; e < rowptr[n_rows]; ++e)
+        SGP_REQUIRE(col[e] >= 0 && col[e] < n_cols, "sgp_split_plan_fill: column out of range");
     FillArgs a{rowptr, col, val, n_rows, n_cols, wave_of_row, slot_of_row, tile_of_wave, rows_of_wave, n_waves, n_tiles,
                waves, chunks, max_union, hdr, rowid, ucol, (uint16_t*)afr, adr, rinv};
     memset(hdr, 0, sizeof(int32_t) * 64 * n_tiles);
@@ -280,29 +308,39 @@ extern "C" int sgp_split_plan_fill(const int64_t* rowptr, const int64_t* col, co
 
     int nthr = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
     nthr = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(nthr, 64), n_tiles));
+    // every thread's scratch takes 8 bytes per column: at most 1 GiB of it in all
+    nthr = (int)std::max<int64_t>(1, std::min<int64_t>(nthr, (1ll << 30) / (8 * n_cols)));
     std::atomic<int64_t> next(0), keys(0), usum(0), umax(0);
-    std::atomic<int> bad(0);
+    std::atomic<int> bad(0);                               // 1: the deal breaks the kernel's limits, 2: out of memory
     auto work = [&]() {
-        Scratch s(a);
-        int64_t k_local = 0, u_local = 0, u_max = 0;
-        for (;;) {
-            const int64_t t = next.fetch_add(1);
-            if (t >= n_tiles || bad.load()) break;
-            int64_t U = 0;
-            const int64_t k = fill_tile(a, t, first_wave.data(), row_list.data(), row_first.data(), s, U);
-            if (k < 0) { bad.store(1); break; }
-            k_local += k; u_local += U; u_max = std::max(u_max, U);
-        }
-        keys += k_local; usum += u_local;
-        int64_t cur = umax.load();
-        while (u_max > cur && !umax.compare_exchange_weak(cur, u_max)) {}
+        try {
+            Scratch s(a);
+            int64_t k_local = 0, u_local = 0, u_max = 0;
+            for (;;) {
+                const int64_t t = next.fetch_add(1);
+                if (t >= n_tiles || bad.load()) break;
+                int64_t U = 0;
+                const int64_t k = fill_tile(a, t, first_wave.data(), row_list.data(), row_first.data(), s, U);
+                if (k < 0) { bad.store(1); break; }
+                k_local += k; u_local += U; u_max = std::max(u_max, U);
+            }
+            keys += k_local; usum += u_local;
+            int64_t cur = umax.load();
+            while (u_max > cur && !umax.compare_exchange_weak(cur, u_max)) {}
+        } catch (...) { bad.store(2); }                    // (a thread's exception must not leave the thread)
     };
     if (nthr == 1) work();
     else {
         std::vector<std::thread> pool;
-        for (int i = 0; i < nthr; ++i) pool.emplace_back(work);
+        pool.reserve(nthr);
+        try {
+            for (int i = 0; i < nthr; ++i) pool.emplace_back(work);
+        } catch (const std::system_error&) {               // no more threads to be had: the ones started do the work
+            if (pool.empty()) work();
+        }
         for (auto& th : pool) th.join();
     }
+    if (bad.load() == 2) return sgp::fail(SGP_ENOMEM, "sgp_split_plan_fill: out of host memory");
     if (bad.load()) return sgp::fail(SGP_EUNSUP, "sgp_split_plan_fill: the dealt rows break the kernel's limits");
     double norm_inf = 0.0;
     for (int64_t r = 0; r < n_rows; ++r) {
@@ -315,4 +353,34 @@ extern "C" int sgp_split_plan_fill(const int64_t* rowptr, const int64_t* col, co
     stats[3] = dealt / (double)n_tiles; stats[4] = (double)usum.load() / dealt;
     stats[5] = (double)keys.load() / ((double)n_waves * chunks * 32); stats[6] = (double)umax.load(); stats[7] = norm_inf;
     return 0;
+  });
+}
+
+extern "C" int64_t sgp_split_plan_bands(const int32_t* ucol, int64_t n_tiles, int32_t max_union, int64_t n_cols,
+                                        int64_t col_budget, int32_t* band_first) {
+  return guarded<int64_t>("sgp_split_plan_bands", [&]() -> int64_t {
+    if (!ucol || !band_first || n_tiles < 1 || n_tiles >= (1ll << 31) || max_union < 1 || n_cols < 1 || col_budget < 1)
+        return sgp::fail(SGP_EINVAL, "sgp_split_plan_bands: bad argument");
+    // the deal's bookkeeping one level up: mark[c] = band that last staged column c
+    std::vector<int64_t> mark(n_cols, -1);
+    int64_t band = 0, b_cols = 0;
+    band_first[0] = 0;
+    for (int64_t t = 0; t < n_tiles; ++t) {
+        const int32_t* u = ucol + t * max_union;
+        int64_t fresh = 0, U = 0;
+        for (; U < max_union && u[U] >= 0; ++U) {
+            if (u[U] >= n_cols) return sgp::fail(SGP_EINVAL, "sgp_split_plan_bands: column out of range");
+            fresh += mark[u[U]] != band;
+        }
+        if (t > band_first[band] && b_cols + fresh > col_budget) {      // (a tile beyond the budget on its own: a band of one)
+            band_first[++band] = (int32_t)t;
+            b_cols = 0;
+            fresh = U;
+        }
+        for (int64_t i = 0; i < U; ++i) mark[u[i]] = band;
+        b_cols += fresh;
+    }
+    band_first[band + 1] = (int32_t)n_tiles;
+    return band + 1;
+  });
 }

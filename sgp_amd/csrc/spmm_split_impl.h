@@ -133,6 +133,9 @@ struct SplitArgs {
     const int* hdr; const int* rowid; const int* ucol; const h8* afr; const int* adr; const float* rinv;
     int n_tiles, tiles_per_xcd;
     int time_major;                          // 1: an XCD walks ITS time chunks (chunk % 8 == xcd) over ALL tiles -- a step's whole slab stays in its L2
+                                             // 2: the same band by band (operators whose slab exceeds an L2): bands / n_bands / chunks_per_xcd
+    const int* bands; int n_bands;           // bands[n_bands + 1]: first tile of every band of consecutive tiles, then n_tiles
+    int chunks_per_xcd;                      // ceil(time chunks / 8): workgroups a band spends per tile and XCD
     const float* X; long long xrs, xbs;
     const float* XH; long long xhrs, xhbs;   // halo source (columns >= n_own): local block of a node partition
     int n_own;
@@ -253,9 +256,23 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void spmm_split(SplitArgs a) {
     // small operators (the source rows of one step fit an L2): time-major -- every tile of a time chunk runs on the SAME
     // XCD side by side, so a staged row is fetched from the fabric once per step instead of once per XCD that holds a
     // tile referencing it
-    const int tile = a.time_major ? j % a.n_tiles : xcd * a.tiles_per_xcd + j % a.tiles_per_xcd;
-    const int tchunk = a.time_major ? (j / a.n_tiles) * 8 + xcd : j / a.tiles_per_xcd;
-    if (tile >= a.n_tiles) return;
+    int tile = a.time_major ? j % a.n_tiles : xcd * a.tiles_per_xcd + j % a.tiles_per_xcd;
+    int tchunk = a.time_major ? (j / a.n_tiles) * 8 + xcd : j / a.tiles_per_xcd;
+    if (a.time_major == 2) {
+        // banded time-major (large operators): the tile list is cut into bands whose staged rows of one step fit an L2;
+        // band b owns the workgroups bands[b] * chunks_per_xcd <= j < bands[b + 1] * chunks_per_xcd of every XCD and
+        // walks them time-major over its own tiles -- bands follow each other in workgroup order, nothing waits
+        int lo = 0, hi = a.n_bands;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (a.bands[mid] * a.chunks_per_xcd <= j) lo = mid; else hi = mid;
+        }
+        const int t0 = a.bands[lo], nt = a.bands[lo + 1] - t0, jj = j - t0 * a.chunks_per_xcd;
+        if (nt <= 0 || jj < 0) return;
+        tile = t0 + jj % nt;
+        tchunk = (jj / nt) * 8 + xcd;
+    }
+    if (tile < 0 || tile >= a.n_tiles) return;
     const int t_begin = tchunk * a.t_chunk;
     const int t_end = min(a.batch, t_begin + a.t_chunk);
     if (t_begin >= t_end) return;
@@ -561,17 +578,23 @@ extern "C" int32_t SGP_SPLIT_NAME(waves)(void) { return NW; }
 extern "C" int32_t SGP_SPLIT_NAME(rows_per_wave)(void) { return 16; }
 extern "C" int32_t SGP_SPLIT_NAME(max_feat)(void) { return MAXFEAT; }
 
-extern "C" int SGP_SPLIT_NAME(f32)(const int32_t* hdr, const int32_t* rowid, const int32_t* ucol, const void* afr,
-                                  const int32_t* adr, const float* rinv,
-                                  int32_t n_tiles,
-                                  const float* X, int64_t x_row_stride, int64_t x_batch_stride,
-                                  const float* X_halo, int64_t xh_row_stride, int64_t xh_batch_stride, int32_t n_own,
-                                  float* Y, int64_t y_row_stride, int64_t y_batch_stride,
-                                  int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
-                                  const float* x_tab, int32_t accumulate, int32_t t_chunk, const int32_t* pred, int32_t run_if, sgp_stream_t stream) {
+namespace {
+int launch_split(const int32_t* hdr, const int32_t* rowid, const int32_t* ucol, const void* afr,
+                 const int32_t* adr, const float* rinv,
+                 int32_t n_tiles,
+                 const float* X, int64_t x_row_stride, int64_t x_batch_stride,
+                 const float* X_halo, int64_t xh_row_stride, int64_t xh_batch_stride, int32_t n_own,
+                 float* Y, int64_t y_row_stride, int64_t y_batch_stride,
+                 int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
+                 const float* x_tab, int32_t accumulate, int32_t t_chunk,
+                 int32_t walk, const int32_t* band_first, int32_t n_bands,
+                 const int32_t* pred, int32_t run_if, sgp_stream_t stream) {
     const sgp::Predicate pr{pred, run_if};
     SGP_REQUIRE(n_tiles >= 0 && batch >= 0 && n_rows >= 0 && n_cols >= 0, "spmm_split: negative size");
     if (n_tiles == 0 || batch == 0 || n_rows == 0) return 0;
+    SGP_REQUIRE(walk >= 0 && walk <= 3, "spmm_split: walk = %d (0 chosen here, 1 tile-major, 2 time-major, 3 banded)", walk);
+    SGP_REQUIRE(walk != 3 || (band_first != nullptr && n_bands >= 1 && n_bands <= n_tiles),
+                "spmm_split: band table of %d bands for %d tiles", n_bands, n_tiles);
     SGP_REQUIRE(hdr && rowid && ucol && afr && adr && rinv && X && Y && x_tab, "spmm_split: null pointer");
     SGP_REQUIRE(feat > 0 && feat % 16 == 0 && feat <= MAXFEAT, "spmm_split: feat = %d is not a multiple of 16 up to %d", feat, MAXFEAT);
     SGP_REQUIRE(sgp::aligned16(X) && x_row_stride % 4 == 0 && x_batch_stride % 4 == 0 &&
@@ -616,9 +639,16 @@ extern "C" int SGP_SPLIT_NAME(f32)(const int32_t* hdr, const int32_t* rowid, con
     static const long tm_tune = sgp::tune("split_time_major", -1);
     static const long tm_tc = sgp::tune("split_tc", 0);
     a.time_major = tm_tune >= 0 ? (int)(tm_tune != 0) : (int)((long long)n_cols * feat * 4 <= (4ll << 20) && n_tiles >= 8);
+    a.bands = nullptr; a.n_bands = 0; a.chunks_per_xcd = 0;
+    if (walk != 0) a.time_major = walk - 1;        // the caller's choice (sgp_amd/graph.py: banded for operators beyond the rule above)
+    if (walk == 3) { a.bands = band_first; a.n_bands = n_bands; }
     if (a.time_major) {
         if (tm_tc > 0 && auto_tc) t_chunk = (int)tm_tc;
-        else if (auto_tc && n_tiles <= 32 && t_chunk > 16) t_chunk = 16;       // (few tiles: short chunks keep an XCD's tiles on the same steps)
+        else if (auto_tc && a.time_major == 1 && n_tiles <= 32 && t_chunk > 16) t_chunk = 16;       // (few tiles: short chunks keep an XCD's tiles on the same steps)
+        // bands: 32 steps, whatever their size.  Measured on the target line (profiles/banded/README.md, ms per hop at 16 |
+        // 32 | 64 steps): 2 MB bands of <= 31 tiles 17.19 | 16.75 | 17.09, 4 MB bands 17.16 | 16.69 | 17.00 -- at 16 steps
+        // the plan load of four times as many workgroups costs what the L2 hits return, at 64 the tiles of a band drift apart
+        else if (auto_tc && a.time_major == 2 && t_chunk > 32) t_chunk = 32;
     }
     a.t_chunk = t_chunk;
 #ifdef SGP_ABLATION
@@ -630,6 +660,8 @@ extern "C" int SGP_SPLIT_NAME(f32)(const int32_t* hdr, const int32_t* rowid, con
     a.dbg = nullptr;
     if (abl & 256) { if (hipMalloc(&a.dbg, 8 * NW * 8 * 8) != hipSuccess) return sgp::fail(SGP_EINVAL, "dbg alloc"); (void)hipMemset(a.dbg, 0, 8 * NW * 8 * 8); }
     const int n_tchunks = (batch + t_chunk - 1) / t_chunk;
+    a.chunks_per_xcd = (n_tchunks + 7) / 8;
+    SGP_REQUIRE(8ll * n_tiles * a.chunks_per_xcd < (1ll << 31), "spmm_split: %d tiles x %d time chunks beyond one launch", n_tiles, n_tchunks);
     auto kern = X_halo ? (accumulate ? spmm_split<true, true> : spmm_split<true, false>)
                        : (accumulate ? spmm_split<false, true> : spmm_split<false, false>);
     const int lds_bytes = NBUF * BUF + 2 * feat * 4;
@@ -652,4 +684,33 @@ extern "C" int SGP_SPLIT_NAME(f32)(const int32_t* hdr, const int32_t* rowid, con
         }
     }
     return sgp::check_launch("spmm_split");
+}
+}  // namespace
+
+extern "C" int SGP_SPLIT_NAME(f32)(const int32_t* hdr, const int32_t* rowid, const int32_t* ucol, const void* afr,
+                                  const int32_t* adr, const float* rinv,
+                                  int32_t n_tiles,
+                                  const float* X, int64_t x_row_stride, int64_t x_batch_stride,
+                                  const float* X_halo, int64_t xh_row_stride, int64_t xh_batch_stride, int32_t n_own,
+                                  float* Y, int64_t y_row_stride, int64_t y_batch_stride,
+                                  int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
+                                  const float* x_tab, int32_t accumulate, int32_t t_chunk, const int32_t* pred, int32_t run_if, sgp_stream_t stream) {
+    return launch_split(hdr, rowid, ucol, afr, adr, rinv, n_tiles, X, x_row_stride, x_batch_stride, X_halo, xh_row_stride,
+                        xh_batch_stride, n_own, Y, y_row_stride, y_batch_stride, n_rows, n_cols, batch, feat, x_tab, accumulate,
+                        t_chunk, 0, nullptr, 0, pred, run_if, stream);
+}
+
+extern "C" int SGP_SPLIT_NAME(banded_f32)(const int32_t* hdr, const int32_t* rowid, const int32_t* ucol, const void* afr,
+                                         const int32_t* adr, const float* rinv,
+                                         int32_t n_tiles,
+                                         const float* X, int64_t x_row_stride, int64_t x_batch_stride,
+                                         const float* X_halo, int64_t xh_row_stride, int64_t xh_batch_stride, int32_t n_own,
+                                         float* Y, int64_t y_row_stride, int64_t y_batch_stride,
+                                         int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
+                                         const float* x_tab, int32_t accumulate, int32_t t_chunk,
+                                         int32_t walk, const int32_t* band_first, int32_t n_bands,
+                                         const int32_t* pred, int32_t run_if, sgp_stream_t stream) {
+    return launch_split(hdr, rowid, ucol, afr, adr, rinv, n_tiles, X, x_row_stride, x_batch_stride, X_halo, xh_row_stride,
+                        xh_batch_stride, n_own, Y, y_row_stride, y_batch_stride, n_rows, n_cols, batch, feat, x_tab, accumulate,
+                        t_chunk, walk, band_first, n_bands, pred, run_if, stream);
 }

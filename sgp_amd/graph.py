@@ -78,7 +78,8 @@ def _operands(x, y, halo, x_bound):
 
 class _Choice(NamedTuple):
     """What ``ShiftOperator._select`` chose.  ``kernel`` / ``plan``: the exact-fp32 kernel (a key of ``_LAUNCH``) and
-    its plan; with a ``split`` plan the exact kernel runs behind the split-fp16 hop's predicate.  ``lazy``: that exact
+    its plan; with a ``split`` plan the exact kernel runs behind the split-fp16 hop's predicate (``walk``: how that hop
+    maps workgroups to tiles and time chunks, ``hip.spmm_split``).  ``lazy``: that exact
     kernel is the generic CSR kernel, standing in until an admission flag asks for the planned ones.  ``tile``: the
     tile plan looked up on the way.  ``error``: what the ``force`` value has to raise."""
     kernel: str = None
@@ -87,6 +88,35 @@ class _Choice(NamedTuple):
     lazy: bool = False
     tile: object = None
     error: Exception = None
+    walk: object = None     # split hop: None (the library's rule) or the column budget of the banded time-major walk
+
+
+# Split hop, operators whose source rows of one step exceed an L2 (the library's whole-operator time-major rule,
+# csrc/spmm_split_impl.h): the banded time-major walk.  SGP_TUNE=split_banded=off|on|<bytes>: ``on`` bands those operators
+# with the default budget, a byte count bands EVERY operator that has a split plan with that budget (tests, A/B runs).
+SPLIT_TIME_MAJOR_BYTES = 4 << 20      # a step's slab up to here: whole-operator time-major (library)
+SPLIT_BAND_BYTES = 4 << 20            # default band budget: a step's distinct staged rows of one band (measured: profiles/banded)
+SPLIT_BANDED_DEFAULT = "on"
+
+
+def split_band_cols(n_cols, feat, n_tiles):
+    """Column budget of the banded walk for a split plan of ``n_tiles`` tiles over ``n_cols`` source rows of ``feat``
+    floats, or None where the library's own rule (whole-operator time-major / tile-major) stays."""
+    mode = tune.get("split_banded", SPLIT_BANDED_DEFAULT)
+    if mode == "off" or feat <= 0:
+        return None
+    if mode == "on":
+        if n_cols * feat * 4 <= SPLIT_TIME_MAJOR_BYTES and n_tiles >= 8:
+            return None
+        budget = SPLIT_BAND_BYTES
+    else:
+        try:
+            budget = int(mode)
+        except ValueError:
+            raise ValueError(f"SGP_TUNE: split_banded={mode!r} is not off, on or a byte count") from None
+        if budget <= 0:
+            return None
+    return max(1, budget // (feat * 4))
 
 
 # exact kernel name (``last_kernel``, ``last_exact_kernel``) -> its binding; the CSR kernel's plan is the device CSR
@@ -340,13 +370,16 @@ class ShiftOperator:
         for it -- half the passes, less than half the staged rows per result row."""
         from . import splitplan
         args = (self.rowptr.numpy(), self.col.numpy(), self.val.numpy(), self.num_nodes, self.num_cols)
-        plan = splitplan.build_split_plan(*args, **lim)
+        # the band table of the default budget at 64 features is cut with the plan (and cached with it); other widths and
+        # budgets get theirs on first use (SplitPlan.band_table)
+        bands = dict(band_cols=SPLIT_BAND_BYTES // 256)
+        plan = splitplan.build_split_plan(*args, **lim, **bands)
         # numberings without locality (16 consecutive rows share no columns): deal the rows in a
         # locality order of the graph itself, as the tile plans do
         if plan is not None and plan.stats["rows_per_wave"] < 0.75 * lim["rows_per_wave"] and self.num_nodes >= 2048 and \
                 self.num_cols == self.num_nodes:
             alt = splitplan.build_split_plan(*args, order=locality_order(
-                self.rowptr.numpy(), self.col.numpy(), self.num_nodes), **lim)
+                self.rowptr.numpy(), self.col.numpy(), self.num_nodes), **lim, **bands)
             if alt is not None and alt.stats["staged_per_row"] < plan.stats["staged_per_row"]:
                 plan = alt
         # a plan that stages many rows per result row (no locality at all) loses to the other kernels
@@ -361,7 +394,7 @@ class ShiftOperator:
             deg = (self.rowptr[1:] - self.rowptr[:-1])
             if wide is not None and float((deg > 32 * lim["chunks"]).float().mean()) < 0.5:
                 wide = None
-            passes = splitplan.build_split_passes(*args, max_passes=12, **(wide or lim))
+            passes = splitplan.build_split_passes(*args, max_passes=12, **(wide or lim), **bands)
             if passes is not None and passes[0].stats["rows_per_wave"] >= 0.5 * lim["rows_per_wave"] and \
                     passes[0].stats["staged_per_row"] <= 8:
                 plan = list(passes)
@@ -434,11 +467,11 @@ class ShiftOperator:
         if c.split is not None:
             if force == "split":
                 prof = hip.spmm_split(c.split, x, y, hip.split_profile(x, halo, x_bound, self.norm_inf(), guard=False),
-                                      halo=halo, n_own=self.num_nodes)
+                                      halo=halo, n_own=self.num_nodes, walk=c.walk)
                 self.last_kernel, self.next_bound = "spmm_split", prof.bound_out
                 return y
             prof = hip.split_profile(x, halo, x_bound, self.norm_inf(), guard=tune.get("split_guard", 1, int) != 0)
-            hip.spmm_split(c.split, x, y, prof, halo=halo, n_own=self.num_nodes, predicated=True)
+            hip.spmm_split(c.split, x, y, prof, halo=halo, n_own=self.num_nodes, predicated=True, walk=c.walk)
             self.next_bound, pred = prof.bound_out, (prof.flag, 0)
         _LAUNCH[c.kernel](c.plan, x, y, halo, self.num_nodes, pred=pred)
         if pred is None:
@@ -468,13 +501,23 @@ class ShiftOperator:
             if split is None:
                 return _Choice(error=NotImplementedError(
                     "no split-fp16 plan for this operator / feature width / halo / operand"))
-            return _Choice(split=split)
+            return _Choice(split=split, walk=split_band_cols(self.num_cols, feat, split.n_tiles))
         split = None
         if force is None and not nonfinite and tune.get("hop", "split") == "split" and ops.split_layout and split_width \
                 and self.nnz() >= 8 * self.num_nodes and self.num_nodes >= 2048:
             split = self.split_plan(device)
+        walk = None
+        if split is not None:
+            walk = split_band_cols(self.num_cols, feat, split.n_tiles)
+            if walk is not None:                          # (cut here, i.e. in ``prepare``, not in the first hop)
+                for p in (split if isinstance(split, list) else [split]):
+                    p.band_table(walk)
         if split_only:
-            return _Choice(split=split)
+            return _Choice(split=split, walk=walk)
+        return self._select_exact(feat, device, ops, force, split)._replace(walk=walk)
+
+    def _select_exact(self, feat, device, ops, force, split):
+        """``_select`` behind the split hop's decision: the exact-fp32 kernel (alone, or behind ``split``'s predicate)."""
         # where the split-fp16 hop is the default, the exact kernels sit behind a predicate that admits them on no shipped
         # configuration: their plans -- 16 s of host work on the target graph -- are built the first time a flag shows
         # they ran; until then the generic CSR kernel (exact fp32, no plan) stands in

@@ -148,9 +148,18 @@ SIGNATURES = {
     "sgp_spmm_split_waves": (c_i32, []),
     "sgp_spmm_split_rows_per_wave": (c_i32, []),
     "sgp_spmm_split_max_feat": (c_i32, []),
-    "sgp_split_plan_deal": (c_i64, [c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p]),
-    "sgp_split_plan_fill": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64,
+    "sgp_split_plan_deal": (c_i64, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p]),
+    "sgp_split_plan_fill": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64,
                                            c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32]),
+    "sgp_split_plan_bands": (c_i64, [c_p, c_i64, c_i32, c_i64, c_i64, c_p]),
+    "sgp_spmm_split_banded_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_p, c_i64, c_i64,
+                                                 c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_i64,
+                                                 c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_i32, c_p, c_i32,
+                                                 c_p, c_i32, c_p]),
+    "sgp_spmm_split_wide_banded_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_p, c_i64, c_i64,
+                                                      c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_i64,
+                                                      c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_i32, c_p, c_i32,
+                                                      c_p, c_i32, c_p]),
     "sgp_spmm_colblock_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_p, c_i64, c_i64,
                                              c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_i64,
                                              c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_p]),
@@ -545,12 +554,18 @@ def split_profile(x, halo=None, bound=None, norm_inf=1.0, guard=True):
     return SplitProfile(tab, flag, ColumnBound(bound_out))
 
 
+_SPLIT_WALKS = {None: 0, "tile": 1, "time": 2}
+
+
 @_on_device
-def spmm_split(plan, x, y, profile, t_chunk=0, halo=None, n_own=None, predicated=False):
+def spmm_split(plan, x, y, profile, t_chunk=0, halo=None, n_own=None, predicated=False, walk=None):
     """Split-fp16 hop (plan: sgp_amd.splitplan.SplitPlan on the device of ``x``; ``profile``: the ``SplitProfile``
     of this operand, or a float bound on |x| / None for which one is made here without the admission test --
     callers that force the kernel).  ``predicated``: launch under ``profile.flag == 1`` (the caller enqueues the
-    exact kernel under ``== 0`` behind it)."""
+    exact kernel under ``== 0`` behind it).  ``walk``: which workgroup takes which (tile, time chunk) -- None: the
+    library's rule (time-major where a step's source rows fit an L2, else tile-major), ``"tile"``, ``"time"``, or an int:
+    banded time-major with bands of at most that many distinct staged rows (``SplitPlan.band_table``).  Every walk gives
+    the same bits."""
     lib = require_gpu()
     ops, _ = _hop_operands(x, y, halo, n_own)
     if not isinstance(profile, SplitProfile):
@@ -559,13 +574,18 @@ def spmm_split(plan, x, y, profile, t_chunk=0, halo=None, n_own=None, predicated
     pr = _pred((profile.flag, 1) if predicated else None)
     for p in plans:                                   # (several passes: an operator whose long rows were cut into column segments)
         # the plan's geometry names its kernel: 16 waves x 7 chunks (standard) or 8 x 14 (wide: long rows)
-        entry = lib.sgp_spmm_split_wide_f32 if p.afr.shape[1] == lib.sgp_spmm_split_wide_waves() and \
-            p.afr.shape[2] == lib.sgp_spmm_split_wide_chunks() else lib.sgp_spmm_split_f32
+        entry = lib.sgp_spmm_split_wide_banded_f32 if p.afr.shape[1] == lib.sgp_spmm_split_wide_waves() and \
+            p.afr.shape[2] == lib.sgp_spmm_split_wide_chunks() else lib.sgp_spmm_split_banded_f32
+        if walk is None or isinstance(walk, str):
+            how = (_SPLIT_WALKS[walk], None, 0)
+        else:
+            first, _ = p.band_table(walk)
+            how = (3, first.data_ptr(), first.numel() - 1)
         _check(entry(
             p.hdr.data_ptr(), p.rowid.data_ptr(), p.ucol.data_ptr(), p.afr.data_ptr(), p.adr.data_ptr(),
             p.rinv.data_ptr(), p.n_tiles,
             *ops, p.n_rows, p.n_cols, x.shape[0], x.shape[2],
-            profile.tab.data_ptr(), int(p.accumulate), t_chunk, *pr, _stream(x)), "sgp_spmm_split_f32")
+            profile.tab.data_ptr(), int(p.accumulate), t_chunk, *how, *pr, _stream(x)), "sgp_spmm_split_f32")
     return profile
 
 

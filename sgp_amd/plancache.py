@@ -9,7 +9,7 @@ import tempfile
 
 import torch
 
-VERSION = 7          # bump when a plan format or a planner's output changes
+VERSION = 8          # (8: split plans carry their band tables) bump when a plan format or a planner's output changes
 _dir = None
 stats = {"hits": 0, "misses": 0, "stores": 0}
 

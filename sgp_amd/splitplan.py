@@ -20,6 +20,10 @@ columns, waves to TILES of at most ``waves`` waves whose rows touch at most ``ma
                            fetch a chunk's B operand, packed ``a0 | a1 << 16``: read j of lane ``i + 16 g`` points at the
                            staged row of column ``k = 8 g + 4 j + i / 4``, bytes ``8 (i % 4)``
 
+Large operators also get a BAND TABLE (``SplitPlan.band_table``, native ``sgp_split_plan_bands``): the tile list -- already in
+locality order -- cut into bands of consecutive tiles whose distinct staged rows stay under a column budget, for the
+banded time-major walk of ``sgp_spmm_split_banded_f32``.
+
 Columns a wave does not use up to ``32 * chunks`` are padded with weight 0 and the address of staged row 0
 (finite data, so 0 * x stays 0).  Duplicate entries of a row are summed before the split.
 """
@@ -33,13 +37,48 @@ class SplitPlan:
         self.n_tiles, self.n_rows, self.n_cols = n_tiles, n_rows, n_cols
         self.norm_inf, self.stats = norm_inf, stats
         self.accumulate = False          # later passes of an operator whose long rows were cut into column segments
+        self.bands = {}                  # column budget -> (band_first int32 [n_bands + 1] beside the plan's arrays, largest band)
+        self.ucol_host = ucol if ucol.device.type == "cpu" else None     # what further band tables are cut from
+
+    def __setstate__(self, state):       # (plans pickled before the band table existed)
+        self.__dict__.update(state)
+        self.__dict__.setdefault("bands", {})
+        self.__dict__.setdefault("ucol_host", self.ucol if self.ucol.device.type == "cpu" else None)
 
     def to(self, device):
         p = SplitPlan(self.hdr.to(device), self.rowid.to(device), self.ucol.to(device), self.afr.to(device),
                       self.adr.to(device), self.rinv.to(device), self.n_tiles, self.n_rows, self.n_cols, self.norm_inf,
                       self.stats)
         p.accumulate = self.accumulate
+        p.bands = {k: (t.to(device), m) for k, (t, m) in self.bands.items()}
+        p.ucol_host = self.ucol_host
         return p
+
+    def band_table(self, col_budget):
+        """``(band_first, largest band)`` for bands of at most ``col_budget`` distinct staged rows: ``band_first`` (int32,
+        on the plan's device) holds the first tile of every band and then ``n_tiles``.  Cut once per budget."""
+        col_budget = int(col_budget)
+        if col_budget not in self.bands:
+            host = self.ucol_host if self.ucol_host is not None else self.ucol.cpu()
+            first = build_bands(host, self.n_cols, col_budget)
+            self.bands[col_budget] = (first.to(self.ucol.device), int((first[1:] - first[:-1]).max()))
+        return self.bands[col_budget]
+
+
+def build_bands(ucol, n_cols, col_budget):
+    """Band boundaries of a plan's tile list (``ucol[n_tiles, max_union]``, host): consecutive tiles join a band until the
+    next one would take the band's distinct staged rows over ``col_budget``; a tile beyond the budget on its own is a band
+    of one.  Returns int32 ``[n_bands + 1]``: first tile of every band, then ``n_tiles`` (native: ``sgp_split_plan_bands``)."""
+    from . import hip
+    lib = hip.load()
+    ucol = ucol.contiguous()
+    assert ucol.dtype == torch.int32 and ucol.dim() == 2 and ucol.device.type == "cpu"
+    n_tiles = ucol.shape[0]
+    first = torch.empty(n_tiles + 1, dtype=torch.int32)
+    n = lib.sgp_split_plan_bands(ucol.data_ptr(), n_tiles, ucol.shape[1], int(n_cols), int(col_budget), first.data_ptr())
+    if n < 0:
+        raise (MemoryError if n == -3 else RuntimeError)("sgp_split_plan_bands: " + lib.sgp_last_error().decode())
+    return first[:n + 1].clone()
 
 
 def deal_rows(rowptr, col, n_rows, n_cols, waves, chunks, max_union, rows_per_wave=32, order=None):
@@ -143,7 +182,7 @@ def _bank_aware_slots(w_of_key, pos_of_key, stage, n_chunks_total, chunks):
 
 
 def build_split_plan(rowptr, col, val, n_rows, n_cols, waves=16, chunks=7, max_union=768, order=None, rows_per_wave=16,
-                     threads=0):
+                     threads=0, band_cols=None):
     """``order``: optional sequence of rows (a locality order of the graph, or the subset of rows a later pass of a
     long-row operator touches): rows are dealt to waves in that sequence -- rows outside it get no slot -- while the plan
     keeps addressing rows and columns by their ORIGINAL ids, so no tensor is ever permuted.
@@ -151,7 +190,8 @@ def build_split_plan(rowptr, col, val, n_rows, n_cols, waves=16, chunks=7, max_u
     The work is done by the library's host-side planner (``csrc/plan_split.hip``: ``sgp_split_plan_deal`` /
     ``sgp_split_plan_fill``, all cores; no GPU needed); ``build_split_plan_numpy`` below is the same algorithm in numpy,
     kept as its cross-check (tests/test_splitplan.py holds the two to the same bytes) -- 2 s instead of 23 s on the
-    target graph."""
+    target graph.  ``band_cols``: column budget of a band table cut along with the plan (``SplitPlan.band_table`` cuts
+    others on demand)."""
     import ctypes
     from . import hip
     lib = hip.load()
@@ -160,20 +200,20 @@ def build_split_plan(rowptr, col, val, n_rows, n_cols, waves=16, chunks=7, max_u
     val = np.ascontiguousarray(val, dtype=np.float32)
     if n_rows == 0 or col.size == 0 or not np.isfinite(val).all():
         return None
-    assert rows_per_wave == 16 and rowptr.size >= n_rows + 1
+    assert rows_per_wave == 16 and rowptr.size >= n_rows + 1 and val.size == col.size
     if col.min() < 0 or col.max() >= n_cols:
         raise ValueError("column index out of range")
     seq = None if order is None else np.ascontiguousarray(order, dtype=np.int64)
     ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
     wave_of_row, slot_of_row = np.empty(n_rows, dtype=np.int64), np.empty(n_rows, dtype=np.int64)
     tile_of_wave, rows = np.empty(n_rows, dtype=np.int64), np.empty(n_rows, dtype=np.int64)
-    n_waves = lib.sgp_split_plan_deal(ptr(rowptr), ptr(col), n_rows, n_cols, None if seq is None else ptr(seq),
+    n_waves = lib.sgp_split_plan_deal(ptr(rowptr), ptr(col), col.size, n_rows, n_cols, None if seq is None else ptr(seq),
                                       0 if seq is None else seq.size, waves, chunks, max_union, rows_per_wave,
                                       ptr(wave_of_row), ptr(slot_of_row), ptr(tile_of_wave), ptr(rows))
     if n_waves == -2 or n_waves == 0:
         return None                                   # a row beyond a wave's column budget / nothing dealt
     if n_waves < 0:
-        raise RuntimeError("sgp_split_plan_deal: " + lib.sgp_last_error().decode())
+        raise (MemoryError if n_waves == -3 else RuntimeError)("sgp_split_plan_deal: " + lib.sgp_last_error().decode())
     tile_of_wave, rows = tile_of_wave[:n_waves], rows[:n_waves]
     n_tiles = int(tile_of_wave[-1]) + 1
     hdr = torch.empty((n_tiles, 64), dtype=torch.int32)
@@ -183,13 +223,16 @@ def build_split_plan(rowptr, col, val, n_rows, n_cols, waves=16, chunks=7, max_u
     adr = torch.empty((n_tiles, waves, chunks, 64), dtype=torch.int32)
     rinv = torch.empty((n_tiles, waves, 16), dtype=torch.float32)
     st = np.zeros(8, dtype=np.float64)
-    hip._check(lib.sgp_split_plan_fill(ptr(rowptr), ptr(col), ptr(val), n_rows, n_cols, ptr(wave_of_row), ptr(slot_of_row),
+    hip._check(lib.sgp_split_plan_fill(ptr(rowptr), ptr(col), ptr(val), col.size, n_rows, n_cols, ptr(wave_of_row), ptr(slot_of_row),
                                        ptr(tile_of_wave), ptr(rows), n_waves, n_tiles, waves, chunks, max_union,
                                        hdr.data_ptr(), rowid.data_ptr(), ucol.data_ptr(), afr.data_ptr(), adr.data_ptr(),
                                        rinv.data_ptr(), ptr(st), int(threads)), "sgp_split_plan_fill")
     stats = dict(tiles=n_tiles, waves=int(n_waves), rows_per_wave=float(st[2]), rows_per_tile=float(st[3]),
                  staged_per_row=float(st[4]), chunk_fill=float(st[5]), max_union=int(st[6]))
-    return SplitPlan(hdr, rowid, ucol, afr, adr, rinv, n_tiles, n_rows, n_cols, float(st[7]), stats)
+    plan = SplitPlan(hdr, rowid, ucol, afr, adr, rinv, n_tiles, n_rows, n_cols, float(st[7]), stats)
+    if band_cols:
+        plan.band_table(band_cols)
+    return plan
 
 
 def build_split_plan_numpy(rowptr, col, val, n_rows, n_cols, waves=16, chunks=7, max_union=768, order=None, rows_per_wave=16):
@@ -297,7 +340,7 @@ def build_split_plan_numpy(rowptr, col, val, n_rows, n_cols, waves=16, chunks=7,
 
 
 def build_split_passes(rowptr, col, val, n_rows, n_cols, waves=16, chunks=7, max_union=768, order=None,
-                       rows_per_wave=16, segment=None, max_passes=12):
+                       rows_per_wave=16, segment=None, max_passes=12, band_cols=None):
     """Plans for an operator with rows LONGER than a wave's column budget (the reference's full PV-US / CER-En graphs:
     ~740 / ~495 entries per row, config/largescale/sgp_pv.yaml + experiments/run_largescale_sgp.py:167-170): every
     group of ``rows_per_wave`` consecutive rows has its sorted column union cut into segments of one wave's column
@@ -307,7 +350,7 @@ def build_split_passes(rowptr, col, val, n_rows, n_cols, waves=16, chunks=7, max
     rowptr = np.asarray(rowptr, dtype=np.int64)
     col = np.asarray(col, dtype=np.int64)
     val = np.asarray(val, dtype=np.float32)
-    lim = dict(waves=waves, chunks=chunks, max_union=max_union, rows_per_wave=rows_per_wave)
+    lim = dict(waves=waves, chunks=chunks, max_union=max_union, rows_per_wave=rows_per_wave, band_cols=band_cols)
     one = build_split_plan(rowptr, col, val, n_rows, n_cols, order=order, **lim)
     if one is not None:
         return [one]

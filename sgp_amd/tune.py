@@ -11,6 +11,9 @@ Python layer
     split_guard=1|0, split_passes=1|0   admission statistics of the split-fp16 hop; long-row operators in passes
     time_parallel=1|0, time_parallel_warm=<steps>, time_parallel_tol=1e-6   small graphs, contractive reservoirs: time pieces computed side by side from a
                             warm-up, accepted by a device-side comparison at every splice (0: one sequential chain)
+    split_banded=on|off|<bytes>   split-fp16 hop, banded time-major walk: ``on`` (default) for operators whose source rows of
+                            one step exceed an L2 (band budget: graph.SPLIT_BAND_BYTES), a byte count = that band budget for EVERY
+                            operator with a split plan (tests, A/B runs); off: the library's rule alone (split_time_major below)
     mix_thr=4               a column goes through the dense 16x16x4 part when >= thr of a block's 4 groups use it
     mix_min_share=0.25      least share of (group, column) pairs in the dense part for the mixed kernel to be chosen
     colblock=1|0            column-blocked hop for graphs without locality (0: generic CSR kernel)

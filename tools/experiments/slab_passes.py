@@ -36,7 +36,7 @@ def _fill_plan(rowptr, col, val, n_rows, n_cols, wave_of_row, slot_of_row, tile_
     adr = torch.empty((n_tiles, waves, chunks, 64), dtype=torch.int32)
     rinv = torch.empty((n_tiles, waves, 16), dtype=torch.float32)
     st = np.zeros(8, dtype=np.float64)
-    hip._check(lib.sgp_split_plan_fill(ptr(rowptr), ptr(col), ptr(val), n_rows, n_cols, ptr(wave_of_row), ptr(slot_of_row),
+    hip._check(lib.sgp_split_plan_fill(ptr(rowptr), ptr(col), ptr(val), col.size, n_rows, n_cols, ptr(wave_of_row), ptr(slot_of_row),
                                        ptr(tile_of_wave), ptr(rows), n_waves, n_tiles, waves, chunks, max_union,
                                        hdr.data_ptr(), rowid.data_ptr(), ucol.data_ptr(), afr.data_ptr(), adr.data_ptr(),
                                        rinv.data_ptr(), ptr(st), int(threads)), "sgp_split_plan_fill")
