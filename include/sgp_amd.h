@@ -850,6 +850,62 @@ int sgp_rnn_window_bwd_f32(int32_t cell, int32_t H, int32_t S, int64_t M, float*
                            const float* h_seq, const float* c_seq, const float* dy, int32_t dy_full,
                            sgp_stream_t stream);
 
+/* ------------------------------------------------ DCRNN baseline: diffusion convolution and its GRU cell -----
+ * dcrnn.hip.  EXACT-FP32 contract as above: v_mfma_f32_16x16x4_f32 in the matrix kernels, plain FMAs in CSR order in
+ * the hop; no float atomics, bit-identical from run to run; no persistent kernel and no barrier between workgroups (a
+ * hop that needs its neighbours' previous hop is the next launch in stream order).
+ * The filters' input cat([x | h], A_f [x | h], .., A_b^k [x | h]) is kept as two "concat buffers" of 2 k + 1 slots:
+ * the x side [S R, (2 k + 1) Fin] for all steps at once, whose product with the stacked x columns of the three
+ * filters (one sgp_dense_f32 launch, biases folded in) is G [S R, 3 H] = (r | u | c); and the h side [R, (2 k + 1) H]
+ * per step.  Slot 0 is the value itself, slots 1 .. k its A_f powers, k + 1 .. 2 k its A_b powers.
+ * Domain: H a multiple of 16 in 16 .. 128, k >= 1; anything else returns SGP_EUNSUP with the reason in sgp_last_error
+ * (sgp_dcrnn_supported answers without a GPU). */
+int32_t sgp_dcrnn_supported(int32_t H, int32_t k);
+
+/* One hop order of one or two supports (rowptr1 = NULL: one) given as CSR tables over n rows (int32 / fp32, columns in
+ * [0, n)): for each support s, Y[b, i, ycol_s : ycol_s + feat] (= | += with accumulate) sum_e val_s[e] *
+ * X[b, col_s[e], xcol_s : xcol_s + feat].  Strides in floats; X and Y may be the same allocation when the column
+ * ranges read and written differ.  One wave owns a destination row and walks its supports in order, so two supports
+ * may accumulate into the same destination columns.
+ *   replaces one self.propagate(sup_index, x=x_sup, weight=sup_weights) per support of
+ *   tsl/nn/layers/graph_convs/diff_conv.py:98-102 (message(), line 72, summed at the targets), and with the tables of
+ *   the transposed supports what autograd derives for it */
+int sgp_diffuse_f32(const int32_t* rowptr0, const int32_t* col0, const float* val0, int64_t xcol0, int64_t ycol0,
+                    const int32_t* rowptr1, const int32_t* col1, const float* val1, int64_t xcol1, int64_t ycol1,
+                    const float* X, int64_t x_row_stride, int64_t x_batch_stride,
+                    float* Y, int64_t y_row_stride, int64_t y_batch_stride,
+                    int32_t n, int32_t batch, int32_t feat, int32_t accumulate, sgp_stream_t stream);
+
+/* [r | u] = sigmoid(Dh Wh_ru^T + G[:, 0 : 2 H]) over R rows; Dh [R, (2 k + 1) H] with h in slot 0; w_ru_packed:
+ * sgp_dense_pack_f32 of the h columns of forget_gate and update_gate stacked, [2 H, (2 k + 1) H].  Stores r and u into
+ * ruc [R, 3 H] (columns 0 .. 2 H) and r * h into slot 0 of Drh.
+ *   replaces the h half of forget_gate / update_gate's filters, the sigmoids and r * h of
+ *   tsl/nn/blocks/encoders/gcrnn.py:14-17 (filters: diff_conv.py:105) */
+int sgp_dcrnn_gates_f32(const float* Dh, int64_t d_row_stride, const float* w_ru_packed,
+                        const float* G, int64_t g_row_stride, float* ruc, int64_t ruc_row_stride,
+                        float* Drh, int64_t drh_row_stride, int64_t R, int32_t H, int32_t k, sgp_stream_t stream);
+
+/* c = tanh(Drh Wh_c^T + G[:, 2 H : 3 H]), h' = u h_prev + (1 - u) c.  c goes to ruc[:, 2 H : 3 H]; h' to h_seq_t
+ * [R, H] (may be NULL), to the leading H columns of dh_next (slot 0 of the next step's Dh, may be NULL, may be the
+ * buffer h_prev points into) and to h_last [R, H] (may be NULL).
+ *   replaces the h half of candidate_gate's filters, the tanh and the state update of gcrnn.py:18-19 */
+int sgp_dcrnn_update_f32(const float* Drh, int64_t d_row_stride, const float* w_c_packed,
+                         const float* G, int64_t g_row_stride, float* ruc, int64_t ruc_row_stride,
+                         const float* h_prev, int64_t h_row_stride, float* h_seq_t, float* dh_next,
+                         int64_t dh_next_row_stride, float* h_last, int64_t R, int32_t H, int32_t k,
+                         sgp_stream_t stream);
+
+/* The elementwise half of one reversed step; dh [R, H] is the carried cotangent of h_t, updated in place; dz [R, 3 H]
+ * = (dzr | dzu | dzc), the gradients of the pre-activations.
+ *   phase 1: dzc = dh (1 - u)(1 - c^2), dzu = dh (h_prev - c) u (1 - u), dh <- dh u
+ *   phase 2: with dDrh (slot 0 of the cotangent of Drh): dzr = dDrh h_prev r (1 - r), dh += dDrh r
+ * ruc and dz may be the same allocation with the same row stride (dz then overwrites r | u | c in place): element
+ * (row, col) of each of the three blocks is read and written by one thread, which loads all it needs before it stores.
+ *   replaces what autograd derives for gcrnn.py:15-19 */
+int sgp_dcrnn_bwd_f32(int32_t phase, float* dh, const float* ruc, int64_t ruc_row_stride,
+                      const float* h_prev, int64_t h_row_stride, const float* dDrh, int64_t ddrh_row_stride,
+                      float* dz, int64_t dz_row_stride, int64_t R, int32_t H, sgp_stream_t stream);
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

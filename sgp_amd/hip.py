@@ -198,6 +198,15 @@ SIGNATURES = {
     "sgp_rnn_window_fwd_f32": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_u64,
                                               c_p, c_i32, c_p]),
     "sgp_rnn_window_bwd_f32": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i64, c_p, c_p, c_p, c_p, c_p, c_i32, c_p]),
+    "sgp_dcrnn_supported": (c_i32, [c_i32, c_i32]),
+    "sgp_diffuse_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_i64,
+                                       c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_p]),
+    "sgp_dcrnn_gates_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i32, c_i32,
+                                           c_p]),
+    "sgp_dcrnn_update_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p,
+                                            c_i64, c_i32, c_i32, c_p]),
+    "sgp_dcrnn_bwd_f32": (ctypes.c_int, [c_i32, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i32,
+                                         c_p]),
     "sgp_event_create": (ctypes.c_int, [ctypes.POINTER(c_p)]),
     "sgp_event_destroy": (ctypes.c_int, [c_p]),
     "sgp_event_record": (ctypes.c_int, [c_p, c_p]),
@@ -1285,6 +1294,89 @@ def rnn_window_bwd(gates, cell, H, S, M, packed, h_seq, c_seq, dy, dy_full):
     _check(lib.sgp_rnn_window_bwd_f32(RNN_CELLS.get(cell, -1), H, S, M, gates.data_ptr(), packed.data_ptr(),
                                       _ptr(h_seq), _ptr(c_seq), dy.data_ptr(), int(bool(dy_full)), _stream(gates)),
            "sgp_rnn_window_bwd_f32")
+
+
+# ---------------------------------------------------------------- DCRNN: diffusion hop and GRU cell (dcrnn.hip)
+def dcrnn_supported(H, k):
+    """Whether the diffusion-GRU kernels cover hidden size ``H`` with ``k`` hops per support (no GPU needed)."""
+    return bool(load().sgp_dcrnn_supported(int(H), int(k)))
+
+
+def dcrnn_require(H, k):
+    if not dcrnn_supported(H, k):
+        raise NotImplementedError("dcrnn: " + load().sgp_last_error().decode())
+
+
+@_on_device
+def diffuse(x, y, feat, supports, accumulate=False):
+    """One hop order of one or two supports (include/sgp_amd.h, sgp_diffuse_f32).  ``x``, ``y``: [B, n, width] float32
+    CUDA views with unit column stride (they may be views of one buffer); ``supports``: one or two
+    ``((rowptr, col, val), xcol, ycol)``: ``y[b, i, ycol : ycol + feat] (+)= sum_e val[e] x[b, col[e], xcol : xcol + feat]``."""
+    lib = require_gpu()
+    xp, xrs, xbs = _view3(x, "x")
+    yp, yrs, ybs = _view3(y, "y")
+    if x.shape[:2] != y.shape[:2]:
+        raise ValueError(f"x {tuple(x.shape)} and y {tuple(y.shape)} must agree in batch and nodes")
+    if not 1 <= len(supports) <= 2:
+        raise ValueError("one or two supports per launch")
+    B, n = x.shape[0], x.shape[1]
+    args = []
+    for (rowptr, col, val), xcol, ycol in supports:
+        if rowptr.numel() != n + 1:
+            raise ValueError(f"support over {rowptr.numel() - 1} rows, x has {n}")
+        if xcol < 0 or ycol < 0 or xcol + feat > x.shape[2] or ycol + feat > y.shape[2]:
+            raise ValueError("column range outside the buffer")
+        args += [rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), int(xcol), int(ycol)]
+    if len(supports) == 1:
+        args += [None, None, None, 0, 0]
+    _check(lib.sgp_diffuse_f32(*args, xp, xrs, xbs, yp, yrs, ybs, n, B, int(feat), int(bool(accumulate)), _stream(y)),
+           "sgp_diffuse_f32")
+
+
+@_on_device
+def dcrnn_gates(dh, w_ru, g, ruc, drh, H, k):
+    """``[r | u] = sigmoid(dh Wh_ru^T + g[:, :2 H])`` into ``ruc[:, :2 H]``, ``r * h`` into slot 0 of ``drh``
+    (sgp_dcrnn_gates_f32); all [R, .] float32 CUDA views with unit column stride."""
+    lib = require_gpu()
+    K = (2 * k + 1) * H
+    dp, drs = _rows2(dh, "dh", K)
+    gp, grs = _rows2(g, "g", 3 * H)
+    rp, rrs = _rows2(ruc, "ruc", 3 * H)
+    op, ors = _rows2(drh, "drh", H)
+    _check(lib.sgp_dcrnn_gates_f32(dp, drs, w_ru.data_ptr(), gp, grs, rp, rrs, op, ors, dh.shape[0], H, k, _stream(dh)),
+           "sgp_dcrnn_gates_f32")
+
+
+@_on_device
+def dcrnn_update(drh, w_c, g, ruc, h_prev, H, k, h_seq_t=None, dh_next=None, h_last=None):
+    """``c = tanh(drh Wh_c^T + g[:, 2 H:])``, ``h' = u h_prev + (1 - u) c`` (sgp_dcrnn_update_f32); ``h'`` goes to
+    whichever of ``h_seq_t`` [R, H] (contiguous), ``dh_next`` (leading H columns) and ``h_last`` [R, H] is given."""
+    lib = require_gpu()
+    K = (2 * k + 1) * H
+    dp, drs = _rows2(drh, "drh", K)
+    gp, grs = _rows2(g, "g", 3 * H)
+    rp, rrs = _rows2(ruc, "ruc", 3 * H)
+    hp, hrs = _rows2(h_prev, "h_prev", H)
+    for name, t in (("h_seq_t", h_seq_t), ("h_last", h_last)):
+        if t is not None and (_rows2(t, name, H)[1] != H or t.shape[0] != drh.shape[0]):
+            raise ValueError(f"{name}: expected a contiguous [{drh.shape[0]}, {H}]")
+    np_, nrs = _rows2(dh_next, "dh_next", H) if dh_next is not None else (None, 0)
+    _check(lib.sgp_dcrnn_update_f32(dp, drs, w_c.data_ptr(), gp, grs, rp, rrs, hp, hrs, _ptr(h_seq_t), np_, nrs,
+                                    _ptr(h_last), drh.shape[0], H, k, _stream(drh)), "sgp_dcrnn_update_f32")
+
+
+@_on_device
+def dcrnn_bwd(phase, dh, ruc, h_prev, dz, H, ddrh=None):
+    """The elementwise half of one reversed step (sgp_dcrnn_bwd_f32); ``dh`` [R, H] contiguous, updated in place."""
+    lib = require_gpu()
+    if not dh.is_contiguous() or dh.shape[1] != H:
+        raise ValueError("dh: expected a contiguous [R, H]")
+    rp, rrs = _rows2(ruc, "ruc", 3 * H)
+    hp, hrs = _rows2(h_prev, "h_prev", H)
+    zp, zrs = _rows2(dz, "dz", 3 * H)
+    qp, qrs = _rows2(ddrh, "ddrh", H) if ddrh is not None else (None, 0)
+    _check(lib.sgp_dcrnn_bwd_f32(int(phase), dh.data_ptr(), rp, rrs, hp, hrs, qp, qrs, zp, zrs, dh.shape[0], H,
+                                 _stream(dh)), "sgp_dcrnn_bwd_f32")
 
 
 class Event:

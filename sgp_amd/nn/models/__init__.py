@@ -2,6 +2,7 @@ from .esn_model import ESNModel
 from .sgp_model import OnlineSGPModel, SGPInputEncoder, SGPModel, masked_mae
 from .gated_gn_model import GatedGraphNetwork, GatedGraphNetworkMLPModel, GatedGraphNetworkModel
 from .rnn_model import FCRNNModel, RNNModel
+from .dcrnn_model import DCRNNModel
 
 __all__ = ["SGPInputEncoder", "SGPModel", "OnlineSGPModel", "ESNModel", "masked_mae", "GatedGraphNetwork",
-           "GatedGraphNetworkModel", "GatedGraphNetworkMLPModel", "RNNModel", "FCRNNModel"]
+           "GatedGraphNetworkModel", "GatedGraphNetworkMLPModel", "RNNModel", "FCRNNModel", "DCRNNModel"]
