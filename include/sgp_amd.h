@@ -906,6 +906,85 @@ int sgp_dcrnn_bwd_f32(int32_t phase, float* dh, const float* ruc, int64_t ruc_ro
                       const float* h_prev, int64_t h_row_stride, const float* dDrh, int64_t ddrh_row_stride,
                       float* dz, int64_t dz_row_stride, int64_t R, int32_t H, sgp_stream_t stream);
 
+/* ------------------------------------------------ Graph WaveNet baseline: gated TCN, dense learned adjacency, norm -----
+ * gwnet.hip.  EXACT-FP32 contract as above (v_mfma_f32_16x16x4_f32 in the matrix kernels), no float atomics, every sum
+ * in one fixed order: bit-identical from run to run and independent of the row or batch item a value falls into.
+ * Activations are time-major [S, M, H] (M = b n): tap j of the temporal convolution is the row offset j d M.
+ * Domain of the model: H a multiple of 16 in 16 .. 128, Kt in 1 .. 4; anything else returns SGP_EUNSUP with the reason
+ * in sgp_last_error (sgp_gwnet_supported answers without a GPU). */
+int32_t sgp_gwnet_supported(int32_t H, int32_t Kt);
+
+/* y[r] = tanh(a) * sigmoid(g), [a | g] = sum_j W_j x[r + j tap_rows] + bias for n_rows output rows; X has x_rows rows
+ * (n_rows + (Kt - 1) tap_rows <= x_rows is checked).  w_packed: sgp_dense_pack_f32 of the conv weight [2 H, H, 1, Kt]
+ * rearranged tap-major to [2 H, Kt H]; bias [2 H].  act (may be NULL): [n_rows, 2 H] = [tanh a | sigmoid g] for the
+ * backward pass.  Row strides in floats, multiples of 4; buffers 16-byte aligned.
+ *   replaces self.conv(x) of tsl/nn/base/temporal_conv.py:54 (Conv2d(H, 2 H, (1, Kt), dilation (1, d)), no padding:
+ *   tsl/nn/blocks/encoders/tcn.py:60-68 with causal_padding False) and gated_tanh of temporal_conv.py:88 */
+int sgp_gwnet_tconv_f32(const float* X, int64_t x_row_stride, int64_t x_rows, int64_t tap_rows,
+                        const float* w_packed, const float* bias, float* Y, int64_t y_row_stride,
+                        float* act, int64_t act_row_stride, int64_t n_rows, int32_t H, int32_t Kt,
+                        sgp_stream_t stream);
+
+/* dz = [dy s (1 - t^2) | dy t s (1 - s)] written over act = [t | s] of the forward pass (which therefore runs once).
+ *   replaces what autograd derives for gated_tanh (temporal_conv.py:88); the convolution's own gradients are
+ *   sgp_dense_wgrad_f32 / sgp_dense_f32 per tap on time-major slices */
+int sgp_gwnet_tconv_bwd_f32(const float* dY, int64_t dy_row_stride, float* act, int64_t act_row_stride,
+                            int64_t n_rows, int32_t H, sgp_stream_t stream);
+
+/* Y[i, w, ycol : ycol + feat] (= | += with accumulate) sum_v A[w, v] X[i, v, xcol : xcol + feat] for every batch item i
+ * (transpose: A[v, w]).  A: dense fp32 [n, n] with a row stride, shared by all items; X and Y may be column slots of one
+ * concat buffer when the column ranges differ.  feat a multiple of 16; strides and column offsets multiples of 4.
+ *   replaces torch.einsum('ncvl, wv -> ncwl', (x1, a)) of tsl/nn/layers/graph_convs/dense_spatial_conv.py:81, and with
+ *   transpose what autograd derives for it with respect to x1 */
+int sgp_adj_apply_f32(const float* A, int64_t a_row_stride, int32_t transpose,
+                      const float* X, int64_t xcol, int64_t x_row_stride, int64_t x_batch_stride,
+                      float* Y, int64_t ycol, int64_t y_row_stride, int64_t y_batch_stride,
+                      int32_t n, int32_t batch, int32_t feat, int32_t accumulate, sgp_stream_t stream);
+
+/* dA[w, v] (= | +=) sum_i sum_f dY[i, w, dycol + f] X[i, v, xcol + f], the items in order.  A small operator splits
+ * the items into slices with one partial each (work, sgp_adj_grad_workspace_floats; 0: none needed), added in slice
+ * order in fp64.
+ *   replaces what autograd derives for dense_spatial_conv.py:81 with respect to a */
+int64_t sgp_adj_grad_workspace_floats(int32_t n, int32_t batch);
+int sgp_adj_grad_f32(const float* dY, int64_t dycol, int64_t dy_row_stride, int64_t dy_batch_stride,
+                     const float* X, int64_t xcol, int64_t x_row_stride, int64_t x_batch_stride,
+                     float* dA, int64_t da_row_stride, int32_t n, int32_t batch, int32_t feat, int32_t accumulate,
+                     float* work, int64_t work_floats, sgp_stream_t stream);
+
+/* A[r, :] = softmax(L[r, :]) with the row maximum subtracted; dL = A (dA - sum_j dA A) where L > 0, else 0 (the relu of
+ * the logits folded into the backward pass; dL may be dA).
+ *   replaces torch.softmax(logits, dim=1) of lib/nn/models/gwnet_model.py:12 and what autograd derives for lines 10-12 */
+int sgp_row_softmax_f32(const float* L, int64_t l_row_stride, float* A, int64_t a_row_stride, int32_t n_rows, int32_t n,
+                        sgp_stream_t stream);
+int sgp_row_softmax_bwd_f32(const float* A, int64_t a_row_stride, const float* dA, int64_t da_row_stride,
+                            const float* L, int64_t l_row_stride, float* dL, int64_t dl_row_stride,
+                            int32_t n_rows, int32_t n, sgp_stream_t stream);
+
+/* z = dropout(Y) + res (res may be NULL), out = norm(z) over R rows of H <= 256 columns.  kind 0: none; 1: batch
+ * (training: statistics over all rows, biased variance, running buffers updated with the unbiased one; else the
+ * running buffers); 2: layer, (z - mean) / (std + eps) with the population std, then the affine.  Dropout is the Philox
+ * scheme of sgp_dense_f32 at index row * H + col.  z_save [R, H] (may be NULL) and stats (batch: mean | rstd | low part of the mean [3 H],
+ * required; layer: (mean, 1 / (std + eps)) [R, 2], may be NULL) are what the backward pass reads.  work: batch
+ * training only, sgp_gwnet_norm_workspace_doubles.
+ *   replaces self.dropout(x), x + res[:, -x.size(1):] and norm(x) of graph_wavenet_model.py:157-160
+ *   (tsl/nn/layers/norm/batch_norm.py:35-37, layer_norm.py:40-46) */
+int64_t sgp_gwnet_norm_workspace_doubles(int64_t R, int32_t H);
+int sgp_gwnet_norm_f32(int32_t kind, int32_t training, const float* Y, int64_t y_row_stride,
+                       const float* res, int64_t res_row_stride, double dropout_p, uint64_t seed,
+                       const float* weight, const float* bias, float* running_mean, float* running_var,
+                       double momentum, double eps, float* z_save, float* stats,
+                       float* out, int64_t out_row_stride, int64_t R, int32_t H,
+                       double* work, int64_t work_doubles, sgp_stream_t stream);
+
+/* dY = dz * keep, dRes = dz (may be NULL), dweight = column sums of dOut * xhat, dbias of dOut (fp64 over row slices,
+ * slice order), with dz the cotangent of z.
+ *   replaces what autograd derives for graph_wavenet_model.py:157-160 */
+int sgp_gwnet_norm_bwd_f32(int32_t kind, int32_t training, const float* dOut, int64_t dout_row_stride,
+                           const float* z, const float* stats, const float* weight, double dropout_p, uint64_t seed,
+                           double eps, float* dY, int64_t dy_row_stride, float* dRes, int64_t dres_row_stride,
+                           float* dweight, float* dbias, int64_t R, int32_t H,
+                           double* work, int64_t work_doubles, sgp_stream_t stream);
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

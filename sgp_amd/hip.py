@@ -207,6 +207,22 @@ SIGNATURES = {
                                             c_i64, c_i32, c_i32, c_p]),
     "sgp_dcrnn_bwd_f32": (ctypes.c_int, [c_i32, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i32,
                                          c_p]),
+    "sgp_gwnet_supported": (c_i32, [c_i32, c_i32]),
+    "sgp_gwnet_tconv_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_i32, c_i32,
+                                           c_p]),
+    "sgp_gwnet_tconv_bwd_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_i32, c_p]),
+    "sgp_adj_apply_f32": (ctypes.c_int, [c_p, c_i64, c_i32, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64,
+                                         c_i32, c_i32, c_i32, c_i32, c_p]),
+    "sgp_adj_grad_workspace_floats": (c_i64, [c_i32, c_i32]),
+    "sgp_adj_grad_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64,
+                                        c_i32, c_i32, c_i32, c_i32, c_p, c_i64, c_p]),
+    "sgp_row_softmax_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_p]),
+    "sgp_row_softmax_bwd_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_p]),
+    "sgp_gwnet_norm_workspace_doubles": (c_i64, [c_i64, c_i32]),
+    "sgp_gwnet_norm_f32": (ctypes.c_int, [c_i32, c_i32, c_p, c_i64, c_p, c_i64, c_f64, c_u64, c_p, c_p, c_p, c_p,
+                                          c_f64, c_f64, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_p]),
+    "sgp_gwnet_norm_bwd_f32": (ctypes.c_int, [c_i32, c_i32, c_p, c_i64, c_p, c_p, c_p, c_f64, c_u64, c_f64, c_p, c_i64,
+                                              c_p, c_i64, c_p, c_p, c_i64, c_i32, c_p, c_i64, c_p]),
     "sgp_event_create": (ctypes.c_int, [ctypes.POINTER(c_p)]),
     "sgp_event_destroy": (ctypes.c_int, [c_p]),
     "sgp_event_record": (ctypes.c_int, [c_p, c_p]),
@@ -1377,6 +1393,166 @@ def dcrnn_bwd(phase, dh, ruc, h_prev, dz, H, ddrh=None):
     qp, qrs = _rows2(ddrh, "ddrh", H) if ddrh is not None else (None, 0)
     _check(lib.sgp_dcrnn_bwd_f32(int(phase), dh.data_ptr(), rp, rrs, hp, hrs, qp, qrs, zp, zrs, dh.shape[0], H,
                                  _stream(dh)), "sgp_dcrnn_bwd_f32")
+
+
+# ---------------------------------------------------------------- Graph WaveNet: gated TCN, dense operator, norm (gwnet.hip)
+def gwnet_supported(H, Kt):
+    """Whether the Graph WaveNet kernels cover hidden size ``H`` with temporal kernel size ``Kt`` (no GPU needed)."""
+    return bool(load().sgp_gwnet_supported(int(H), int(Kt)))
+
+
+def gwnet_require(H, Kt):
+    if not gwnet_supported(H, Kt):
+        raise NotImplementedError("gwnet: " + load().sgp_last_error().decode())
+
+
+@_on_device
+def gwnet_tconv(x, packed, bias, n_rows, tap_rows, H, Kt, out=None, act=None):
+    """``y = tanh(a) * sigmoid(g)``, ``[a | g] = sum_j W_j x[r + j tap_rows] + bias`` over ``n_rows`` rows of the
+    time-major ``x [rows, >= H]`` (sgp_gwnet_tconv_f32); ``act [n_rows, 2 H]`` receives ``[tanh a | sigmoid g]``."""
+    lib = require_gpu()
+    xp, xrs = _rows2(x, "x", H)
+    if out is None:
+        out = torch.empty(n_rows, H, dtype=torch.float32, device=x.device)
+    op, ors = _rows2(out, "out", H)
+    ap, ars = _rows2(act, "act", 2 * H) if act is not None else (None, 0)
+    _check(lib.sgp_gwnet_tconv_f32(xp, xrs, x.shape[0], int(tap_rows), packed.data_ptr(), bias.data_ptr(), op, ors,
+                                   ap, ars, int(n_rows), int(H), int(Kt), _stream(x)), "sgp_gwnet_tconv_f32")
+    return out
+
+
+@_on_device
+def gwnet_tconv_bwd(dy, act, H):
+    """``act = [t | s] -> dz = [dy s (1 - t^2) | dy t s (1 - s)]`` in place (sgp_gwnet_tconv_bwd_f32)."""
+    lib = require_gpu()
+    dp, drs = _rows2(dy, "dy", H)
+    ap, ars = _rows2(act, "act", 2 * H)
+    _check(lib.sgp_gwnet_tconv_bwd_f32(dp, drs, ap, ars, act.shape[0], int(H), _stream(act)), "sgp_gwnet_tconv_bwd_f32")
+    return act
+
+
+def _adj2(A, name):
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or A.dtype != torch.float32 or not A.is_cuda or \
+            (A.shape[1] > 1 and A.stride(1) != 1):
+        raise ValueError(f"{name}: expected a square float32 CUDA matrix with unit column stride, got {tuple(A.shape)}")
+    return A.data_ptr(), max(A.stride(0), A.shape[1])
+
+
+@_on_device
+def adj_apply(A, x, y, feat, xcol=0, ycol=0, transpose=False, accumulate=False):
+    """``y[i, w, ycol : ycol + feat] (+)= sum_v A[w, v] x[i, v, xcol : xcol + feat]`` (``transpose``: ``A[v, w]``) for
+    every item ``i`` (sgp_adj_apply_f32).  ``x``, ``y``: [B, n, width] float32 CUDA views, possibly of one buffer."""
+    lib = require_gpu()
+    ap, ars = _adj2(A, "A")
+    xp, xrs, xbs = _view3(x, "x")
+    yp, yrs, ybs = _view3(y, "y")
+    n = A.shape[0]
+    if x.shape[:2] != y.shape[:2] or x.shape[1] != n:
+        raise ValueError(f"x {tuple(x.shape)}, y {tuple(y.shape)} and A {tuple(A.shape)} must agree in batch and nodes")
+    if xcol < 0 or ycol < 0 or xcol + feat > x.shape[2] or ycol + feat > y.shape[2]:
+        raise ValueError("column range outside the buffer")
+    _check(lib.sgp_adj_apply_f32(ap, ars, int(bool(transpose)), xp, int(xcol), xrs, xbs, yp, int(ycol), yrs, ybs,
+                                 n, x.shape[0], int(feat), int(bool(accumulate)), _stream(y)), "sgp_adj_apply_f32")
+    return y
+
+
+@_on_device
+def adj_grad(dy, x, dA, feat, dycol=0, xcol=0, accumulate=False):
+    """``dA[w, v] (+)= sum_i sum_f dy[i, w, dycol + f] x[i, v, xcol + f]`` (sgp_adj_grad_f32); deterministic."""
+    lib = require_gpu()
+    ap, ars = _adj2(dA, "dA")
+    dp, drs, dbs = _view3(dy, "dy")
+    xp, xrs, xbs = _view3(x, "x")
+    n, B = dA.shape[0], x.shape[0]
+    if x.shape[:2] != dy.shape[:2] or x.shape[1] != n:
+        raise ValueError(f"x {tuple(x.shape)}, dy {tuple(dy.shape)} and dA {tuple(dA.shape)} must agree")
+    if xcol < 0 or dycol < 0 or xcol + feat > x.shape[2] or dycol + feat > dy.shape[2]:
+        raise ValueError("column range outside the buffer")
+    nw = lib.sgp_adj_grad_workspace_floats(n, B)
+    work = torch.empty(nw, dtype=torch.float32, device=x.device) if nw > 0 else None
+    _check(lib.sgp_adj_grad_f32(dp, int(dycol), drs, dbs, xp, int(xcol), xrs, xbs, ap, ars, n, B, int(feat),
+                                int(bool(accumulate)), _ptr(work), max(nw, 0), _stream(dA)), "sgp_adj_grad_f32")
+    return dA
+
+
+@_on_device
+def row_softmax(L, out=None):
+    """Rows of ``softmax(L)`` (sgp_row_softmax_f32); ``L``: [rows, n] float32 CUDA, unit column stride."""
+    lib = require_gpu()
+    lp, lrs = _rows2(L, "L", L.shape[1])
+    if out is None:
+        out = torch.empty(L.shape[0], L.shape[1], dtype=torch.float32, device=L.device)
+    op, ors = _rows2(out, "out", L.shape[1])
+    _check(lib.sgp_row_softmax_f32(lp, lrs, op, ors, L.shape[0], L.shape[1], _stream(L)), "sgp_row_softmax_f32")
+    return out
+
+
+@_on_device
+def row_softmax_bwd(A, dA, L, out=None):
+    """``dL = A (dA - sum_j dA A) [L > 0]`` (sgp_row_softmax_bwd_f32)."""
+    lib = require_gpu()
+    n = A.shape[1]
+    ap, ars = _rows2(A, "A", n)
+    gp, grs = _rows2(dA, "dA", n)
+    lp, lrs = _rows2(L, "L", n)
+    if out is None:
+        out = torch.empty(A.shape[0], n, dtype=torch.float32, device=A.device)
+    op, ors = _rows2(out, "out", n)
+    _check(lib.sgp_row_softmax_bwd_f32(ap, ars, gp, grs, lp, lrs, op, ors, A.shape[0], n, _stream(A)),
+           "sgp_row_softmax_bwd_f32")
+    return out
+
+
+NORM_KINDS = {"none": 0, "batch": 1, "layer": 2}
+
+
+@_on_device
+def gwnet_norm(y, res, kind, training, weight=None, bias=None, running_mean=None, running_var=None, momentum=0.1,
+               eps=1e-5, dropout_p=0., seed=0, save=False):
+    """``norm(dropout(y) + res)`` over rows ``y [R, H]`` (sgp_gwnet_norm_f32); ``res`` may be None.  Returns
+    ``(out [R, H], z, stats)``: with ``save`` the pre-norm sum ``z [R, H]`` and the statistics the backward pass reads
+    (``None`` for ``kind='none'``)."""
+    lib = require_gpu()
+    R, H = y.shape
+    yp, yrs = _rows2(y, "y", H)
+    rp, rrs = _rows2(res, "res", H) if res is not None else (None, 0)
+    k = NORM_KINDS[kind]
+    dev = y.device
+    out = torch.empty(R, H, dtype=torch.float32, device=dev)
+    z = torch.empty(R, H, dtype=torch.float32, device=dev) if (save and k) else None
+    stats = None
+    if k == 1:
+        stats = torch.empty(3 * H, dtype=torch.float32, device=dev)
+    elif k == 2 and save:
+        stats = torch.empty(R, 2, dtype=torch.float32, device=dev)
+    work = None
+    if k == 1 and training:
+        work = torch.empty(lib.sgp_gwnet_norm_workspace_doubles(R, H), dtype=torch.float64, device=dev)
+    _check(lib.sgp_gwnet_norm_f32(k, int(bool(training)), yp, yrs, rp, rrs, float(dropout_p), int(seed), _ptr(weight),
+                                  _ptr(bias), _ptr(running_mean), _ptr(running_var), float(momentum), float(eps),
+                                  _ptr(z), _ptr(stats), out.data_ptr(), H, R, H, _ptr(work),
+                                  work.numel() if work is not None else 0, _stream(y)), "sgp_gwnet_norm_f32")
+    return out, z, stats
+
+
+@_on_device
+def gwnet_norm_bwd(dout, z, stats, kind, training, weight=None, eps=1e-5, dropout_p=0., seed=0, want_res=True):
+    """``(dy, dres or None, dweight, dbias)`` of :func:`gwnet_norm` (sgp_gwnet_norm_bwd_f32)."""
+    lib = require_gpu()
+    R, H = dout.shape
+    dp, drs = _rows2(dout, "dout", H)
+    k = NORM_KINDS[kind]
+    dev = dout.device
+    dy = torch.empty(R, H, dtype=torch.float32, device=dev)
+    dres = torch.empty(R, H, dtype=torch.float32, device=dev) if want_res else None
+    dw = torch.empty(H, dtype=torch.float32, device=dev) if k else None
+    db = torch.empty(H, dtype=torch.float32, device=dev) if k else None
+    work = torch.empty(lib.sgp_gwnet_norm_workspace_doubles(R, H), dtype=torch.float64, device=dev) if k else None
+    _check(lib.sgp_gwnet_norm_bwd_f32(k, int(bool(training)), dp, drs, _ptr(z), _ptr(stats), _ptr(weight),
+                                      float(dropout_p), int(seed), float(eps), dy.data_ptr(), H, _ptr(dres), H,
+                                      _ptr(dw), _ptr(db), R, H, _ptr(work), work.numel() if work is not None else 0,
+                                      _stream(dout)), "sgp_gwnet_norm_bwd_f32")
+    return dy, dres, dw, db
 
 
 class Event:

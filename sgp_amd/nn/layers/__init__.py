@@ -2,5 +2,7 @@ from .gated_gn import GatedGraphNetwork, edge_plan
 from .rnn import RNN
 from .diff_conv import DiffConv, DiffusionPlan, diffusion_plan
 from .dcrnn import DCRNN, DCRNNCell
+from .gwnet import GatedTemporalConv, Norm, SpatialConvOrderK, TemporalConvNet
 
-__all__ = ["GatedGraphNetwork", "edge_plan", "RNN", "DiffConv", "DiffusionPlan", "diffusion_plan", "DCRNN", "DCRNNCell"]
+__all__ = ["GatedGraphNetwork", "edge_plan", "RNN", "DiffConv", "DiffusionPlan", "diffusion_plan", "DCRNN", "DCRNNCell",
+           "GatedTemporalConv", "TemporalConvNet", "SpatialConvOrderK", "Norm"]

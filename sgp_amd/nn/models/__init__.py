@@ -3,6 +3,8 @@ from .sgp_model import OnlineSGPModel, SGPInputEncoder, SGPModel, masked_mae
 from .gated_gn_model import GatedGraphNetwork, GatedGraphNetworkMLPModel, GatedGraphNetworkModel
 from .rnn_model import FCRNNModel, RNNModel
 from .dcrnn_model import DCRNNModel
+from .gwnet_model import GraphWaveNetModel
 
 __all__ = ["SGPInputEncoder", "SGPModel", "OnlineSGPModel", "ESNModel", "masked_mae", "GatedGraphNetwork",
-           "GatedGraphNetworkModel", "GatedGraphNetworkMLPModel", "RNNModel", "FCRNNModel", "DCRNNModel"]
+           "GatedGraphNetworkModel", "GatedGraphNetworkMLPModel", "RNNModel", "FCRNNModel", "DCRNNModel",
+           "GraphWaveNetModel"]
