@@ -381,6 +381,17 @@ int32_t sgp_spmm_tiled_max_union(int32_t feat);
 int32_t sgp_spmm_tiled_max_tile_rows(void);
 int32_t sgp_spmm_tiled_max_row_edges(void);
 
+/* Which kernel form a launch takes -- host-only queries; the entries dispatch on these same answers.
+ * sgp_spmm_tiled_form: rows per edge group (1, 2, or 4 / 6 for tall tiles) and 16-edge batches per row (1, 2, 8) of a
+ * plan with the given tallest tile and largest padded per-row edge count (NULL outputs are skipped).  Returns 0, or
+ * SGP_EUNSUP where sgp_spmm_tiled_f32 has no kernel: beyond the limits above, or 8 batches with more than one row per
+ * group.
+ * sgp_spmm_csr_form: lanes per source-row chunk of the generic rows kernel (4, 8, 16, 32, 64) for `feat`-wide operands,
+ * or 0 = the scalar kernel (feat % 4 != 0, or aligned == 0: a stride that is no multiple of 4 floats / a pointer off a
+ * 16-byte boundary).  predicated != 0 names the bounded-grid form of the same lane count. */
+int sgp_spmm_tiled_form(int32_t tile_rows, int32_t max_row_edges, int32_t* rows_per_group, int32_t* batches);
+int32_t sgp_spmm_csr_form(int32_t feat, int32_t aligned, int32_t predicated);
+
 /* ------------------------------------------------------------- Reservoir ---
  * One leaky-ESN layer over the whole sequence (time loop on the device):
  *   h[t] = (1 - alpha) * h[t-1] + alpha * act(x[t] W_ih^T + b + h[t-1] W_hh^T)

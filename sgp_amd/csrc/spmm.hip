@@ -455,6 +455,33 @@ int32_t sgp_spmm_tiled_max_union(int32_t feat) {
 int32_t sgp_spmm_tiled_max_tile_rows(void) { return 6 * kTiledGroups; }   // (rows / group 1, 2, 4, 6)
 int32_t sgp_spmm_tiled_max_row_edges(void) { return 8 * 16; }
 
+// Which instantiation a tile plan takes (host only; the entry below dispatches on this answer): rows per edge group
+// (1, 2; tall tiles 4 or 6 -- the kernel masks the rows a group does not have) and 16-edge batches per row.
+int sgp_spmm_tiled_form(int32_t tile_rows, int32_t max_row_edges, int32_t* rows_per_group, int32_t* batches) {
+    SGP_REQUIRE(tile_rows > 0 && max_row_edges >= 0 && max_row_edges % 16 == 0, "sgp_spmm_tiled_form: bad size");
+    if (tile_rows > sgp_spmm_tiled_max_tile_rows() || max_row_edges > sgp_spmm_tiled_max_row_edges())
+        return sgp::fail(SGP_EUNSUP, "sgp_spmm_tiled_f32: tile_rows=%d / max_row_edges=%d out of range",
+                         tile_rows, max_row_edges);
+    int rpg = (tile_rows + kTiledGroups - 1) / kTiledGroups;
+    rpg = rpg <= 2 ? rpg : (rpg <= 4 ? 4 : 6);
+    const int nb = (rpg > 2 && max_row_edges <= 16) ? 1 : (max_row_edges <= 32 ? 2 : 8);
+    if (rows_per_group) *rows_per_group = rpg;
+    if (batches) *batches = nb;
+    if (nb == 8 && rpg != 1)
+        return sgp::fail(SGP_EUNSUP, "spmm_tiled: no kernel for rows/group=%d batches=%d", rpg, nb);
+    return 0;
+}
+
+// Lanes per source row chunk of the generic rows kernel (4 .. 64; the predicated launch takes the grid-strided form of
+// the same instantiation), or 0: the scalar kernel (feature widths that are no multiple of 4 floats, or operands that are
+// not 16-byte aligned: `aligned` = 0).  Host only; the entry below dispatches on this answer.
+int32_t sgp_spmm_csr_form(int32_t feat, int32_t aligned, int32_t predicated) {
+    (void)predicated;                    // (rows and rows_strided share their lane count)
+    if (feat <= 0 || feat % 4 != 0 || !aligned) return 0;
+    if (feat >= 256 || feat % 256 == 0) return 64;
+    return feat > 64 ? 32 : feat > 32 ? 16 : feat > 16 ? 8 : 4;
+}
+
 int sgp_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val,
                      const float* X, int64_t xrs, int64_t xbs,
                      const float* Xh, int64_t xhrs, int64_t xhbs, int32_t n_own,
@@ -472,7 +499,7 @@ int sgp_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val
                      sgp::aligned16(X) && sgp::aligned16(Y) &&
                      (!Xh || (xhrs % 4 == 0 && xhbs % 4 == 0 && sgp::aligned16(Xh)));
     const unsigned gx = (n_rows + 3) / 4;
-    if (!vec) {
+    if (sgp_spmm_csr_form(feat, vec, pr.flag != nullptr) == 0) {
         SGP_REQUIRE(batch <= 65535, "sgp_spmm_csr_f32: scalar path supports batch <= 65535");
         hipLaunchKernelGGL(spmm_csr_scalar, dim3(gx, batch), dim3(256), 0, s,
                            rowptr, col, val, src, Y, yrs, ybs, n_rows, batch, feat);
@@ -492,11 +519,13 @@ int sgp_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val
             hipLaunchKernelGGL((spmm_csr_rows<LPR, TB>), dim3(gx, gy, (feat + 4 * LPR - 1) / (4 * LPR)), \
                                dim3(256), 0, s, rowptr, col, val, src, Y, yrs, ybs, n_rows, batch, feat);  \
     } while (0)
-    if (feat >= 256 || feat % 256 == 0) SGP_ROWS(64);
-    else if (feat > 64) SGP_ROWS(32);
-    else if (feat > 32) SGP_ROWS(16);
-    else if (feat > 16) SGP_ROWS(8);
-    else SGP_ROWS(4);
+    switch (sgp_spmm_csr_form(feat, 1, bounded)) {
+        case 64: SGP_ROWS(64); break;
+        case 32: SGP_ROWS(32); break;
+        case 16: SGP_ROWS(16); break;
+        case 8: SGP_ROWS(8); break;
+        default: SGP_ROWS(4); break;
+    }
 #undef SGP_ROWS
     return sgp::check_launch("spmm_csr_rows");
 }
@@ -525,9 +554,9 @@ int sgp_spmm_tiled_f32(const int32_t* trow, const int32_t* uptr, const int32_t* 
     if (max_union > kTiledCapacity)
         return sgp::fail(SGP_EUNSUP, "sgp_spmm_tiled_f32: a tile references %d distinct rows, LDS stage holds %d",
                          max_union, kTiledCapacity);
-    if (tile_rows > sgp_spmm_tiled_max_tile_rows() || max_row_edges > sgp_spmm_tiled_max_row_edges())
-        return sgp::fail(SGP_EUNSUP, "sgp_spmm_tiled_f32: tile_rows=%d / max_row_edges=%d out of range",
-                         tile_rows, max_row_edges);
+    int32_t rpg = 0, nb = 0;
+    const int form_rc = sgp_spmm_tiled_form(tile_rows, max_row_edges, &rpg, &nb);
+    if (form_rc && rpg == 0) return form_rc;               // beyond the limits (a pair without a kernel: below, as before)
     SGP_REQUIRE(xrs % 4 == 0 && xbs % 4 == 0 && yrs % 4 == 0 && ybs % 4 == 0 &&
                 sgp::aligned16(X) && sgp::aligned16(Y) &&
                 (!Xh || (xhrs % 4 == 0 && xhbs % 4 == 0 && sgp::aligned16(Xh))),
@@ -549,9 +578,7 @@ int sgp_spmm_tiled_f32(const int32_t* trow, const int32_t* uptr, const int32_t* 
     a.t_chunk = tc;
     a.n_tchunks = (batch + tc - 1) / tc;
     a.stage_bytes = ((max_union + 63) / 64 * 64) * 256;   // whole passes of 64 staged rows
-    int rpg = (tile_rows + kTiledGroups - 1) / kTiledGroups;
-    rpg = rpg <= 2 ? rpg : (rpg <= 4 ? 4 : 6);          // (the kernel masks the rows a group does not have)
-    const int nb = (rpg > 2 && max_row_edges <= 16) ? 1 : (max_row_edges <= 32 ? 2 : 8);
+    if (form_rc) return form_rc;                           // rows/group x batches without a kernel
     hipStream_t s = (hipStream_t)stream;
     return Xh ? dispatch_tiled<true>(a, rpg, nb, s) : dispatch_tiled<false>(a, rpg, nb, s);
 }

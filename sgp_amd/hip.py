@@ -59,6 +59,8 @@ SIGNATURES = {
     "sgp_spmm_tiled_max_union": (c_i32, [c_i32]),
     "sgp_spmm_tiled_max_tile_rows": (c_i32, []),
     "sgp_spmm_tiled_max_row_edges": (c_i32, []),
+    "sgp_spmm_tiled_form": (ctypes.c_int, [c_i32, c_i32, c_p, c_p]),
+    "sgp_spmm_csr_form": (c_i32, [c_i32, c_i32, c_i32]),
     "sgp_reservoir_workspace_bytes": (c_i64, [c_i32, c_i32]),
     "sgp_reservoir_f32": (ctypes.c_int, [c_p, c_i64, c_i64,
                                          c_p, c_p, c_p,
@@ -229,6 +231,8 @@ SIGNATURES = {
     "sgp_event_elapsed_ms": (ctypes.c_int, [c_p, c_p, ctypes.POINTER(c_f32)]),
 }
 
+SGP_EINVAL, SGP_EUNSUP, SGP_ENOMEM = -1, -2, -3       # error codes of include/sgp_amd.h
+
 ACT_CODES = {"tanh": 0, "relu": 1, "self_norm": 2, "identity": 3,
              "tanh_rel": 4}     # tanh with relative accuracy near zero (layers whose bias is tiny: ReservoirLayer.kernel_activation)
 
@@ -331,7 +335,7 @@ def cu_masked_streams(device, n_reserved):
 def _check(rc, what):
     if rc != 0:
         msg = load().sgp_last_error().decode()
-        kind = NotImplementedError if rc == -2 else RuntimeError
+        kind = NotImplementedError if rc == SGP_EUNSUP else RuntimeError
         raise kind(f"{what} failed (code {rc}): {msg}")
 
 
@@ -649,6 +653,22 @@ def tall_tile_limits(feat):
     return dict(max_union=lib.sgp_spmm_tiled_max_union(feat),
                 max_tile_rows=lib.sgp_spmm_tiled_max_tile_rows(),
                 max_row_edges=lib.sgp_spmm_tiled_max_row_edges())
+
+
+def tiled_form(tile_rows, max_row_edges):
+    """``(rows per edge group, 16-edge batches per row)`` of the ``sgp_spmm_tiled_f32`` instantiation a plan with these
+    two fields takes, or None where the entry has no kernel (host only: ``sgp_spmm_tiled_form``)."""
+    rpg, nb = c_i32(0), c_i32(0)
+    rc = load().sgp_spmm_tiled_form(int(tile_rows), int(max_row_edges), ctypes.addressof(rpg), ctypes.addressof(nb))
+    if rc not in (0, SGP_EUNSUP):
+        _check(rc, "sgp_spmm_tiled_form")
+    return (rpg.value, nb.value) if rc == 0 else None
+
+
+def csr_form(feat, aligned=True, predicated=False):
+    """Lanes per source-row chunk of the ``sgp_spmm_csr_f32`` launch for these operands (4 .. 64), 0 = the scalar kernel;
+    ``predicated``: the bounded-grid form of that lane count (host only: ``sgp_spmm_csr_form``)."""
+    return int(load().sgp_spmm_csr_form(int(feat), int(bool(aligned)), int(bool(predicated))))
 
 
 # ---------------------------------------------------------------- reservoir
