@@ -996,6 +996,60 @@ int sgp_gwnet_norm_bwd_f32(int32_t kind, int32_t training, const float* dOut, in
                            float* dweight, float* dbias, int64_t R, int32_t H,
                            double* work, int64_t work_doubles, sgp_stream_t stream);
 
+/* ------------------------------------------- k-hop subgraph sampling ---
+ * The batch construction of lib/dataloader/subgraph_dataloader.py on a device-resident int32 edge list.  Node sets
+ * and flag arrays are BIT arrays in 64-bit words (bit i of word i / 64); bits at and beyond the stated length are
+ * ignored.  Every size may be up to 2^31 - 1; all launches are grid-stride.  Ids outside [0, n_nodes) are never
+ * followed: they are skipped, and where an `err` word is given it is set to 1 (it is never cleared here).
+ *
+ * sgp_subgraph_mark: set the bits of ids[0 .. n_ids) in mask (atomic OR; the caller cleared the mask).
+ *   replaces `subsets = [node_idx]` / `node_mask[subsets[-1]] = True` of torch_geometric.utils.k_hop_subgraph, called
+ *   at subgraph_dataloader.py:159 */
+int sgp_subgraph_mark(const int32_t* ids, int64_t n_ids, uint64_t* mask, int64_t n_nodes, int32_t* err,
+                      sgp_stream_t stream);
+/* One hop: mask_out = mask_in | { dst[e] : src[e] in mask_in }.  mask_out is first overwritten with a copy of
+ * mask_in; the two must be different buffers (a node reached in this hop must not expand in it).
+ *   replaces one turn of `torch.index_select(node_mask, 0, row, out=edge_mask); subsets.append(col[edge_mask])` in
+ *   k_hop_subgraph(flow='target_to_source') (subgraph_dataloader.py:159-161: row = edge_index[0], col = edge_index[1]) */
+int sgp_subgraph_expand(const int32_t* src, const int32_t* dst, int64_t n_edges, const uint64_t* mask_in,
+                        uint64_t* mask_out, int64_t n_nodes, sgp_stream_t stream);
+/* flags bit e = mask[src[e]] & mask[dst[e]] (ceil(n_edges / 64) words, all written); edge_mask (may be NULL): the same
+ * as one byte per edge, the `edge_mask` k_hop_subgraph returns.
+ *   replaces `edge_mask = node_mask[row] & node_mask[col]` of k_hop_subgraph (subgraph_dataloader.py:159-162) */
+int sgp_subgraph_edge_flags(const int32_t* src, const int32_t* dst, int64_t n_edges, const uint64_t* mask,
+                            int64_t n_nodes, uint64_t* flags, uint8_t* edge_mask, sgp_stream_t stream);
+
+/* Ordered compaction of an n-bit array: the indices of the set bits ascending, and each one's exclusive rank.
+ * Three passes, no workgroup waits for another: sgp_compact_count writes the set bits of every tile of 16 384 flags to
+ * tile_offsets[sgp_compact_tiles(n)], scans them in place (exclusive, one workgroup) and writes the number of set bits
+ * to the device word `total`; sgp_compact_scatter then writes, for the r-th set bit i: idx32[r] = idx64[r] = i and
+ * rank[i] = r (each may be NULL; idx* hold n_set entries, rank n, entries of clear bits untouched).  n_set is the total
+ * the caller read back.  sgp_compact_pack_u8 turns one byte per flag (non-zero = set) into the bit array.
+ *   replaces `torch.cat(subsets).unique(return_inverse=True)` and `node_idx[subset] = torch.arange(subset.size(0))` of
+ *   k_hop_subgraph (sorted node ids, relabel table) and, on edge flags, the positions that `edge_index[:, edge_mask]`
+ *   keeps (subgraph_dataloader.py:159-164) */
+int64_t sgp_compact_tiles(int64_t n);
+int sgp_compact_pack_u8(const uint8_t* flags, int64_t n, uint64_t* bits, sgp_stream_t stream);
+int sgp_compact_count(const uint64_t* bits, int64_t n, int32_t* tile_offsets, int32_t* total, sgp_stream_t stream);
+int sgp_compact_scatter(const uint64_t* bits, int64_t n, const int32_t* tile_offsets, int64_t n_set, int32_t* idx32,
+                        int64_t* idx64, int32_t* rank, sgp_stream_t stream);
+/* The compaction's scatter on edge flags, writing the edge itself: for the r-th surviving edge e
+ *   out_src[r] = relabel[src[e]], out_dst[r] = relabel[dst[e]], out_weight[r] = weight[e] (weight pair may be NULL).
+ *   replaces `edge_index = edge_index[:, edge_mask]; edge_index = node_idx[edge_index]` of k_hop_subgraph and
+ *   `edge_weight = edge_weight[edge_mask]` (subgraph_dataloader.py:159-164) */
+int sgp_subgraph_edges(const uint64_t* flags, int64_t n_edges, const int32_t* tile_offsets, int64_t n_set,
+                       const int32_t* src, const int32_t* dst, const float* weight, const int32_t* relabel,
+                       int64_t n_nodes, int64_t* out_src, int64_t* out_dst, float* out_weight, sgp_stream_t stream);
+/* The edge cap: out[j] = edge pos[keep[j]], relabelled, j < n_keep, in keep's order.  pos [n_pos]: positions of the
+ * surviving edges (sgp_compact_scatter's idx32; NULL: every edge, n_pos = n_edges); keep NULL: j itself; relabel NULL:
+ * ids as they are.  A keep entry outside [0, n_pos) writes -1 and sets err.
+ *   replaces `edge_index = edge_index[:, keep_edges]; edge_weight = edge_weight[keep_edges]`
+ *   (subgraph_dataloader.py:184-186) */
+int sgp_subgraph_take_edges(const int32_t* src, const int32_t* dst, const float* weight, int64_t n_edges,
+                            const int32_t* pos, int64_t n_pos, const int64_t* keep, int64_t n_keep,
+                            const int32_t* relabel, int64_t n_nodes, int64_t* out_src, int64_t* out_dst,
+                            float* out_weight, int32_t* err, sgp_stream_t stream);
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

@@ -225,6 +225,16 @@ SIGNATURES = {
                                           c_f64, c_f64, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_p]),
     "sgp_gwnet_norm_bwd_f32": (ctypes.c_int, [c_i32, c_i32, c_p, c_i64, c_p, c_p, c_p, c_f64, c_u64, c_f64, c_p, c_i64,
                                               c_p, c_i64, c_p, c_p, c_i64, c_i32, c_p, c_i64, c_p]),
+    "sgp_subgraph_mark": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "sgp_subgraph_expand": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p, c_i64, c_p]),
+    "sgp_subgraph_edge_flags": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p]),
+    "sgp_compact_tiles": (c_i64, [c_i64]),
+    "sgp_compact_pack_u8": (ctypes.c_int, [c_p, c_i64, c_p, c_p]),
+    "sgp_compact_count": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p]),
+    "sgp_compact_scatter": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "sgp_subgraph_edges": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "sgp_subgraph_take_edges": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p,
+                                               c_p, c_p, c_p]),
     "sgp_event_create": (ctypes.c_int, [ctypes.POINTER(c_p)]),
     "sgp_event_destroy": (ctypes.c_int, [c_p]),
     "sgp_event_record": (ctypes.c_int, [c_p, c_p]),
@@ -1028,6 +1038,159 @@ def gather_rows(x, step_index, node_index):
     _check(lib.sgp_gather_rows_f32(xp, xrs, xbs, step_index.data_ptr(), node_index.data_ptr(), K,
                                    out.data_ptr(), D, 0, 1, D, _stream(x)), "sgp_gather_rows_f32")
     return out
+
+
+# ---------------------------------------------------------------- k-hop subgraph sampling (subgraph.hip)
+def _flat(t, name, dtype, numel=None):
+    """1-D contiguous CUDA tensor of ``dtype`` (and at least ``numel`` entries) -> its pointer."""
+    if t.dtype != dtype or not t.is_cuda or t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous 1-D {dtype} CUDA tensor, got {tuple(t.shape)} {t.dtype} {t.device}")
+    if numel is not None and t.numel() < numel:
+        raise ValueError(f"{name}: {t.numel()} entries, {numel} needed")
+    return t.data_ptr()
+
+
+def mask_words(n):
+    """64-bit words of an ``n``-bit mask (never 0, so that an empty mask still has a pointer)."""
+    return max(1, (int(n) + 63) // 64)
+
+
+def compact_tiles(n):
+    """Entries of the compaction's tile table for ``n`` flags (never 0)."""
+    return max(1, load().sgp_compact_tiles(int(n)))
+
+
+def _edges(src, dst, weight=None):
+    E = src.numel()
+    sp, dp = _flat(src, "src", torch.int32), _flat(dst, "dst", torch.int32, E)
+    wp = None if weight is None else _flat(weight, "weight", torch.float32, E)
+    return E, sp, dp, wp
+
+
+@_on_device
+def subgraph_mark(ids, mask, n_nodes, err=None):
+    """Set the bits of ``ids`` (int32) in ``mask`` (int64 words, cleared by the caller)."""
+    lib = require_gpu()
+    _check(lib.sgp_subgraph_mark(_flat(ids, "ids", torch.int32), ids.numel(),
+                                 _flat(mask, "mask", torch.int64, mask_words(n_nodes)), int(n_nodes),
+                                 None if err is None else _flat(err, "err", torch.int32, 1), _stream(mask)),
+           "sgp_subgraph_mark")
+    return mask
+
+
+@_on_device
+def subgraph_expand(src, dst, mask_in, mask_out, n_nodes):
+    """One hop: ``mask_out = mask_in | {dst[e] : src[e] in mask_in}`` (two different buffers)."""
+    lib = require_gpu()
+    E, sp, dp, _ = _edges(src, dst)
+    words = mask_words(n_nodes)
+    _check(lib.sgp_subgraph_expand(sp, dp, E, _flat(mask_in, "mask_in", torch.int64, words),
+                                   _flat(mask_out, "mask_out", torch.int64, words), int(n_nodes), _stream(mask_in)),
+           "sgp_subgraph_expand")
+    return mask_out
+
+
+@_on_device
+def subgraph_edge_flags(src, dst, mask, n_nodes, flags, edge_mask=None):
+    """``flags`` bit e = both endpoints of edge e in ``mask``; ``edge_mask`` (bool [E], optional): the same per edge."""
+    lib = require_gpu()
+    E, sp, dp, _ = _edges(src, dst)
+    _check(lib.sgp_subgraph_edge_flags(sp, dp, E, _flat(mask, "mask", torch.int64, mask_words(n_nodes)), int(n_nodes),
+                                       _flat(flags, "flags", torch.int64, mask_words(E)),
+                                       None if edge_mask is None else _flat(edge_mask, "edge_mask", torch.bool, E),
+                                       _stream(mask)), "sgp_subgraph_edge_flags")
+    return flags
+
+
+@_on_device
+def compact_pack(flags, bits=None):
+    """Bit array (int64 words) of a bool / uint8 flag vector."""
+    lib = require_gpu()
+    n = flags.numel()
+    if flags.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"flags: expected bool or uint8, got {flags.dtype}")
+    if bits is None:
+        bits = torch.empty(mask_words(n), dtype=torch.int64, device=flags.device)
+    _check(lib.sgp_compact_pack_u8(_flat(flags, "flags", flags.dtype), n, _flat(bits, "bits", torch.int64, mask_words(n)),
+                                   _stream(flags)), "sgp_compact_pack_u8")
+    return bits
+
+
+@_on_device
+def compact_count(bits, n, tile_offsets, total):
+    """Passes 1 and 2 of the ordered compaction: per-tile counts, scanned in place; the number of set bits goes to
+    the device word ``total`` (a 1-element int32 view).  No sync."""
+    lib = require_gpu()
+    _check(lib.sgp_compact_count(_flat(bits, "bits", torch.int64, mask_words(n)), int(n),
+                                 _flat(tile_offsets, "tile_offsets", torch.int32, compact_tiles(n)),
+                                 _flat(total, "total", torch.int32, 1), _stream(bits)), "sgp_compact_count")
+
+
+@_on_device
+def compact_scatter(bits, n, tile_offsets, n_set, idx32=None, idx64=None, rank=None):
+    """Pass 3: the r-th set bit i gives ``idx32[r] = idx64[r] = i`` and ``rank[i] = r``."""
+    lib = require_gpu()
+    n_set = int(n_set)
+    _check(lib.sgp_compact_scatter(_flat(bits, "bits", torch.int64, mask_words(n)), int(n),
+                                   _flat(tile_offsets, "tile_offsets", torch.int32, compact_tiles(n)), n_set,
+                                   None if idx32 is None else _flat(idx32, "idx32", torch.int32, n_set),
+                                   None if idx64 is None else _flat(idx64, "idx64", torch.int64, n_set),
+                                   None if rank is None else _flat(rank, "rank", torch.int32, n),
+                                   _stream(bits)), "sgp_compact_scatter")
+
+
+def compact(flags):
+    """``(idx, rank, count)`` of a bool vector on the device: ``idx`` the int64 positions of the set flags, ascending
+    (``torch.nonzero``), ``rank`` int32 [n] the exclusive rank at every set flag (other entries -1).  One host sync."""
+    n = flags.numel()
+    bits = compact_pack(flags)
+    tiles = torch.empty(compact_tiles(n), dtype=torch.int32, device=flags.device)
+    total = torch.zeros(1, dtype=torch.int32, device=flags.device)
+    compact_count(bits, n, tiles, total)
+    count = int(total.item())
+    idx = torch.empty(count, dtype=torch.int64, device=flags.device)
+    rank = torch.full((n,), -1, dtype=torch.int32, device=flags.device)
+    compact_scatter(bits, n, tiles, count, idx64=idx, rank=rank)
+    return idx, rank, count
+
+
+@_on_device
+def subgraph_edges(flags, tile_offsets, n_set, src, dst, weight, relabel, n_nodes, out_index, out_weight=None):
+    """The compaction's scatter on edge flags: the surviving edges, relabelled, to ``out_index`` (int64 [2, n_set])
+    and their weights to ``out_weight``, in edge order."""
+    lib = require_gpu()
+    E, sp, dp, wp = _edges(src, dst, weight if out_weight is not None else None)
+    n_set = int(n_set)
+    if out_index.dtype != torch.int64 or tuple(out_index.shape) != (2, n_set) or not out_index.is_contiguous():
+        raise ValueError(f"out_index: expected contiguous int64 [2, {n_set}], got {tuple(out_index.shape)} {out_index.dtype}")
+    _check(lib.sgp_subgraph_edges(_flat(flags, "flags", torch.int64, mask_words(E)), E,
+                                  _flat(tile_offsets, "tile_offsets", torch.int32, compact_tiles(E)), n_set, sp, dp, wp,
+                                  _flat(relabel, "relabel", torch.int32, n_nodes), int(n_nodes),
+                                  _flat(out_index[0], "out_index", torch.int64), _flat(out_index[1], "out_index", torch.int64),
+                                  None if out_weight is None else _flat(out_weight, "out_weight", torch.float32, n_set),
+                                  _stream(flags)), "sgp_subgraph_edges")
+    return out_index
+
+
+@_on_device
+def subgraph_take_edges(src, dst, weight, pos, keep, n_keep, relabel, n_nodes, out_index, out_weight=None, err=None):
+    """The edge cap: ``out[:, j]`` = edge ``pos[keep[j]]`` relabelled (``pos`` None: all edges; ``keep`` None: the
+    first ``n_keep``; ``relabel`` None: ids as they are), in ``keep``'s order."""
+    lib = require_gpu()
+    E, sp, dp, wp = _edges(src, dst, weight if out_weight is not None else None)
+    n_keep = int(n_keep)
+    n_pos = E if pos is None else pos.numel()
+    if out_index.dtype != torch.int64 or tuple(out_index.shape) != (2, n_keep) or not out_index.is_contiguous():
+        raise ValueError(f"out_index: expected contiguous int64 [2, {n_keep}], got {tuple(out_index.shape)} {out_index.dtype}")
+    _check(lib.sgp_subgraph_take_edges(sp, dp, wp, E, None if pos is None else _flat(pos, "pos", torch.int32), n_pos,
+                                       None if keep is None else _flat(keep, "keep", torch.int64, n_keep), n_keep,
+                                       None if relabel is None else _flat(relabel, "relabel", torch.int32, n_nodes),
+                                       int(n_nodes), _flat(out_index[0], "out_index", torch.int64),
+                                       _flat(out_index[1], "out_index", torch.int64),
+                                       None if out_weight is None else _flat(out_weight, "out_weight", torch.float32, n_keep),
+                                       None if err is None else _flat(err, "err", torch.int32, 1), _stream(src)),
+           "sgp_subgraph_take_edges")
+    return out_index
 
 
 GL_ACT_CODES = {None: 0, "linear": 0, "identity": 0, "relu": 1, "silu": 2}
