@@ -670,6 +670,18 @@ int sgp_grouped_linear_wgrad_f32(const float* X, int64_t x_row_stride, int64_t x
                                  const float* dz, float* dw,
                                  int32_t n_rows, int32_t groups, int32_t ic, int32_t oc,
                                  sgp_stream_t stream);
+/* Which kernel form a launch takes -- host-only queries; the entries dispatch on these same answers (NULL outputs are
+ * skipped; SGP_EINVAL on a bad size).
+ * sgp_grouped_linear_form: jtc = 16-channel output tiles a wave accumulates together (1, 2, or 4: oc <= 16, <= 32,
+ * more -- above 64 channels the wave makes further trips of 4 tiles, the last one partial when ceil(oc / 16) % 4 != 0;
+ * above ic = 128 it makes further trips of 8 k-blocks); xvec = 1 when a lane reads its row piece with one 16-byte load:
+ * ic % 4 == 0, both strides multiples of 4 floats and x_aligned16 (X on a 16-byte boundary), 0 = four scalar loads.
+ * sgp_grouped_linear_wgrad_form: the row slices of sgp_grouped_linear_wgrad_f32 (slices = ceil(n_rows / rows_per_slice),
+ * 0 without rows; every slice but the last has rows_per_slice rows, a multiple of 16 that is at least 64). */
+int sgp_grouped_linear_form(int32_t ic, int32_t oc, int64_t x_row_stride, int64_t x_batch_stride, int32_t x_aligned16,
+                            int32_t* jtc, int32_t* xvec);
+int sgp_grouped_linear_wgrad_form(int32_t n_rows, int32_t groups, int32_t ic, int32_t oc,
+                                  int32_t* rows_per_slice, int32_t* slices);
 
 /* ---------------------------------------------------------- Ridge readout ---
  * The closed-form baseline's readout (experiments/run_closed_form.py:169-247): sklearn Ridge(alpha) fitted once per
@@ -749,10 +761,19 @@ int sgp_dense_f32(const float* X, int64_t x_row_stride, const int32_t* gather, i
                   float* pre, int64_t pre_row_stride, double dropout_p, uint64_t seed, int64_t drop_width,
                   const float* add, int64_t add_row_stride,
                   float* out, const int64_t* out_map, sgp_stream_t stream);
+/* The form sgp_dense_f32 launches for these sizes -- a host-only query; the entry dispatches on this same answer (NULL
+ * outputs are skipped; SGP_EINVAL on a bad size).  rows_per_wg: 128 when ceil(n_rows / 128) * ceil(n_out / 64) >= 512
+ * workgroups (two per CU), 64 otherwise; xvec = 1 when a lane reads its row piece with one 16-byte load: k % 4 == 0,
+ * x_row_stride % 4 == 0 and x_aligned16 (X on a 16-byte boundary), 0 = four scalar loads. */
+int sgp_dense_form(int32_t n_rows, int32_t n_out, int32_t k, int64_t x_row_stride, int32_t x_aligned16,
+                   int32_t* rows_per_wg, int32_t* xvec);
 
 /* dw[o * dw_row_stride + i] = sum_r dZ[r * dz_row_stride + o] * X_row(r)[i] and (db != NULL) db[o] = sum_r dZ[r, o],
  * X_row as in sgp_dense_f32.  Row slices write partials into `work` (sgp_dense_wgrad_workspace_floats floats,
- * with_bias = db != NULL), added in slice order in fp64: no float atomics, bit-identical from run to run.
+ * with_bias = db != NULL), added in slice order in fp64: no float atomics, bit-identical from run to run.  With
+ * kp = k + with_bias there are workspace_floats / (n_out * kp) slices of rows_per_slice =
+ * max(64, ceil(n_rows / max(1, 2048 / (ceil(n_out / 64) * ceil(kp / 64))))) rows rounded up to a multiple of 16
+ * (integer divisions; the last slice may be shorter; one empty slice without rows).
  *   replaces the weight / bias gradients autograd forms for every nn.Linear of the decoder */
 int64_t sgp_dense_wgrad_workspace_floats(int64_t n_rows, int32_t n_out, int32_t k, int32_t with_bias);
 int sgp_dense_wgrad_f32(const float* dZ, int64_t dz_row_stride, const float* X, int64_t x_row_stride,

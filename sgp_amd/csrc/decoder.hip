@@ -266,15 +266,40 @@ int sgp_grouped_linear_fwd_f32(const float* X, int64_t x_row_stride, int64_t x_b
     a.out = out; a.ors = out_row_stride; a.pre = pre;
     set_dropout(a.drop_thresh, a.seed_lo, a.seed_hi, a.keep_scale, dropout_p, seed);
     a.n_rows = n_rows; a.groups = groups; a.ic = ic; a.oc = oc; a.act = act;
-    a.xvec = ic % 4 == 0 && x_row_stride % 4 == 0 && x_batch_stride % 4 == 0 && sgp::aligned16(X);
+    int32_t jtc, xvec;
+    sgp_grouped_linear_form(ic, oc, x_row_stride, x_batch_stride, sgp::aligned16(X) ? 1 : 0, &jtc, &xvec);   // sizes checked above
+    a.xvec = xvec != 0;
     const int grid = (n_rows + 15) / 16;
-    const int JT = (oc + 15) / 16;
     hipStream_t s = (hipStream_t)stream;
     SGP_REQUIRE(groups <= 65535, "sgp_grouped_linear_f32: more than 65535 groups");
-    if (JT == 1) hipLaunchKernelGGL(grouped_linear<1>, dim3(grid, groups), dim3(64), 0, s, a);
-    else if (JT == 2) hipLaunchKernelGGL(grouped_linear<2>, dim3(grid, groups), dim3(64), 0, s, a);
+    if (jtc == 1) hipLaunchKernelGGL(grouped_linear<1>, dim3(grid, groups), dim3(64), 0, s, a);
+    else if (jtc == 2) hipLaunchKernelGGL(grouped_linear<2>, dim3(grid, groups), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(grouped_linear<4>, dim3(grid, groups), dim3(64), 0, s, a);
     return sgp::check_launch("grouped_linear");
+}
+
+int sgp_grouped_linear_form(int32_t ic, int32_t oc, int64_t x_row_stride, int64_t x_batch_stride, int32_t x_aligned16,
+                            int32_t* jtc, int32_t* xvec) {
+    SGP_REQUIRE(ic > 0 && oc > 0, "sgp_grouped_linear_form: bad size");
+    const int JT = (oc + 15) / 16;
+    if (jtc) *jtc = JT == 1 ? 1 : (JT == 2 ? 2 : 4);
+    if (xvec) *xvec = (ic % 4 == 0 && x_row_stride % 4 == 0 && x_batch_stride % 4 == 0 && x_aligned16) ? 1 : 0;
+    return 0;
+}
+
+int sgp_grouped_linear_wgrad_form(int32_t n_rows, int32_t groups, int32_t ic, int32_t oc,
+                                  int32_t* rows_per_slice, int32_t* slices) {
+    SGP_REQUIRE(n_rows >= 0 && groups > 0 && ic > 0 && oc > 0, "sgp_grouped_linear_wgrad_form: bad size");
+    const long long tiles = (long long)groups * ((ic + 15) / 16) * ((oc + 15) / 16);
+    // enough row slices to fill the chip, each at least 64 rows (a multiple of 16)
+    long long want = 4096 / (tiles < 1 ? 1 : tiles);
+    if (want < 1) want = 1;
+    long long rps = (n_rows + want - 1) / want;
+    if (rps < 64) rps = 64;
+    rps = (rps + 15) / 16 * 16;
+    if (rows_per_slice) *rows_per_slice = (int32_t)rps;
+    if (slices) *slices = (int32_t)((n_rows + rps - 1) / rps);
+    return 0;
 }
 
 int sgp_grouped_linear_dact_f32(const float* dy, int64_t dy_row_stride, const float* pre, int32_t act,
@@ -320,14 +345,9 @@ int sgp_grouped_linear_wgrad_f32(const float* X, int64_t x_row_stride, int64_t x
     a.dz = dz; a.dw = dw; a.n_rows = n_rows; a.groups = groups; a.ic = ic; a.oc = oc;
     const long long tiles = (long long)groups * ((ic + 15) / 16) * ((oc + 15) / 16);
     SGP_REQUIRE(tiles < (1ll << 31), "sgp_grouped_linear_wgrad_f32: too many tiles");
-    // enough row slices to fill the chip, each at least 64 rows (a multiple of 16)
-    long long slices = 4096 / (tiles < 1 ? 1 : tiles);
-    if (slices < 1) slices = 1;
-    long long rps = (n_rows + slices - 1) / slices;
-    if (rps < 64) rps = 64;
-    rps = (rps + 15) / 16 * 16;
-    a.rows_per_slice = (int)rps;
-    const long long ny = (n_rows + rps - 1) / rps;
+    int32_t rps, ny;
+    sgp_grouped_linear_wgrad_form(n_rows, groups, ic, oc, &rps, &ny);    // sizes checked above
+    a.rows_per_slice = rps;
     SGP_REQUIRE(ny <= 65535, "sgp_grouped_linear_wgrad_f32: too many row slices");
     hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)tiles, (unsigned)ny), dim3(64), 0, s, a);
     return sgp::check_launch("grouped_linear_wgrad");

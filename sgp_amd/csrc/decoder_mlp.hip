@@ -369,15 +369,26 @@ int sgp_dense_f32(const float* X, int64_t x_row_stride, const int32_t* gather, i
     a.add = add; a.add_rs = add_row_stride; a.out = out;
     a.o_rdiv = out_map[0]; a.o_r0 = out_map[1]; a.o_r1 = out_map[2];
     a.o_cdiv = out_map[3]; a.o_c0 = out_map[4]; a.o_c1 = out_map[5];
-    a.xvec = k % 4 == 0 && x_row_stride % 4 == 0 && sgp::aligned16(X);
+    int32_t rows_per_wg, xvec;
+    sgp_dense_form(n_rows, n_out, k, x_row_stride, sgp::aligned16(X) ? 1 : 0, &rows_per_wg, &xvec);   // sizes checked above
+    a.xvec = xvec != 0;
     const int gy = (n_out + 16 * DN_JT - 1) / (16 * DN_JT);
     SGP_REQUIRE(gy <= 65535, "sgp_dense_f32: too many output columns");
     hipStream_t s = (hipStream_t)stream;
-    // 128 rows per workgroup when that still gives the chip two workgroups per CU, 64 otherwise
-    const long long g128 = (n_rows + 127) / 128;
-    if (g128 * gy >= 512) hipLaunchKernelGGL(dense_kernel<2>, dim3((unsigned)g128, gy), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(dense_kernel<1>, dim3((unsigned)((n_rows + 63) / 64), gy), dim3(256), 0, s, a);
+    const unsigned gx = (unsigned)(((long long)n_rows + rows_per_wg - 1) / rows_per_wg);
+    if (rows_per_wg == 128) hipLaunchKernelGGL(dense_kernel<2>, dim3(gx, gy), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(dense_kernel<1>, dim3(gx, gy), dim3(256), 0, s, a);
     return sgp::check_launch("dense");
+}
+
+int sgp_dense_form(int32_t n_rows, int32_t n_out, int32_t k, int64_t x_row_stride, int32_t x_aligned16,
+                   int32_t* rows_per_wg, int32_t* xvec) {
+    SGP_REQUIRE(n_rows >= 0 && k > 0 && n_out > 0 && x_row_stride >= k, "sgp_dense_form: bad size");
+    // 128 rows per workgroup when that still gives the chip two workgroups per CU, 64 otherwise
+    const long long g128 = ((long long)n_rows + 127) / 128, gy = (n_out + 16 * DN_JT - 1) / (16 * DN_JT);
+    if (rows_per_wg) *rows_per_wg = g128 * gy >= 512 ? 128 : 64;
+    if (xvec) *xvec = (k % 4 == 0 && x_row_stride % 4 == 0 && x_aligned16) ? 1 : 0;
+    return 0;
 }
 
 int64_t sgp_dense_wgrad_workspace_floats(int64_t n_rows, int32_t n_out, int32_t k, int32_t with_bias) {

@@ -131,6 +131,8 @@ SIGNATURES = {
     "sgp_grouped_linear_transpose_f32": (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_p]),
     "sgp_grouped_linear_wgrad_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p,
                                                     c_i32, c_i32, c_i32, c_i32, c_p]),
+    "sgp_grouped_linear_form": (ctypes.c_int, [c_i32, c_i32, c_i64, c_i64, c_i32, c_p, c_p]),
+    "sgp_grouped_linear_wgrad_form": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
     "sgp_abs_max_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_p, c_p]),
     "sgp_spmm_split_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_p, c_i64, c_i64,
                                           c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_i64,
@@ -178,6 +180,7 @@ SIGNATURES = {
     "sgp_dense_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i32, c_i32, c_i32,
                                      c_i32, c_i32, c_i32, c_p, c_i64, c_p, c_i64, c_f64, c_u64, c_i64,
                                      c_p, c_i64, c_p, c_p, c_p]),
+    "sgp_dense_form": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i64, c_i32, c_p, c_p]),
     "sgp_dense_wgrad_workspace_floats": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
     "sgp_dense_wgrad_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_i32,
                                            c_p, c_i64, c_p, c_p, c_i64, c_p]),
@@ -1241,6 +1244,9 @@ def grouped_linear_dact(dy, pre, activation, dropout_p=0., seed=0):
     lib = require_gpu()
     if dy.dim() != 2 or dy.stride(1) != 1:
         dy = dy.contiguous()
+    if pre.dim() != 2 or pre.dtype != torch.float32 or not pre.is_contiguous():
+        raise ValueError(f"pre: expected a contiguous 2-D float32 tensor (the kernel indexes pre and dz flat), got "
+                         f"{tuple(pre.shape)} {pre.dtype} strides {pre.stride()}")
     dz = torch.empty_like(pre)
     _check(lib.sgp_grouped_linear_dact_f32(dy.data_ptr(), dy.stride(0), pre.data_ptr(), GL_ACT_CODES[activation],
                                            float(dropout_p), int(seed), dz.data_ptr(), pre.shape[0], pre.shape[1],
@@ -1265,10 +1271,33 @@ def grouped_linear_wgrad(x2, dz, groups, ic, oc, step_index=None, node_index=Non
     """dW[groups*oc, ic] = sum over rows of dz[row, g*oc + o] * x[row, g*ic + i]."""
     lib = require_gpu()
     xp, xrs, xbs, K, sp, np_, dev = _gl_rows(x2, step_index, node_index, source)
+    if dz.dim() != 2 or dz.dtype != torch.float32 or not dz.is_cuda or not dz.is_contiguous() \
+            or tuple(dz.shape) != (K, groups * oc):
+        raise ValueError(f"dz: expected a contiguous float32 CUDA tensor [{K}, {groups * oc}], got "
+                         f"{tuple(dz.shape)} {dz.dtype} {dz.device} strides {dz.stride()}")
+    if K == 0:                                                          # (tensors without elements have no address to hand over)
+        return torch.zeros(groups * oc, ic, dtype=torch.float32, device=dev)
     dw = torch.empty(groups * oc, ic, dtype=torch.float32, device=dev)
     _check(lib.sgp_grouped_linear_wgrad_f32(xp, xrs, xbs, sp, np_, dz.data_ptr(), dw.data_ptr(),
                                             K, groups, ic, oc, _stream(dw)), "sgp_grouped_linear_wgrad_f32")
     return dw
+
+
+def grouped_linear_form(ic, oc, x_row_stride, x_batch_stride=0, aligned=True):
+    """``(output tiles per trip: 1, 2 or 4; 1 = 16-byte row loads, 0 = scalar loads)`` of the ``sgp_grouped_linear_fwd_f32``
+    launch for these operands (host only: ``sgp_grouped_linear_form``)."""
+    jtc, xvec = c_i32(0), c_i32(0)
+    _check(load().sgp_grouped_linear_form(int(ic), int(oc), int(x_row_stride), int(x_batch_stride), int(bool(aligned)),
+                                          ctypes.addressof(jtc), ctypes.addressof(xvec)), "sgp_grouped_linear_form")
+    return jtc.value, xvec.value
+
+
+def grouped_linear_wgrad_form(n_rows, groups, ic, oc):
+    """``(rows per slice, slices)`` of ``sgp_grouped_linear_wgrad_f32`` (host only)."""
+    rps, ns = c_i32(0), c_i32(0)
+    _check(load().sgp_grouped_linear_wgrad_form(int(n_rows), int(groups), int(ic), int(oc), ctypes.addressof(rps),
+                                                ctypes.addressof(ns)), "sgp_grouped_linear_wgrad_form")
+    return rps.value, ns.value
 
 
 # ---------------------------------------------------------------- decoder MLP / readout (decoder_mlp.hip)
@@ -1283,7 +1312,28 @@ def _rows2(t, name, width):
                          f"{tuple(t.shape)} {t.dtype} {t.device} strides {t.stride()}")
     if t.shape[1] < width:
         raise ValueError(f"{name}: {t.shape[1]} columns, {width} needed")
+    if t.shape[0] > 1 and t.stride(0) < width:
+        raise ValueError(f"{name}: rows {t.stride(0)} floats apart overlap at {width} columns (an expanded view?); "
+                         f"pass a tensor with its own rows")
     return t.data_ptr(), max(t.stride(0), width)
+
+
+def dense_form(n_rows, n_out, k, x_row_stride=None, aligned=True):
+    """``(rows per workgroup: 64 or 128; 1 = 16-byte row loads, 0 = scalar loads)`` of the ``sgp_dense_f32`` launch for
+    these operands (host only: ``sgp_dense_form``)."""
+    rows, xvec = c_i32(0), c_i32(0)
+    _check(load().sgp_dense_form(int(n_rows), int(n_out), int(k), int(k if x_row_stride is None else x_row_stride),
+                                 int(bool(aligned)), ctypes.addressof(rows), ctypes.addressof(xvec)), "sgp_dense_form")
+    return rows.value, xvec.value
+
+
+def dense_wgrad_slices(n_rows, n_out, k, bias=True):
+    """Row slices of the ``sgp_dense_wgrad_f32`` launch (host only: its workspace holds one partial per slice)."""
+    kp = k + int(bool(bias))
+    nw = load().sgp_dense_wgrad_workspace_floats(int(n_rows), int(n_out), int(k), int(bool(bias)))
+    if nw < 0:
+        raise ValueError("dense_wgrad_slices: bad size")
+    return nw // (n_out * kp)
 
 
 @_on_device
@@ -1352,6 +1402,8 @@ def row_segsum(g, n_seg, perm=None, keys=None):
     """[n_seg, width] per-node sums of the rows of g (strided over the batch, or along stably sorted keys)."""
     lib = require_gpu()
     gp, grs = _rows2(g, "g", g.shape[1])
+    if g.shape[0] == 0:                                                 # no rows (and no address): every node's sum is 0
+        return torch.zeros(n_seg, g.shape[1], dtype=torch.float32, device=g.device)
     out = torch.empty(n_seg, g.shape[1], dtype=torch.float32, device=g.device)
     _check(lib.sgp_row_segsum_f32(gp, grs, g.shape[0], g.shape[1], _ptr(perm), _ptr(keys), n_seg, out.data_ptr(),
                                   _stream(g)), "sgp_row_segsum_f32")
@@ -1362,6 +1414,9 @@ def row_segsum(g, n_seg, perm=None, keys=None):
 def masked_mae(y_hat, y, mask=None, mask_nans=False):
     """(loss [] float32, count [1] float64) of MaskedMAE over contiguous float32 tensors of one shape."""
     lib = require_gpu()
+    if not y_hat.numel():                                               # nothing counts: 0, as tsl's MaskedMetric.compute
+        return (torch.zeros((), dtype=torch.float32, device=y_hat.device),
+                torch.zeros(1, dtype=torch.float64, device=y_hat.device))
     loss = torch.empty((), dtype=torch.float32, device=y_hat.device)
     count = torch.empty(1, dtype=torch.float64, device=y_hat.device)
     _check(lib.sgp_masked_mae_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), y_hat.numel(), int(mask_nans),
@@ -1373,6 +1428,8 @@ def masked_mae(y_hat, y, mask=None, mask_nans=False):
 def masked_mae_bwd(y_hat, y, mask, mask_nans, grad_out, count):
     lib = require_gpu()
     grad = torch.empty_like(y_hat)
+    if not y_hat.numel():
+        return grad
     _check(lib.sgp_masked_mae_bwd_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), y_hat.numel(), int(mask_nans),
                                       grad_out.data_ptr(), count.data_ptr(), grad.data_ptr(), _stream(grad)),
            "sgp_masked_mae_bwd_f32")

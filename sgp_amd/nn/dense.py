@@ -83,6 +83,13 @@ def dev(t, device):
     return t.detach().to(device, torch.float32)
 
 
+def rows2d(t):
+    """``t [rows, width]`` as the dense kernels take it: unit column stride and rows that do not overlap.  Autograd
+    hands expanded gradients over (``stride(0) == 0``: every row is the same memory); those are copied."""
+    ok = (t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
+    return t if ok else t.contiguous()
+
+
 def seed():
     """A fresh 63-bit dropout seed from torch's default generator."""
     return int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -175,7 +182,7 @@ class PositionalFn(torch.autograd.Function):
     def backward(ctx, dy):
         emb, gather = ctx.saved_tensors
         bwd, n_out, k, row_mod, n_tokens, edev, wdev, bdev = ctx.cfg
-        dy = dy if dy.stride(1) == 1 else dy.contiguous()
+        dy = rows2d(dy)
         dw, db = hip.dense_wgrad(dy, emb, n_out, k, gather=gather, row_mod=row_mod)
         demb = None
         if ctx.needs_input_grad[1]:

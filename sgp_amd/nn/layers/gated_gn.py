@@ -241,8 +241,6 @@ class GatedGraphNetwork(nn.Module):
         n = x.shape[-2]
         lead = x.shape[:-2]
         plan = plan_for(edge_index, n, x.device)
-        rows = x.float().reshape(-1, self.in_channels)
-        if rows.stride(1) != 1:
-            rows = rows.contiguous()
+        rows = dense.rows2d(x.float().reshape(-1, self.in_channels))
         y = self._rows(rows, plan, rows.shape[0] // n).reshape(*lead, n, self.out_channels)
         return y.cpu() if on_cpu else y

@@ -70,7 +70,7 @@ class _TConvFn(torch.autograd.Function):
         ctx.used = True
         x, act = ctx.saved_tensors
         taps, M, d, H, Kt, R, wdev, bdev = ctx.cfg
-        dy = dy if dy.stride(1) == 1 else dy.contiguous()
+        dy = dense.rows2d(dy)
         dz = hip.gwnet_tconv_bwd(dy, act, H)
         dwm = torch.empty(2 * H, Kt * H, dtype=torch.float32, device=x.device)
         db = None
@@ -275,7 +275,7 @@ class SpatialConvOrderK(nn.Module):
             raise ValueError(f"support: expected [{n}, {n}], got {tuple(support.shape)}")
         x, on_cpu = hip.to_gpu(x)
         A = support.to(x.device, torch.float32)
-        A = A if A.stride(1) == 1 else A.contiguous()
+        A = dense.rows2d(A)
         rows = x.float().reshape(-1, self.input_size)
         y = spatial_conv(rows, n, spatial_packs(self._packs, "mlp", None, self.mlp, x.device), A=A, mlp=self.mlp,
                          order=self.order)
@@ -306,7 +306,7 @@ class _AdjFn(torch.autograd.Function):
         logits, A, esg, etg, idx = ctx.saved_tensors
         n_tokens, sdev, tdev = ctx.cfg
         n, emb = esg.shape
-        dL = hip.row_softmax_bwd(A, dA if dA.stride(1) == 1 else dA.contiguous(), logits)
+        dL = hip.row_softmax_bwd(A, dense.rows2d(dA), logits)
         des = hip.dense(dL, hip.dense_pack(etg, transpose=True), emb, n)
         det, _ = hip.dense_wgrad(dL, esg, n, emb, bias=False)
         if idx is not None:
@@ -334,8 +334,8 @@ class _NormFn(torch.autograd.Function):
         rm = rv = None
         if running is not None:
             rm, rv = (t if t.is_cuda else t.to(dev) for t in running)
-        res = res if (res is None or res.stride(1) == 1) else res.contiguous()
-        out, z, stats = hip.gwnet_norm(y if y.stride(1) == 1 else y.contiguous(), res, kind, training, wd, bd, rm, rv,
+        res = res if res is None else dense.rows2d(res)
+        out, z, stats = hip.gwnet_norm(dense.rows2d(y), res, kind, training, wd, bd, rm, rv,
                                        momentum, eps, p, seed, save=save)
         if running is not None and training:
             for t, d in zip(running, (rm, rv)):

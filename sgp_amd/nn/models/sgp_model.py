@@ -251,9 +251,7 @@ class SGPModel(nn.Module):
         x, on_cpu = hip.to_gpu(x)
         b, n = x.shape[0], x.shape[1]
         if self.fully_connected:
-            rows = x.float().reshape(b * n, x.shape[-1])
-            if rows.stride(1) != 1:
-                rows = rows.contiguous()
+            rows = dense.rows2d(x.float().reshape(b * n, x.shape[-1]))
             h = self._fc_input(rows, None, b * n)
         else:
             h = self.input_encoder[1](x).reshape(b * n, self.out_channels)
