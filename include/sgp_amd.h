@@ -800,6 +800,66 @@ int sgp_masked_mae_bwd_f32(const float* y_hat, const float* y, const uint8_t* ma
                            const float* grad_out, const double* count, float* grad, sgp_stream_t stream);
 
 
+/* ------------------------------------------------ Training step: optimizer, losses, metrics -----
+ * train.hip.  Every reduction adds fixed partials in a fixed order in fp64: no float atomics, bit-identical from
+ * run to run.
+ *
+ * Chunk table (device memory, int64 [n_chunks][3]): (tensor id, element offset, length).  A chunk lies inside one
+ * tensor; tensor t's base addresses are params[t], grads[t], exp_avg[t], exp_avg_sq[t] of four DEVICE pointer arrays.
+ * The kernels take any chunk length (sgp_amd/optim.py cuts 2048 elements) and any 4-byte aligned base: a chunk is a
+ * head of up to 3 scalars, 16-byte vectors, and a tail.
+ *
+ * norm_f32[0] (and norm_f64[0] when not NULL) = sqrt(sum of g^2 over every chunk): one workgroup per chunk writes
+ * partial[chunk] (fp64, n_chunks doubles), one workgroup adds them.  0 without chunks.
+ *   replaces the norm of torch.nn.utils.clip_grad_norm_ (gradient_clip_val of the reference's trainers) */
+int sgp_multi_sqnorm_f32(const int64_t* table, int64_t n_chunks, const float* const* grads, double* partial,
+                         float* norm_f32, double* norm_f64, sgp_stream_t stream);
+
+/* One Adam step (torch.optim.adam._single_tensor_adam, no amsgrad, no maximize) over the table, one launch:
+ *   max_norm > 0:  g *= min(1, max_norm / (norm[0] + 1e-6)) -- clip_grad_norm_'s coefficient, read from the device;
+ *                  a non-finite norm propagates as in torch.  The clipped gradient is NOT written back.
+ *                  max_norm <= 0: no clip, norm may be NULL.
+ *   decoupled = 0: g += weight_decay * p (Adam);  decoupled = 1: p *= 1 - lr * weight_decay (AdamW)
+ *   m += (1 - beta1) (g - m);  v = beta2 v + (1 - beta2) g^2
+ *   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps),  step >= 1 the number of THIS step.
+ * Every hyper-parameter is passed by value (a scheduler needs no device write).
+ *   replaces torch.optim.Adam.step and the in-place scaling of clip_grad_norm_ */
+int sgp_adam_step_f32(const int64_t* table, int64_t n_chunks, float* const* params, const float* const* grads,
+                      float* const* exp_avg, float* const* exp_avg_sq, const float* norm, double max_norm,
+                      double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                      int32_t decoupled, sgp_stream_t stream);
+
+/* state[h][0..5] += per horizon step h of contiguous y_hat, y [batch, horizon, nodes, channels] (mask: uint8 of the
+ * same shape, NULL = all valid), with d = y_hat' - y and y_hat' = y_hat * (scale + 5e-8) + bias (scale, bias NULL =
+ * y_hat; element (n, c) at n * sc_node_stride + c -- tsl ScalerModule.inverse_transform_tensor):
+ *   0: sum |d|   1: their number   2: sum d^2 (over the elements of 1)   5: sum y (over the elements of 1)
+ *   3: sum |d / y|   4: their number
+ * An element enters 0 / 1 / 2 / 5 when the mask keeps it and, with mask_nans, |d| is not NaN and, with mask_inf, not
+ * infinite; it enters 3 / 4 when the mask keeps it, |d / y| is finite-or-NaN (MaskedMAPE: mask_inf always) and, with
+ * mask_nans, not NaN -- MaskedMetric._check_mask on the metric's own value.  `work`: at least
+ * sgp_masked_metrics_workspace_doubles doubles (per-unit partials: 2048 elements of one horizon step each); a second
+ * launch of one workgroup per step adds them into `state` ([horizon][6] fp64, persistent: the caller zeroes it).
+ *   replaces MaskedMAE / MaskedMSE / MaskedMAPE / MaskedMRE .update, with and without at= (tsl/nn/metrics) */
+int64_t sgp_masked_metrics_workspace_doubles(int64_t batch, int32_t horizon, int64_t nodes, int32_t channels);
+int sgp_masked_metrics_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t batch, int32_t horizon,
+                           int64_t nodes, int32_t channels, const float* scale, const float* bias,
+                           int64_t sc_node_stride, int32_t mask_nans, int32_t mask_inf, double* work,
+                           int64_t work_doubles, double* state, sgp_stream_t stream);
+
+/* loss[0] = sum of f(y_hat, y) over the counted elements / their number (count[0]; the plain sum, 0, when nothing
+ * counts), over contiguous [batch, horizon, row]; kind 0: f = |d|, 1: d^2, 2: |d / y| (infinite values never count);
+ * at >= 0: horizon step `at` only, -1: all.  grad[e] = grad_out[0] / count[0] * df/dy_hat on the counted elements
+ * (sign(d), 2 d, sign(d) / |y|), 0 elsewhere.  `work`: sgp_masked_loss_workspace_doubles doubles.
+ *   replaces MaskedMAE / MaskedMSE / MaskedMAPE as loss_fn of the reference's Predictor */
+int64_t sgp_masked_loss_workspace_doubles(int64_t batch, int32_t horizon, int64_t row, int32_t at);
+int sgp_masked_loss_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t batch, int32_t horizon,
+                        int64_t row, int32_t kind, int32_t at, int32_t mask_nans, double* work, int64_t work_doubles,
+                        float* loss, double* count, sgp_stream_t stream);
+int sgp_masked_loss_bwd_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t batch, int32_t horizon,
+                            int64_t row, int32_t kind, int32_t at, int32_t mask_nans, const float* grad_out,
+                            const double* count, float* grad, sgp_stream_t stream);
+
+
 /* ------------------------------------------------ Gated graph network: edges -----
  * The per-edge MLP, gate and sum of a GatedGraphNetwork layer (gated_gn.hip), forward and backward, for the same
  * edge list in every batch item.  EXACT-FP32 contract as above: every product is a v_mfma_f32_16x16x4_f32.

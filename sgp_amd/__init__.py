@@ -7,6 +7,10 @@ from .graph import ShiftOperator
 from .nn.encoders import GESNEncoder, SGPEncoder, SGPSpatialEncoder, SGPTemporalEncoder
 from .nn.reservoir import GESNLayer, GraphESN, Reservoir, ReservoirLayer
 from .readout import RidgeReadout, closed_form_readout
+from .metrics import (MaskedMAE, MaskedMAPE, MaskedMRE, MaskedMSE, MetricSet, masked_loss, masked_mae, masked_mape,
+                      masked_mse)
+from .optim import FusedAdam
+from .predictors import Predictor
 from .sgp_preprocessing import (preprocess_adj, preprocess_dataset, reservoir_preprocessing_,
                                 sgp_spatial_embedding, sgp_spatial_support)
 from .utils import encode_dataset, self_normalizing_activation

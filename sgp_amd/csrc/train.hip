@@ -1,0 +1,403 @@
+// The training step outside the model (gfx950): the optimizer, the gradient norm, the losses and the logged metrics.
+//   sgp_multi_sqnorm_f32       L2 norm of a LIST of gradient tensors: one workgroup per chunk of the chunk table writes
+//                              its fp64 partial, a single workgroup adds the partials in a fixed order.
+//   sgp_adam_step_f32          torch.optim.Adam / AdamW over the same chunk table in one launch, with clip_grad_norm_'s
+//                              coefficient formed from the device norm inside the update.
+//   sgp_masked_metrics_f32     one pass over y_hat, y, mask for the sums behind mae / mse / mape / mre of every horizon
+//                              step, added into a persistent [H, 6] fp64 state.
+//   sgp_masked_loss_f32 / _bwd MaskedMAE / MSE / MAPE as a loss, optionally at one horizon step.
+// Every reduction is a fixed tree over fixed partials: no float atomics, bit-identical from run to run.
+//
+// Chunk table (device, int64 [n_chunks][3]): (tensor id, element offset, length).  A chunk never crosses a tensor; its
+// tensor's four base pointers come from four device pointer arrays indexed by the id.  Tensors need 4-byte alignment
+// only: a chunk is walked as (head of up to 3 scalars until the walk's lead pointer is 16-byte aligned, 16-byte
+// vectors, tail of up to 3 scalars); an operand that is misaligned relative to the lead is read by scalars.
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+using sgp::f32x4;
+
+constexpr int TR_THREADS = 256;
+constexpr int TR_WAVES = TR_THREADS / 64;
+constexpr int MET_SEG = 2048;              // elements of one (horizon step, segment) unit of the metric / loss passes
+constexpr int MET_COLS = 6;                // |d| sum, |d| count, d^2 sum, |d / y| sum, |d / y| count, masked y sum
+
+// Sum of NV doubles per thread over the workgroup, in a fixed order (xor-free shuffle tree per wave, then the waves in
+// order); the result is valid in thread 0.
+template <int NV>
+__device__ __forceinline__ void block_sum(double (&v)[NV], double* lds /* [NV * TR_WAVES] */) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();                                          // (the caller may reuse lds from a previous sum)
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) lds[k * TR_WAVES + wave] = v[k];
+    __syncthreads();
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            double s = lds[k * TR_WAVES];
+#pragma unroll
+            for (int w = 1; w < TR_WAVES; ++w) s += lds[k * TR_WAVES + w];
+            v[k] = s;
+        }
+}
+
+__device__ __forceinline__ int head_of(const float* p, long long len) {
+    const int h = (int)((4u - (unsigned)((reinterpret_cast<uintptr_t>(p) >> 2) & 3u)) & 3u);
+    return (long long)h < len ? h : (int)len;
+}
+__device__ __forceinline__ bool vec_ok(const float* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+__device__ __forceinline__ f32x4 load4(const float* p, bool vec) {
+    if (vec) return *reinterpret_cast<const f32x4*>(p);
+    f32x4 r = {p[0], p[1], p[2], p[3]};
+    return r;
+}
+__device__ __forceinline__ void store4(float* p, bool vec, f32x4 x) {
+    if (vec) { *reinterpret_cast<f32x4*>(p) = x; return; }
+    p[0] = x.x; p[1] = x.y; p[2] = x.z; p[3] = x.w;
+}
+
+// ------------------------------------------------------------------------------------------------ gradient norm
+__global__ __launch_bounds__(TR_THREADS) void multi_sqnorm_kernel(const long long* __restrict__ table,
+                                                                  const float* const* __restrict__ grads,
+                                                                  double* __restrict__ partial) {
+    __shared__ double lds[TR_WAVES];
+    const long long c = blockIdx.x;
+    const float* g = grads[table[3 * c]] + table[3 * c + 1];
+    const long long len = table[3 * c + 2];
+    const int head = head_of(g, len);
+    const long long nvec = (len - head) >> 2, tail0 = head + 4 * nvec;
+    double s[1] = {0.0};
+    if ((int)threadIdx.x < head) { const double x = g[threadIdx.x]; s[0] += x * x; }
+    for (long long i = threadIdx.x; i < nvec; i += TR_THREADS) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(g + head + 4 * i);
+        s[0] += (double)x.x * x.x + (double)x.y * x.y + (double)x.z * x.z + (double)x.w * x.w;
+    }
+    if (tail0 + threadIdx.x < len) { const double x = g[tail0 + threadIdx.x]; s[0] += x * x; }
+    block_sum<1>(s, lds);
+    if (threadIdx.x == 0) partial[c] = s[0];
+}
+
+__global__ __launch_bounds__(TR_THREADS) void sqnorm_final_kernel(const double* __restrict__ partial, long long n,
+                                                                  float* __restrict__ norm_f32,
+                                                                  double* __restrict__ norm_f64) {
+    __shared__ double lds[TR_WAVES];
+    double s[1] = {0.0};
+    for (long long i = threadIdx.x; i < n; i += TR_THREADS) s[0] += partial[i];
+    block_sum<1>(s, lds);
+    if (threadIdx.x == 0) {
+        const double nrm = sqrt(s[0]);
+        if (norm_f64) norm_f64[0] = nrm;
+        norm_f32[0] = (float)nrm;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ Adam
+struct AdamConst {
+    float max_norm;        // <= 0: no clip
+    float wd;              // L2: g += wd * p  (0: none)
+    float decay;           // decoupled: p *= decay  (1: none)
+    float w1;              // 1 - beta1 (lerp weight)
+    float beta2, w2;       // v = v * beta2 + w2 * g * g
+    float bc2_sqrt, eps;   // denom = sqrt(v) / bc2_sqrt + eps
+    float neg_step;        // p += neg_step * m / denom,  neg_step = -lr / (1 - beta1^step)
+};
+
+__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float coef, bool clip, const AdamConst& k) {
+    if (clip) g *= coef;
+    if (k.wd != 0.f) g = g + k.wd * p;
+    if (k.decay != 1.f) p *= k.decay;
+    // Tensor.lerp_(end, weight): start + weight * (end - start) below 0.5, end - (end - start) * (1 - weight) from there
+    m = k.w1 < 0.5f ? m + k.w1 * (g - m) : g - (g - m) * (1.f - k.w1);
+    v = v * k.beta2 + k.w2 * g * g;
+    const float denom = sqrtf(v) / k.bc2_sqrt + k.eps;
+    p = p + k.neg_step * m / denom;
+}
+
+__global__ __launch_bounds__(TR_THREADS) void adam_step_kernel(const long long* __restrict__ table,
+                                                               float* const* __restrict__ params,
+                                                               const float* const* __restrict__ grads,
+                                                               float* const* __restrict__ exp_avg,
+                                                               float* const* __restrict__ exp_avg_sq,
+                                                               const float* __restrict__ norm, AdamConst k) {
+    const long long c = blockIdx.x;
+    const long long t = table[3 * c], off = table[3 * c + 1], len = table[3 * c + 2];
+    float* p = params[t] + off;
+    const float* g = grads[t] + off;
+    float* m = exp_avg[t] + off;
+    float* v = exp_avg_sq[t] + off;
+    const bool clip = k.max_norm > 0.f;
+    float coef = 1.f;
+    if (clip) {
+        // clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max = 1); a NaN norm stays NaN (the comparison is false)
+        coef = k.max_norm / (norm[0] + 1e-6f);
+        coef = coef > 1.f ? 1.f : coef;
+    }
+    const int head = head_of(p, len);
+    const long long nvec = (len - head) >> 2, tail0 = head + 4 * nvec;
+    if ((int)threadIdx.x < head) adam_one(p[threadIdx.x], g[threadIdx.x], m[threadIdx.x], v[threadIdx.x], coef, clip, k);
+    const bool gv = vec_ok(g + head), mv = vec_ok(m + head), vv = vec_ok(v + head);
+    for (long long i = threadIdx.x; i < nvec; i += TR_THREADS) {
+        const long long e = head + 4 * i;
+        const f32x4 P = *reinterpret_cast<f32x4*>(p + e), G = load4(g + e, gv), M = load4(m + e, mv), V = load4(v + e, vv);
+        float pp[4] = {P.x, P.y, P.z, P.w}, mm[4] = {M.x, M.y, M.z, M.w}, vs[4] = {V.x, V.y, V.z, V.w};
+        const float gg[4] = {G.x, G.y, G.z, G.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) adam_one(pp[q], gg[q], mm[q], vs[q], coef, clip, k);
+        const f32x4 Po = {pp[0], pp[1], pp[2], pp[3]}, Mo = {mm[0], mm[1], mm[2], mm[3]}, Vo = {vs[0], vs[1], vs[2], vs[3]};
+        *reinterpret_cast<f32x4*>(p + e) = Po;
+        store4(m + e, mv, Mo);
+        store4(v + e, vv, Vo);
+    }
+    const long long e = tail0 + threadIdx.x;
+    if (e < len) adam_one(p[e], g[e], m[e], v[e], coef, clip, k);
+}
+
+// ------------------------------------------------------------------------------------------------ metrics and losses
+// y_hat, y, mask are contiguous [B, H, R] (R = nodes * channels).  Horizon step h owns the J = B * R elements
+// j = b * R + r at address (b * H + h) * R + r; a unit is MET_SEG consecutive j of one h.
+struct Transform { const float* scale; const float* bias; long long node_stride; int channels; };
+
+__device__ __forceinline__ long long addr_of(long long j, long long R, long long H, long long h, long long& r) {
+    long long b;
+    if (((unsigned long long)j | (unsigned long long)R) >> 32) { b = j / R; r = j - b * R; }
+    else { const unsigned q = (unsigned)j / (unsigned)R; b = q; r = (unsigned)j - q * (unsigned)R; }
+    return (b * H + h) * R + r;
+}
+
+__device__ __forceinline__ float inverse_transform(float yh, const Transform& tr, long long r) {
+    if (!tr.scale) return yh;
+    const long long n = r / tr.channels, c = r - n * tr.channels;
+    const long long at = n * tr.node_stride + c;
+    return yh * (tr.scale[at] + 5e-8f) + tr.bias[at];          // ScalerModule.inverse_transform_tensor (tsl.epsilon)
+}
+
+// MaskedMetric._check_mask on the metric's own value
+__device__ __forceinline__ bool counts(bool m, float val, int mask_nans, int mask_inf) {
+    return m && !(mask_nans && isnan(val)) && !(mask_inf && isinf(val));
+}
+
+__global__ __launch_bounds__(TR_THREADS) void masked_metrics_kernel(const float* __restrict__ yh, const float* __restrict__ y,
+                                                                    const unsigned char* __restrict__ mask, long long J,
+                                                                    long long H, long long R, long long nseg, Transform tr,
+                                                                    int mask_nans, int mask_inf, double* __restrict__ partial) {
+    __shared__ double lds[MET_COLS * TR_WAVES];
+    const long long u = blockIdx.x, h = u / nseg, seg = u - h * nseg;
+    const long long j1 = (seg + 1) * MET_SEG < J ? (seg + 1) * MET_SEG : J;
+    double s[MET_COLS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long long j = seg * MET_SEG + threadIdx.x; j < j1; j += TR_THREADS) {
+        long long r;
+        const long long a = addr_of(j, R, H, h, r);
+        const float t = y[a], d = inverse_transform(yh[a], tr, r) - t;
+        const bool m = mask ? mask[a] != 0 : true;
+        const float ad = fabsf(d);
+        if (counts(m, ad, mask_nans, mask_inf)) { s[0] += (double)ad; s[1] += 1.0; s[2] += (double)(d * d); s[5] += (double)t; }
+        const float q = fabsf(d / t);
+        if (counts(m, q, mask_nans, 1)) { s[3] += (double)q; s[4] += 1.0; }
+    }
+    block_sum<MET_COLS>(s, lds);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int k = 0; k < MET_COLS; ++k) partial[u * MET_COLS + k] = s[k];
+}
+
+// one workgroup per horizon step: state[h][k] += sum over the step's segments, in a fixed order
+__global__ __launch_bounds__(TR_THREADS) void masked_metrics_final_kernel(const double* __restrict__ partial, long long nseg,
+                                                                          double* __restrict__ state) {
+    __shared__ double lds[MET_COLS * TR_WAVES];
+    const long long h = blockIdx.x;
+    double s[MET_COLS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long long i = threadIdx.x; i < nseg; i += TR_THREADS)
+#pragma unroll
+        for (int k = 0; k < MET_COLS; ++k) s[k] += partial[(h * nseg + i) * MET_COLS + k];
+    block_sum<MET_COLS>(s, lds);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int k = 0; k < MET_COLS; ++k) state[h * MET_COLS + k] += s[k];
+}
+
+enum { LOSS_MAE = 0, LOSS_MSE = 1, LOSS_MAPE = 2 };
+
+__device__ __forceinline__ float loss_value(int kind, float d, float t) {
+    return kind == LOSS_MAE ? fabsf(d) : (kind == LOSS_MSE ? d * d : fabsf(d / t));
+}
+
+__global__ __launch_bounds__(TR_THREADS) void masked_loss_kernel(const float* __restrict__ yh, const float* __restrict__ y,
+                                                                 const unsigned char* __restrict__ mask, long long J,
+                                                                 long long H, long long R, long long h, int kind,
+                                                                 int mask_nans, double* __restrict__ partial) {
+    __shared__ double lds[2 * TR_WAVES];
+    const long long seg = blockIdx.x;
+    const long long j1 = (seg + 1) * MET_SEG < J ? (seg + 1) * MET_SEG : J;
+    double s[2] = {0.0, 0.0};
+    for (long long j = seg * MET_SEG + threadIdx.x; j < j1; j += TR_THREADS) {
+        long long r;
+        const long long a = addr_of(j, R, H, h, r);
+        const float t = y[a], val = loss_value(kind, yh[a] - t, t);
+        if (counts(mask ? mask[a] != 0 : true, val, mask_nans, kind == LOSS_MAPE)) { s[0] += (double)val; s[1] += 1.0; }
+    }
+    block_sum<2>(s, lds);
+    if (threadIdx.x == 0) { partial[2 * seg] = s[0]; partial[2 * seg + 1] = s[1]; }
+}
+
+__global__ __launch_bounds__(TR_THREADS) void masked_loss_final_kernel(const double* __restrict__ partial, long long nseg,
+                                                                       float* __restrict__ loss, double* __restrict__ count) {
+    __shared__ double lds[2 * TR_WAVES];
+    double s[2] = {0.0, 0.0};
+    for (long long i = threadIdx.x; i < nseg; i += TR_THREADS) { s[0] += partial[2 * i]; s[1] += partial[2 * i + 1]; }
+    block_sum<2>(s, lds);
+    if (threadIdx.x == 0) {
+        loss[0] = s[1] > 0.0 ? (float)(s[0] / s[1]) : (float)s[0];      // MaskedMetric.compute: value when numel == 0
+        count[0] = s[1];
+    }
+}
+
+__global__ void masked_loss_bwd_kernel(const float* __restrict__ yh, const float* __restrict__ y,
+                                       const unsigned char* __restrict__ mask, long long n, long long H, long long R,
+                                       long long at, int kind, int mask_nans, const float* __restrict__ gout,
+                                       const double* __restrict__ count, float* __restrict__ grad) {
+    const float scale = gout[0] / (float)count[0];
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        float g = 0.f;
+        if (at < 0 || (e / R) % H == at) {
+            const float t = y[e], d = yh[e] - t;
+            if (counts(mask ? mask[e] != 0 : true, loss_value(kind, d, t), mask_nans, kind == LOSS_MAPE)) {
+                const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f * d);
+                g = kind == LOSS_MAE ? scale * sgn : (kind == LOSS_MSE ? scale * 2.f * d : scale * sgn / fabsf(t));
+            }
+        }
+        grad[e] = g;
+    }
+}
+
+long long units_of(long long J) { return J > 0 ? (J + MET_SEG - 1) / MET_SEG : 0; }
+constexpr long long MAX_GRID = 2147483647LL;
+
+}  // namespace
+
+extern "C" {
+
+int sgp_multi_sqnorm_f32(const int64_t* table, int64_t n_chunks, const float* const* grads, double* partial,
+                         float* norm_f32, double* norm_f64, sgp_stream_t stream) {
+    SGP_REQUIRE(table && grads && partial && norm_f32, "sgp_multi_sqnorm_f32: null pointer");
+    SGP_REQUIRE(n_chunks >= 0 && n_chunks <= MAX_GRID, "sgp_multi_sqnorm_f32: bad size");
+    if (n_chunks > 0) {
+        hipLaunchKernelGGL(multi_sqnorm_kernel, dim3((unsigned)n_chunks), dim3(TR_THREADS), 0, (hipStream_t)stream,
+                           (const long long*)table, grads, partial);
+        if (int rc = sgp::check_launch("multi_sqnorm")) return rc;
+    }
+    hipLaunchKernelGGL(sqnorm_final_kernel, dim3(1), dim3(TR_THREADS), 0, (hipStream_t)stream, partial,
+                       (long long)n_chunks, norm_f32, norm_f64);
+    return sgp::check_launch("sqnorm_final");
+}
+
+int sgp_adam_step_f32(const int64_t* table, int64_t n_chunks, float* const* params, const float* const* grads,
+                      float* const* exp_avg, float* const* exp_avg_sq, const float* norm, double max_norm,
+                      double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                      int32_t decoupled, sgp_stream_t stream) {
+    SGP_REQUIRE(table && params && grads && exp_avg && exp_avg_sq, "sgp_adam_step_f32: null pointer");
+    SGP_REQUIRE(n_chunks >= 0 && n_chunks <= MAX_GRID, "sgp_adam_step_f32: bad size");
+    SGP_REQUIRE(step >= 1, "sgp_adam_step_f32: step counts from 1");
+    SGP_REQUIRE(decoupled == 0 || decoupled == 1, "sgp_adam_step_f32: decoupled is 0 or 1");
+    SGP_REQUIRE(!(max_norm > 0.0) || norm, "sgp_adam_step_f32: a clip needs the norm (null pointer)");
+    SGP_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && lr >= 0.0 && weight_decay >= 0.0,
+                "sgp_adam_step_f32: bad hyper-parameter");
+    if (n_chunks == 0) return 0;
+    // torch.optim.adam._single_tensor_adam: the scalars are formed in double on the host and rounded once
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    AdamConst k;
+    k.max_norm = max_norm > 0.0 ? (float)max_norm : 0.f;
+    k.wd = decoupled ? 0.f : (float)weight_decay;
+    k.decay = decoupled ? (float)(1.0 - lr * weight_decay) : 1.f;
+    k.w1 = (float)(1.0 - beta1);
+    k.beta2 = (float)beta2;
+    k.w2 = (float)(1.0 - beta2);
+    k.bc2_sqrt = (float)sqrt(bc2);
+    k.eps = (float)eps;
+    k.neg_step = (float)(-(lr / bc1));
+    hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)n_chunks), dim3(TR_THREADS), 0, (hipStream_t)stream,
+                       (const long long*)table, params, grads, exp_avg, exp_avg_sq, norm, k);
+    return sgp::check_launch("adam_step");
+}
+
+int64_t sgp_masked_metrics_workspace_doubles(int64_t batch, int32_t horizon, int64_t nodes, int32_t channels) {
+    if (batch < 0 || horizon < 0 || nodes < 0 || channels < 0) return -1;
+    return (int64_t)horizon * units_of(batch * nodes * channels) * MET_COLS;
+}
+
+int sgp_masked_metrics_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t batch, int32_t horizon,
+                           int64_t nodes, int32_t channels, const float* scale, const float* bias,
+                           int64_t sc_node_stride, int32_t mask_nans, int32_t mask_inf, double* work,
+                           int64_t work_doubles, double* state, sgp_stream_t stream) {
+    SGP_REQUIRE(y_hat && y && work && state, "sgp_masked_metrics_f32: null pointer");
+    SGP_REQUIRE(batch >= 0 && horizon >= 0 && nodes >= 0 && channels >= 0 && sc_node_stride >= 0,
+                "sgp_masked_metrics_f32: bad size");
+    SGP_REQUIRE((scale == nullptr) == (bias == nullptr), "sgp_masked_metrics_f32: scale and bias come together");
+    SGP_REQUIRE((mask_nans == 0 || mask_nans == 1) && (mask_inf == 0 || mask_inf == 1),
+                "sgp_masked_metrics_f32: mask_nans / mask_inf are 0 or 1");
+    const long long R = nodes * channels, J = batch * R, nseg = units_of(J);
+    if (nseg == 0 || horizon == 0) return 0;
+    SGP_REQUIRE(nseg * horizon <= MAX_GRID, "sgp_masked_metrics_f32: too many units");
+    SGP_REQUIRE(work_doubles >= nseg * horizon * MET_COLS, "sgp_masked_metrics_f32: workspace too small");
+    Transform tr = {scale, bias, sc_node_stride, channels};
+    hipLaunchKernelGGL(masked_metrics_kernel, dim3((unsigned)(nseg * horizon)), dim3(TR_THREADS), 0, (hipStream_t)stream,
+                       y_hat, y, mask, J, (long long)horizon, R, nseg, tr, mask_nans, mask_inf, work);
+    if (int rc = sgp::check_launch("masked_metrics")) return rc;
+    hipLaunchKernelGGL(masked_metrics_final_kernel, dim3((unsigned)horizon), dim3(TR_THREADS), 0, (hipStream_t)stream,
+                       (const double*)work, nseg, state);
+    return sgp::check_launch("masked_metrics_final");
+}
+
+int64_t sgp_masked_loss_workspace_doubles(int64_t batch, int32_t horizon, int64_t row, int32_t at) {
+    if (batch < 0 || horizon < 0 || row < 0) return -1;
+    return 2 * units_of(at < 0 ? batch * horizon * row : batch * row);
+}
+
+int sgp_masked_loss_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t batch, int32_t horizon,
+                        int64_t row, int32_t kind, int32_t at, int32_t mask_nans, double* work, int64_t work_doubles,
+                        float* loss, double* count, sgp_stream_t stream) {
+    SGP_REQUIRE(y_hat && y && work && loss && count, "sgp_masked_loss_f32: null pointer");
+    SGP_REQUIRE(batch >= 0 && horizon >= 0 && row >= 0, "sgp_masked_loss_f32: bad size");
+    SGP_REQUIRE(kind >= LOSS_MAE && kind <= LOSS_MAPE, "sgp_masked_loss_f32: kind is 0 (mae), 1 (mse) or 2 (mape)");
+    SGP_REQUIRE(at >= -1 && (at < 0 || at < horizon), "sgp_masked_loss_f32: at outside the horizon");
+    SGP_REQUIRE(mask_nans == 0 || mask_nans == 1, "sgp_masked_loss_f32: mask_nans is 0 or 1");
+    // without `at` the tensor is one flat row; with it, step `at` of [B, H, R]
+    const long long J = at < 0 ? batch * horizon * row : batch * row, nseg = units_of(J);
+    SGP_REQUIRE(nseg <= MAX_GRID, "sgp_masked_loss_f32: too many units");
+    SGP_REQUIRE(work_doubles >= 2 * nseg, "sgp_masked_loss_f32: workspace too small");
+    if (nseg > 0) {
+        hipLaunchKernelGGL(masked_loss_kernel, dim3((unsigned)nseg), dim3(TR_THREADS), 0, (hipStream_t)stream,
+                           y_hat, y, mask, J, at < 0 ? 1LL : (long long)horizon, at < 0 ? J : (long long)row,
+                           at < 0 ? 0LL : (long long)at, kind, mask_nans, work);
+        if (int rc = sgp::check_launch("masked_loss")) return rc;
+    }
+    hipLaunchKernelGGL(masked_loss_final_kernel, dim3(1), dim3(TR_THREADS), 0, (hipStream_t)stream,
+                       (const double*)work, nseg, loss, count);
+    return sgp::check_launch("masked_loss_final");
+}
+
+int sgp_masked_loss_bwd_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t batch, int32_t horizon,
+                            int64_t row, int32_t kind, int32_t at, int32_t mask_nans, const float* grad_out,
+                            const double* count, float* grad, sgp_stream_t stream) {
+    SGP_REQUIRE(y_hat && y && grad_out && count && grad, "sgp_masked_loss_bwd_f32: null pointer");
+    SGP_REQUIRE(batch >= 0 && horizon >= 0 && row >= 0, "sgp_masked_loss_bwd_f32: bad size");
+    SGP_REQUIRE(kind >= LOSS_MAE && kind <= LOSS_MAPE, "sgp_masked_loss_bwd_f32: kind is 0 (mae), 1 (mse) or 2 (mape)");
+    SGP_REQUIRE(at >= -1 && (at < 0 || at < horizon), "sgp_masked_loss_bwd_f32: at outside the horizon");
+    SGP_REQUIRE(mask_nans == 0 || mask_nans == 1, "sgp_masked_loss_bwd_f32: mask_nans is 0 or 1");
+    const long long n = batch * horizon * row;
+    if (n == 0) return 0;
+    long long grid = (n + 255) / 256;
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(masked_loss_bwd_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream,
+                       y_hat, y, mask, n, (long long)horizon, (long long)row, (long long)at, kind, mask_nans, grad_out,
+                       count, grad);
+    return sgp::check_launch("masked_loss_bwd");
+}
+
+}  // extern "C"

@@ -187,6 +187,17 @@ SIGNATURES = {
     "sgp_row_segsum_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i32, c_p, c_p, c_i32, c_p, c_p]),
     "sgp_masked_mae_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p]),
     "sgp_masked_mae_bwd_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p]),
+    "sgp_multi_sqnorm_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "sgp_adam_step_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_f64,
+                                         c_f64, c_f64, c_f64, c_f64, c_f64, c_i64, c_i32, c_p]),
+    "sgp_masked_metrics_workspace_doubles": (c_i64, [c_i64, c_i32, c_i64, c_i32]),
+    "sgp_masked_metrics_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_i64, c_i32, c_p, c_p, c_i64, c_i32, c_i32,
+                                              c_p, c_i64, c_p, c_p]),
+    "sgp_masked_loss_workspace_doubles": (c_i64, [c_i64, c_i32, c_i64, c_i32]),
+    "sgp_masked_loss_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_i64, c_i32, c_i32, c_i32, c_p, c_i64,
+                                           c_p, c_p, c_p]),
+    "sgp_masked_loss_bwd_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_p,
+                                               c_p]),
     "sgp_gated_gn_supported": (c_i32, [c_i32, c_i32]),
     "sgp_gated_gn_chunk_edges": (c_i32, []),
     "sgp_gated_gn_workspace_bytes": (c_i64, [c_i32, c_i64, c_i64, c_i64, c_i32, c_i32]),
@@ -1433,6 +1444,105 @@ def masked_mae_bwd(y_hat, y, mask, mask_nans, grad_out, count):
     _check(lib.sgp_masked_mae_bwd_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), y_hat.numel(), int(mask_nans),
                                       grad_out.data_ptr(), count.data_ptr(), grad.data_ptr(), _stream(grad)),
            "sgp_masked_mae_bwd_f32")
+    return grad
+
+
+# ---------------------------------------------------------------- training step (train.hip)
+LOSS_KINDS = {"mae": 0, "mse": 1, "mape": 2}
+METRIC_COLS = 6     # per horizon step: sum |d|, its count, sum d^2, sum |d / y|, its count, sum of the counted y
+
+
+@_on_device
+def multi_sqnorm(table, grads, partial, norm_f32, norm_f64=None):
+    """L2 norm of the gradient list behind ``table`` (int64 CUDA ``[n_chunks, 3]``; ``grads``: int64 CUDA tensor of
+    base addresses) into the device scalars ``norm_f32`` / ``norm_f64``; ``partial``: float64 CUDA, one per chunk."""
+    lib = require_gpu()
+    n = table.shape[0]
+    if partial.numel() < n:
+        raise ValueError("multi_sqnorm: partial holds fewer doubles than the table has chunks")
+    _check(lib.sgp_multi_sqnorm_f32(table.data_ptr(), n, grads.data_ptr(), partial.data_ptr(), norm_f32.data_ptr(),
+                                    _ptr(norm_f64), _stream(table)), "sgp_multi_sqnorm_f32")
+
+
+@_on_device
+def adam_step(table, params, grads, exp_avg, exp_avg_sq, *, lr, betas, eps, weight_decay, step, norm=None,
+              max_norm=0.0, decoupled=False):
+    """One Adam / AdamW step over the chunk table (one launch); ``norm``: the device scalar of ``multi_sqnorm`` when
+    ``max_norm > 0``.  The four pointer arrays are int64 CUDA tensors of base addresses, indexed by the table's ids."""
+    lib = require_gpu()
+    _check(lib.sgp_adam_step_f32(table.data_ptr(), table.shape[0], params.data_ptr(), grads.data_ptr(),
+                                 exp_avg.data_ptr(), exp_avg_sq.data_ptr(), _ptr(norm), float(max_norm), float(lr),
+                                 float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
+                                 int(bool(decoupled)), _stream(table)), "sgp_adam_step_f32")
+
+
+def _bhr(y_hat, y, mask, what):
+    """Contiguous float32 CUDA ``y_hat``, ``y`` of one shape ``[B, H, ...]`` (uint8 ``mask`` of the same shape)."""
+    for name, t in (("y_hat", y_hat), ("y", y)):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous float32 CUDA tensor")
+    if y_hat.shape != y.shape or y.dim() < 2:
+        raise ValueError(f"{what}: y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} must share a shape [B, H, ...]")
+    if mask is not None and (mask.shape != y.shape or mask.dtype != torch.uint8 or not mask.is_cuda
+                             or not mask.is_contiguous()):
+        raise ValueError(f"{what}: mask must be a contiguous uint8 CUDA tensor of the shape of y")
+
+
+@_on_device
+def masked_metrics(y_hat, y, mask, state, scale=None, bias=None, sc_node_stride=0, mask_nans=False, mask_inf=False):
+    """Add the masked sums of one batch ``[B, H, N, C]`` into ``state`` (float64 CUDA ``[H, METRIC_COLS]``): one pass
+    over the batch and one fixed-order add, no host sync.  ``scale`` / ``bias``: the inverse transform of ``y_hat``
+    (float32 CUDA, element (n, c) at ``n * sc_node_stride + c``)."""
+    lib = require_gpu()
+    _bhr(y_hat, y, mask, "masked_metrics")
+    if y.dim() != 4:
+        raise ValueError("masked_metrics: expected [B, H, N, C]")
+    B, H, N, C = y.shape
+    if tuple(state.shape) != (H, METRIC_COLS) or state.dtype != torch.float64 or not state.is_cuda \
+            or not state.is_contiguous():
+        raise ValueError(f"masked_metrics: state must be contiguous float64 CUDA [{H}, {METRIC_COLS}]")
+    if not y.numel():
+        return state
+    work = torch.empty(max(1, lib.sgp_masked_metrics_workspace_doubles(B, H, N, C)), dtype=torch.float64, device=y.device)
+    _check(lib.sgp_masked_metrics_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), B, H, N, C, _ptr(scale), _ptr(bias),
+                                      int(sc_node_stride), int(bool(mask_nans)), int(bool(mask_inf)), work.data_ptr(),
+                                      work.numel(), state.data_ptr(), _stream(y)), "sgp_masked_metrics_f32")
+    return state
+
+
+def _loss_dims(y, at):
+    B, H = y.shape[0], y.shape[1]
+    if at is not None and not 0 <= int(at) < H:
+        raise ValueError(f"masked_loss: at={at} outside the horizon of {H} steps")
+    return B, H, (y.numel() // (B * H) if B * H else 0), (-1 if at is None else int(at))
+
+
+@_on_device
+def masked_loss(y_hat, y, mask=None, kind="mae", at=None, mask_nans=False):
+    """(loss [] float32, count [1] float64) of MaskedMAE / MaskedMSE / MaskedMAPE over ``[B, H, ...]``, all steps or
+    step ``at``: per-segment fp64 partials from many workgroups, added in a fixed order."""
+    lib = require_gpu()
+    _bhr(y_hat, y, mask, "masked_loss")
+    B, H, R, at = _loss_dims(y, at)
+    loss = torch.empty((), dtype=torch.float32, device=y.device)
+    count = torch.empty(1, dtype=torch.float64, device=y.device)
+    work = torch.empty(max(1, lib.sgp_masked_loss_workspace_doubles(B, H, R, at)), dtype=torch.float64, device=y.device)
+    _check(lib.sgp_masked_loss_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), B, H, R, LOSS_KINDS[kind], at,
+                                   int(bool(mask_nans)), work.data_ptr(), work.numel(), loss.data_ptr(),
+                                   count.data_ptr(), _stream(y)), "sgp_masked_loss_f32")
+    return loss, count
+
+
+@_on_device
+def masked_loss_bwd(y_hat, y, mask, kind, at, mask_nans, grad_out, count):
+    lib = require_gpu()
+    B, H, R, at = _loss_dims(y, at)
+    grad = torch.empty_like(y_hat)
+    if not y_hat.numel():
+        return grad
+    _check(lib.sgp_masked_loss_bwd_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), B, H, R, LOSS_KINDS[kind], at,
+                                       int(bool(mask_nans)), grad_out.data_ptr(), count.data_ptr(), grad.data_ptr(),
+                                       _stream(grad)), "sgp_masked_loss_bwd_f32")
     return grad
 
 
