@@ -1131,6 +1131,49 @@ int sgp_subgraph_take_edges(const int32_t* src, const int32_t* dst, const float*
                             const int32_t* relabel, int64_t n_nodes, int64_t* out_src, int64_t* out_dst,
                             float* out_weight, int32_t* err, sgp_stream_t stream);
 
+/* ------------------------------------------- graph construction ---
+ * Row-wise selection over an N x N similarity that is either never formed (geographic) or given (dense).  Entry A[i, j]
+ * of row i, column j.  `threshold`: entries whose value is below it are dropped (-inf: none); `binary`: kept values
+ * become 1 (knn) or `sim > 0` (no knn); an entry whose value rounds to 0 in fp32 is no entry.  Values come out in fp64
+ * (the caller rounds once, after its O(E) post-processing).
+ *
+ * knn entries: per row the k best candidates by (value descending, column ascending), the diagonal excluded unless
+ * include_self.  out_col / out_val [n, k]: the row's kept entries; a slot whose entry was dropped holds value 0.
+ * 1 <= k <= n; k above sgp_conn_max_knn() (512) is SGP_EUNSUP.
+ *
+ * rows entries (no knn): called twice.  With row_count [n] given: the number of entries of every row.  With row_count
+ * NULL: rowptr [n + 1] (the caller's exclusive scan of the counts, int64) and out_col / out_val [rowptr[n]] receive the
+ * rows, columns ascending.
+ *
+ * Geographic source: unit [3, n] fp64 unit vectors (x | y | z) of the nodes; the value of (i, j) is
+ * exp(-(scale asin(min(1, |u_i - u_j| / 2)))^2) with scale = 2 R / theta, evaluated for kept entries only: knn selects
+ * on min(|u_i - u_j|^2, chord_zero) (chord_zero: the squared chord from which the fp64 value is exactly 0, so those
+ * tie), rows tests the squared chord against [chord_lo, chord_hi] (below: kept; above: dropped; inside: the value
+ * itself is tested).
+ *   replaces geographical_distance + gaussian_kernel (tsl/ops/similarities.py:58-101, lib/datasets/pv.py:88-95) and,
+ *   for both sources, top_k (similarities.py:104-122), `adj[adj < threshold] = 0`, `fill_diagonal` and the non-zero
+ *   scan of adj_to_edge_index / csr_matrix in get_connectivity (tsl/datasets/prototypes/dataset.py:411-433)
+ * Dense source: sim [n, n] fp32 (is_f64 = 0) or fp64 with the given element strides; fp64 is compared as fp64. */
+int32_t sgp_conn_max_knn(void);
+int sgp_conn_geo_knn_f64(const double* unit, int64_t n, int32_t k, int32_t include_self, int32_t binary,
+                         double threshold, double chord_zero, double scale, int32_t* out_col, double* out_val,
+                         sgp_stream_t stream);
+int sgp_conn_geo_rows_f64(const double* unit, int64_t n, int32_t include_self, int32_t binary, double threshold,
+                          double chord_lo, double chord_hi, double scale, int32_t* row_count, const int64_t* rowptr,
+                          int32_t* out_col, double* out_val, sgp_stream_t stream);
+int sgp_conn_dense_knn(const void* sim, int32_t is_f64, int64_t row_stride, int64_t col_stride, int64_t n, int32_t k,
+                       int32_t include_self, int32_t binary, double threshold, int32_t* out_col, double* out_val,
+                       sgp_stream_t stream);
+int sgp_conn_dense_rows(const void* sim, int32_t is_f64, int64_t row_stride, int64_t col_stride, int64_t n,
+                        int32_t include_self, int32_t binary, double threshold, int32_t* row_count,
+                        const int64_t* rowptr, int32_t* out_col, double* out_val, sgp_stream_t stream);
+/* out[a, b] = mean over chunks c < n_chunks of exp(-gamma max(0, n_c[a] + n_c[b] - 2 <x_c[:, a], x_c[:, b]>)), chunk c =
+ * rows [c period, (c + 1) period) of x [>= n_chunks period, n]; the diagonal is exactly 1.  The Gram tiles run on the
+ * exact-fp32 matrix-core form; norms [n_chunks, n] is scratch (the chunks' squared column norms).
+ *   replaces the `rbf_kernel(xi, gamma=gamma)` loop of CEREn.compute_similarity (lib/datasets/cer_en.py:153-164) */
+int sgp_correntropy_f32(const float* x, int64_t x_row_stride, int32_t n, int32_t period, int32_t n_chunks, double gamma,
+                        float* norms, float* out, int64_t out_row_stride, sgp_stream_t stream);
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

@@ -3,6 +3,8 @@
 Python surface.  Compute lives in ``csrc/libsgp_amd.so`` (hand-written HIP for gfx950); there
 is no CPU fallback."""
 from . import dataloader, datasets, hip
+from .connectivity import (correntropy_connectivity, correntropy_similarity, dense_connectivity,
+                           geographic_connectivity)
 from .graph import ShiftOperator
 from .nn.encoders import GESNEncoder, SGPEncoder, SGPSpatialEncoder, SGPTemporalEncoder
 from .nn.reservoir import GESNLayer, GraphESN, Reservoir, ReservoirLayer

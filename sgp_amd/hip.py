@@ -249,6 +249,14 @@ SIGNATURES = {
     "sgp_subgraph_edges": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p]),
     "sgp_subgraph_take_edges": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p,
                                                c_p, c_p, c_p]),
+    "sgp_conn_max_knn": (c_i32, []),
+    "sgp_conn_geo_knn_f64": (ctypes.c_int, [c_p, c_i64, c_i32, c_i32, c_i32, c_f64, c_f64, c_f64, c_p, c_p, c_p]),
+    "sgp_conn_geo_rows_f64": (ctypes.c_int, [c_p, c_i64, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64, c_p, c_p, c_p, c_p,
+                                             c_p]),
+    "sgp_conn_dense_knn": (ctypes.c_int, [c_p, c_i32, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_f64, c_p, c_p, c_p]),
+    "sgp_conn_dense_rows": (ctypes.c_int, [c_p, c_i32, c_i64, c_i64, c_i64, c_i32, c_i32, c_f64, c_p, c_p, c_p, c_p,
+                                           c_p]),
+    "sgp_correntropy_f32": (ctypes.c_int, [c_p, c_i64, c_i32, c_i32, c_i32, c_f64, c_p, c_p, c_i64, c_p]),
     "sgp_event_create": (ctypes.c_int, [ctypes.POINTER(c_p)]),
     "sgp_event_destroy": (ctypes.c_int, [c_p]),
     "sgp_event_record": (ctypes.c_int, [c_p, c_p]),
@@ -1903,6 +1911,121 @@ def gwnet_norm_bwd(dout, z, stats, kind, training, weight=None, eps=1e-5, dropou
                                       _ptr(dw), _ptr(db), R, H, _ptr(work), work.numel() if work is not None else 0,
                                       _stream(dout)), "sgp_gwnet_norm_bwd_f32")
     return dy, dres, dw, db
+
+
+# ---------------------------------------------------------------- graph construction (sgp_amd/connectivity.py)
+def conn_max_knn():
+    """Largest ``knn`` the row-selection kernels keep per row (host only)."""
+    return int(load().sgp_conn_max_knn())
+
+
+def _conn_threshold(threshold):
+    return float("-inf") if threshold is None else float(threshold)
+
+
+def _conn_unit(unit):
+    if unit.dim() != 2 or unit.shape[0] != 3 or unit.dtype != torch.float64 or not unit.is_cuda or \
+            not unit.is_contiguous():
+        raise ValueError("unit: expected contiguous float64 CUDA [3, N]")
+    return unit.shape[1]
+
+
+def _conn_sim(sim):
+    if sim.dim() != 2 or sim.shape[0] != sim.shape[1] or sim.dtype not in (torch.float32, torch.float64) or \
+            not sim.is_cuda:
+        raise ValueError("sim: expected a square float32 / float64 CUDA matrix")
+    return sim.shape[0], int(sim.dtype == torch.float64)
+
+
+def _conn_rows(count_pass, fill_pass, n, device):
+    """Count pass, scan, ONE host read (the entry count), fill pass -> ``(rowptr int64 [n + 1], col int32, val fp64)``."""
+    counts = torch.empty(n, dtype=torch.int32, device=device)
+    count_pass(counts)
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    torch.cumsum(counts, 0, out=rowptr[1:])
+    n_entries = int(rowptr[-1].item())
+    if n_entries > 2 ** 31 - 1:
+        raise ValueError(f"connectivity: {n_entries} entries exceed the int32 CSR index range")
+    col = torch.empty(n_entries, dtype=torch.int32, device=device)
+    val = torch.empty(n_entries, dtype=torch.float64, device=device)
+    if n_entries:
+        fill_pass(rowptr, col, val)
+    return rowptr, col, val
+
+
+@_on_device
+def conn_geo_knn(unit, k, include_self, binary, threshold, chord_zero, scale):
+    """Per row the ``k`` nearest nodes on fp64 unit vectors ``unit [3, N]`` -> ``(col int32 [N, k], val fp64 [N, k])``;
+    a slot whose entry the threshold (or fp32 underflow) dropped holds value 0 (sgp_conn_geo_knn_f64)."""
+    lib = require_gpu()
+    n = _conn_unit(unit)
+    col = torch.empty(n, k, dtype=torch.int32, device=unit.device)
+    val = torch.empty(n, k, dtype=torch.float64, device=unit.device)
+    _check(lib.sgp_conn_geo_knn_f64(unit.data_ptr(), n, int(k), int(bool(include_self)), int(bool(binary)),
+                                    _conn_threshold(threshold), float(chord_zero), float(scale), col.data_ptr(),
+                                    val.data_ptr(), _stream(unit)), "sgp_conn_geo_knn_f64")
+    return col, val
+
+
+@_on_device
+def conn_geo_rows(unit, include_self, binary, threshold, chord_lo, chord_hi, scale):
+    """Every entry inside the chord bound as CSR rows with ascending columns (sgp_conn_geo_rows_f64; one host sync)."""
+    lib = require_gpu()
+    n = _conn_unit(unit)
+    head = (unit.data_ptr(), n, int(bool(include_self)), int(bool(binary)), _conn_threshold(threshold), float(chord_lo),
+            float(chord_hi), float(scale))
+    return _conn_rows(
+        lambda counts: _check(lib.sgp_conn_geo_rows_f64(*head, counts.data_ptr(), None, None, None, _stream(unit)),
+                              "sgp_conn_geo_rows_f64"),
+        lambda rowptr, col, val: _check(lib.sgp_conn_geo_rows_f64(*head, None, rowptr.data_ptr(), col.data_ptr(),
+                                                                  val.data_ptr(), _stream(unit)),
+                                        "sgp_conn_geo_rows_f64"),
+        n, unit.device)
+
+
+@_on_device
+def conn_dense_knn(sim, k, include_self, binary, threshold):
+    """:func:`conn_geo_knn` over the rows of a given similarity (any strides; sgp_conn_dense_knn)."""
+    lib = require_gpu()
+    n, is_f64 = _conn_sim(sim)
+    col = torch.empty(n, k, dtype=torch.int32, device=sim.device)
+    val = torch.empty(n, k, dtype=torch.float64, device=sim.device)
+    _check(lib.sgp_conn_dense_knn(sim.data_ptr(), is_f64, sim.stride(0), sim.stride(1), n, int(k),
+                                  int(bool(include_self)), int(bool(binary)), _conn_threshold(threshold),
+                                  col.data_ptr(), val.data_ptr(), _stream(sim)), "sgp_conn_dense_knn")
+    return col, val
+
+
+@_on_device
+def conn_dense_rows(sim, include_self, binary, threshold):
+    """:func:`conn_geo_rows` over a given similarity (sgp_conn_dense_rows; one host sync)."""
+    lib = require_gpu()
+    n, is_f64 = _conn_sim(sim)
+    head = (sim.data_ptr(), is_f64, sim.stride(0), sim.stride(1), n, int(bool(include_self)), int(bool(binary)),
+            _conn_threshold(threshold))
+    return _conn_rows(
+        lambda counts: _check(lib.sgp_conn_dense_rows(*head, counts.data_ptr(), None, None, None, _stream(sim)),
+                              "sgp_conn_dense_rows"),
+        lambda rowptr, col, val: _check(lib.sgp_conn_dense_rows(*head, None, rowptr.data_ptr(), col.data_ptr(),
+                                                                val.data_ptr(), _stream(sim)), "sgp_conn_dense_rows"),
+        n, sim.device)
+
+
+@_on_device
+def correntropy(x, period, n_chunks, gamma):
+    """``[N, N]`` fp32 mean over the first ``n_chunks`` chunks of ``period`` rows of ``x [T, N]`` (float32 CUDA, unit
+    column stride) of the Gaussian kernel between columns (sgp_correntropy_f32)."""
+    lib = require_gpu()
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError("x: expected a float32 CUDA [T, N] with unit column stride")
+    n = x.shape[1]
+    if n_chunks < 1 or n_chunks * period > x.shape[0]:
+        raise ValueError("correntropy: the chunks exceed the rows of x")
+    norms = torch.empty(n_chunks, n, dtype=torch.float32, device=x.device)
+    out = torch.empty(n, n, dtype=torch.float32, device=x.device)
+    _check(lib.sgp_correntropy_f32(x.data_ptr(), max(x.stride(0), n), n, int(period), int(n_chunks), float(gamma),
+                                   norms.data_ptr(), out.data_ptr(), n, _stream(x)), "sgp_correntropy_f32")
+    return out
 
 
 class Event:
