@@ -699,6 +699,16 @@ int sgp_grouped_linear_wgrad_form(int32_t n_rows, int32_t groups, int32_t ic, in
  * Workspace sizes (bytes, -1 on a bad size): which = 0 colmeans, 1 Gram (n_cols counts the ones column), 2 predict
  * (n_out = horizon x channels).  n_rows = n_steps x n_nodes. */
 int64_t sgp_ridge_workspace_bytes(int32_t which, int64_t n_rows, int32_t n_cols, int32_t n_out);
+/* The launch regime of the three entries for these sizes -- a host-only query (no device call, no stream) computed by
+ * the functions the entries launch with; same arguments as sgp_ridge_workspace_bytes.  out[] (int64):
+ *   which = 0: {row slices, rows per slice}
+ *   which = 1: {nt1 = ceil(n_cols / 128), upper-triangle tiles, row slices, rows per slice (the last slices may be
+ *              short or empty), the most fp32 partials (one per 256 rows) a slice adds into its fp64 slab}
+ *   which = 2: {NT = ceil(n_out / 16), workgroups, the most 64-row blocks a workgroup walks, 32-column panels,
+ *              dynamic LDS bytes}
+ * SGP_EINVAL on a size the entry refuses; SGP_EUNSUP (out[] still filled) where sgp_ridge_predict_score_f32 answers
+ * SGP_EUNSUP: the dynamic LDS plus the kernel's 768 static bytes exceed 160 KiB. */
+int sgp_ridge_form(int32_t which, int64_t n_rows, int32_t n_cols, int32_t n_out, int64_t* out);
 
 /* means[c] = column means of the virtual matrix (fp64; the fp32 values are summed in fp64).
  *   replaces the centring inside sklearn Ridge.fit (run_closed_form.py:195, _preprocess_data) */
@@ -708,7 +718,9 @@ int sgp_ridge_colmeans_f32(const int64_t* segs, int32_t n_segs, const int32_t* s
 /* gram[i * ldg + j] (fp64, both triangles) = Zc^T Zc for Zc = [Z - shift | 1]: shift[c] (fp32, device; NULL = no
  * shift) is subtracted in fp32, the ones column is appended when ones = 1.  EXACT-FP32 contract: the products are
  * v_mfma_f32_32x32x2_f32 (one fp32 rounding per product-add, no reduced-precision inputs) over at most 256 rows, and
- * each such partial is added into fp64.  Only upper-triangle 128 x 128 tiles are computed.
+ * each such partial is added into fp64.  Only upper-triangle 128 x 128 tiles are computed.  Products of two
+ * node-invariant columns (segments of node stride 0, the ones column) would add one value n_nodes times in a row, each
+ * addition rounding the same way; with n_nodes > 1 and such a segment they are n_nodes x the fp64 sum over the steps.
  *   replaces the X^T X + X^T y of the 12 Ridge.fit calls at run_closed_form.py:191-196 (one Gram for every lag: the
  *   targets are columns of the same matrix) */
 int sgp_ridge_gram_f32(const int64_t* segs, int32_t n_segs, const int32_t* steps, int64_t n_steps, int64_t n_nodes,

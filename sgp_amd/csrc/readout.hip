@@ -245,6 +245,50 @@ __global__ void ridge_gram_reduce_kernel(const double* __restrict__ part, int n_
     G[(int64_t)j * ldg + i] = s;
 }
 
+// Node-invariant columns (a segment of node stride 0, the ones column) hold one value for the n_nodes rows of a step.
+// The MFMA partial adds such a pair's product n_nodes times in a row, and every one of those additions rounds the same
+// way: the error grows with the run instead of averaging out (8.6e-7 Sum|a b| measured with 22 such columns over 29
+// nodes).  Their products are therefore redone here as n_nodes x the fp64 sum over the steps, in a fixed order:
+// one workgroup per pair (i <= j) of the `nb` invariant columns, thread t takes steps t, t + 256, ...
+__device__ inline int invariant_col(const Segs& S, int ones, int b) {
+    int col = -1;
+#pragma unroll
+    for (int k = 0; k < kMaxSegs; ++k)
+        if (k < S.n && S.s[k].ns == 0) {
+            if (col < 0 && b >= 0 && b < S.s[k].span) col = S.s[k].col0 + b;
+            b -= S.s[k].span;
+        }
+    if (col < 0 && ones && b == 0) col = S.ncols;
+    return col;
+}
+
+__global__ __launch_bounds__(256) void ridge_gram_invariant_kernel(Segs S, const int32_t* __restrict__ steps,
+                                                                 int64_t n_steps, int64_t n_nodes,
+                                                                 const float* __restrict__ shift, int ones, int nb,
+                                                                 double* __restrict__ G, int64_t ldg) {
+    __shared__ double red[256];
+    const int bi = blockIdx.x / nb, bj = blockIdx.x % nb;
+    if (bi > bj) return;                                     // the whole workgroup
+    const int i = invariant_col(S, ones, bi), j = invariant_col(S, ones, bj);
+    const ColSrc ca = resolve(S, i, ones), cb = resolve(S, j, ones);
+    const float sha = (shift && ca.kind == 0) ? shift[i] : 0.f;
+    const float shb = (shift && cb.kind == 0) ? shift[j] : 0.f;
+    double acc = 0.0;
+    for (int64_t s = threadIdx.x; s < n_steps; s += 256) {
+        const int st = steps[s];
+        acc += (double)fetch(ca, st, 0, sha) * (double)fetch(cb, st, 0, shb);
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int k = 0; k < 256; ++k) t += red[k];
+        t *= (double)n_nodes;
+        G[(int64_t)i * ldg + j] = t;
+        G[(int64_t)j * ldg + i] = t;
+    }
+}
+
 // ------------------------------------------------------------------ predict + score
 struct Score {
     const float* scale;  // inverse scaler, element (n, c) at n * sc_ns + c; nullptr = no inverse transform
@@ -454,15 +498,39 @@ int gram_slices(int64_t n_rows, int n_tiles, int64_t& rows_per_slice) {
     return (int)p;
 }
 
+// fp32 partials a slice of `rows` rows adds into its slab: one per GFLUSH rows, the last one short (an empty slice
+// writes one zero slab)
+int64_t gram_flushes(int64_t rows) {
+    const int64_t nblk = (rows + GKB - 1) / GKB, per = GFLUSH / GKB;
+    return nblk > 0 ? (nblk + per - 1) / per : 1;
+}
+
+// columns ridge_gram_invariant_kernel redoes: those of node stride 0 and the ones column, when rows of one step
+// differ at all (n_nodes > 1) and a segment is among them (the ones column alone sums exactly)
+int gram_invariant_cols(const Segs& S, int ones, int64_t n_nodes) {
+    int nb = 0;
+    for (int k = 0; k < S.n; ++k)
+        if (S.s[k].ns == 0) nb += S.s[k].span;
+    return (n_nodes > 1 && nb > 0) ? nb + ones : 0;
+}
+
 int predict_nt(int hc) { return (hc + 15) / 16; }
+
+int predict_dpad(int ncols) { return (ncols + PKB - 1) / PKB * PKB; }
 
 int64_t predict_lds(int dpad, int nt) {
     const int hcp = 16 * nt;
     return (int64_t)dpad * hcp * 4 + PRB * PLD * 4 + (int64_t)16 * hcp * 4 * 8;
 }
 
+// the kernel's static __shared__ (rstep, rnode, rsidx) counts against the same 160 KiB as the dynamic part
+constexpr int64_t PSTATIC = 3 * PRB * 4;
+bool predict_fits(int64_t lds) { return lds + PSTATIC <= 160 * 1024; }
+
+int64_t predict_blocks(int64_t n_rows) { return (n_rows + PRB - 1) / PRB; }
+
 int64_t predict_grid(int64_t n_rows) {
-    const int64_t nrb = (n_rows + PRB - 1) / PRB;
+    const int64_t nrb = predict_blocks(n_rows);
     return nrb < PGRID ? nrb : PGRID;
 }
 
@@ -481,6 +549,43 @@ int64_t sgp_ridge_workspace_bytes(int32_t which, int64_t n_rows, int32_t n_cols,
     }
     if (which == 2 && n_out >= 1 && n_out <= 64) return predict_grid(n_rows) * 16 * predict_nt(n_out) * 4 * 8;
     return -1;
+}
+
+int sgp_ridge_form(int32_t which, int64_t n_rows, int32_t n_cols, int32_t n_out, int64_t* out) {
+    const char* what = "sgp_ridge_form";
+    SGP_REQUIRE(out, "%s: null pointer", what);
+    SGP_REQUIRE(which >= 0 && which <= 2, "%s: which must be 0, 1 or 2", what);
+    // the entries' own limits: 16384 segment columns (the Gram's count includes its ones column), 2^31 steps x nodes
+    SGP_REQUIRE(n_rows >= 1 && n_cols >= 1 && n_cols <= 16384 + (which == 1), "%s: bad size (%lld rows, %d columns)",
+                what, (long long)n_rows, (int)n_cols);
+    int64_t rps;
+    if (which == 0) {
+        out[0] = cm_slices(n_rows, rps);
+        out[1] = rps;
+        return 0;
+    }
+    if (which == 1) {
+        int nt1;
+        const int nt = gram_tiles(n_cols, nt1);
+        out[2] = gram_slices(n_rows, nt, rps);
+        out[0] = nt1;
+        out[1] = nt;
+        out[3] = rps;
+        out[4] = gram_flushes(rps < n_rows ? rps : n_rows);          // slice 0 is never shorter than another
+        return 0;
+    }
+    SGP_REQUIRE(n_out >= 1 && n_out <= 64, "%s: horizon x channels must be 1 .. 64", what);
+    const int nt = predict_nt(n_out), dpad = predict_dpad(n_cols);
+    const int64_t lds = predict_lds(dpad, nt), grid = predict_grid(n_rows);
+    out[0] = nt;
+    out[1] = grid;
+    out[2] = (predict_blocks(n_rows) + grid - 1) / grid;
+    out[3] = dpad / PKB;
+    out[4] = lds;
+    if (!predict_fits(lds))
+        return sgp::fail(SGP_EUNSUP, "%s: %d features x %d outputs need %lld bytes of LDS (at most 160 KiB)", what,
+                         (int)n_cols, (int)n_out, (long long)lds);
+    return 0;
 }
 
 int sgp_ridge_colmeans_f32(const int64_t* segs, int32_t n_segs, const int32_t* steps, int64_t n_steps,
@@ -531,6 +636,11 @@ int sgp_ridge_gram_f32(const int64_t* segs, int32_t n_segs, const int32_t* steps
     const int64_t n_el = (int64_t)nt * GTILE;
     hipLaunchKernelGGL(ridge_gram_reduce_kernel, dim3((unsigned)((n_el + 255) / 256)), dim3(256), 0, st, part, p, nt,
                        nt1, mp, gram, ldg);
+    if (int rc = sgp::check_launch(what)) return rc;
+    const int nb = gram_invariant_cols(S, ones, n_nodes);
+    if (nb == 0) return 0;
+    hipLaunchKernelGGL(ridge_gram_invariant_kernel, dim3((unsigned)((int64_t)nb * nb)), dim3(256), 0, st, S, steps,
+                       n_steps, n_nodes, shift, ones, nb, gram, ldg);
     return sgp::check_launch(what);
 }
 
@@ -553,9 +663,9 @@ int sgp_ridge_predict_score_f32(const int64_t* segs, int32_t n_segs, const int32
     SGP_REQUIRE(sc_node_stride >= 0 && y_ss >= 0 && y_ns >= 0 && m_ss >= 0 && m_ns >= 0 && m_cs >= 0,
                 "%s: negative stride", what);
     const int hc = horizon * channels, nt = predict_nt(hc);
-    const int dpad = (S.ncols + PKB - 1) / PKB * PKB;
+    const int dpad = predict_dpad(S.ncols);
     const int64_t lds = predict_lds(dpad, nt);
-    if (lds > 160 * 1024)
+    if (!predict_fits(lds))
         return sgp::fail(SGP_EUNSUP, "%s: %d features x %d outputs need %lld bytes of LDS (at most 160 KiB)", what,
                          S.ncols, hc, (long long)lds);
     const int64_t n_rows = n_steps * n_nodes;

@@ -170,6 +170,7 @@ SIGNATURES = {
     "sgp_spmm_colblock_rows_cap": (c_i32, []),
     "sgp_spmm_colblock_round_pad": (c_i32, []),
     "sgp_ridge_workspace_bytes": (c_i64, [c_i32, c_i64, c_i32, c_i32]),
+    "sgp_ridge_form": (ctypes.c_int, [c_i32, c_i64, c_i32, c_i32, c_p]),
     "sgp_ridge_colmeans_f32": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p]),
     "sgp_ridge_gram_f32": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_i64, c_p, c_i32, c_p, c_i64, c_p, c_i64, c_p]),
     "sgp_ridge_predict_score_f32": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i32, c_i32,
@@ -2066,6 +2067,26 @@ def ridge_workspace(which, n_rows, n_cols, n_out, device):
     if nbytes < 0:
         raise ValueError(f"ridge readout: no workspace for {n_rows} rows x {n_cols} columns")
     return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+_RIDGE_FORM_KEYS = {"colmeans": (0, ("slices", "rows_per_slice")),
+                    "gram": (1, ("nt1", "tiles", "slices", "rows_per_slice", "flushes")),
+                    "predict": (2, ("nt", "grid", "blocks_per_wg", "panels", "lds_bytes"))}
+
+
+def ridge_form(which, n_rows, n_cols, n_out=0):
+    """The launch regime of ``ridge_colmeans`` / ``ridge_gram`` (``n_cols`` counts the ones column) /
+    ``ridge_predict_score`` (``n_out`` = horizon x channels) for these sizes, as a dict (host only: ``sgp_ridge_form``).
+    ``which``: "colmeans", "gram", "predict" or 0, 1, 2.  Raises as the entry would: ValueError on a bad size,
+    NotImplementedError where predict's W does not fit in LDS."""
+    idx = _RIDGE_FORM_KEYS[which][0] if which in _RIDGE_FORM_KEYS else int(which)
+    keys = next((k for i, k in _RIDGE_FORM_KEYS.values() if i == idx), ())
+    out = (c_i64 * 5)()
+    rc = load().sgp_ridge_form(idx, int(n_rows), int(n_cols), int(n_out), ctypes.addressof(out))
+    if rc == SGP_EINVAL:
+        raise ValueError(f"ridge_form: {load().sgp_last_error().decode()}")
+    _check(rc, "sgp_ridge_form")
+    return {k: int(out[i]) for i, k in enumerate(keys)}
 
 
 @_on_device
