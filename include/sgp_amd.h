@@ -1186,6 +1186,41 @@ int sgp_conn_dense_rows(const void* sim, int32_t is_f64, int64_t row_stride, int
 int sgp_correntropy_f32(const float* x, int64_t x_row_stride, int32_t n, int32_t period, int32_t n_chunks, double gamma,
                         float* norms, float* out, int64_t out_row_stride, sgp_stream_t stream);
 
+/* --------------------------------------------------------- scalers ---
+ * Fits of tsl's StandardScaler / MinMaxScaler / RobustScaler and the fused transform.  x is a row-major fp32 [m, g]
+ * matrix: m reduced rows, g groups (one bias / scale each).  mask: NULL or bytes (non-zero = counts), indexed as
+ * flat_index / mask_div (mask_div divides g: 1 = a mask of x's shape, C = tsl's [T, N, 1] mask over C channels).  An
+ * element counts iff its mask byte is set and it is not NaN.
+ *
+ * Launch regime (sgp_amd.scalers.launch_plan): regime 0 "long" (g <= 8): rows_per_wg rows per workgroup, fp64 partials
+ * added by a second stage in a fixed order, global integer histograms; needs ws of sgp_scaler_workspace_bytes.
+ * regime 1 "many": a workgroup owns tile_cols (16 | 32 | 64) adjacent columns, everything in LDS; ws may be NULL.
+ *
+ * moments: stats [6, g] fp64 = count | mean | sum of squared deviations from the mean (want_var; else 0) | min | max |
+ *   1 where an unmasked NaN was seen.  Two passes (the second for want_var); no float atomics, fixed summation order.
+ * select: exact order statistics ostat [g, 6] = the elements of rank floor / ceil of the virtual indices
+ *   q / 100 * (count - 1) for q = q_lo, q_mid, q_hi (numpy's linear method), the count taken from stats on the device.
+ *   Radix select on order-preserving keys: 4 passes of 8-bit digits (long) or 8 of 4-bit digits (many).
+ * finish: kind 0 standard (bias = mean, scale = population std), 1 min-max (p0 < p1: the output range), 2 robust
+ *   (p0, p1: the quantile range given to select, bias = median; adjust: 0 or the unit-variance divisor); fp64, rounded
+ *   to fp32 once; |scale| <= 10 * 2^-23 becomes 1; an empty group, or without a mask (has_mask = 0) a group that held a
+ *   NaN, gets bias = scale = NaN.  bias / scale: [g] fp32.
+ * apply: out[i] = (x[i] - bias[i % n_params]) / scale[i % n_params] + 5e-8, or with `inverse`
+ *   x[i] * (scale[..] + 5e-8) + bias[..]; unfused fp32 with IEEE division (bit-equal to torch's evaluation); out may
+ *   be x.
+ *   replaces Scaler.transform / inverse_transform and the numpy fits of tsl/data/preprocessing/scalers.py:114-283 */
+int64_t sgp_scaler_workspace_bytes(int64_t m, int64_t g, int32_t regime, int64_t rows_per_wg);
+int sgp_scaler_moments_f32(const float* x, const uint8_t* mask, int64_t mask_div, int64_t m, int64_t g, int32_t want_var,
+                           int32_t regime, int64_t rows_per_wg, int32_t tile_cols, double* stats, void* ws,
+                           int64_t ws_bytes, sgp_stream_t stream);
+int sgp_scaler_select_f32(const float* x, const uint8_t* mask, int64_t mask_div, int64_t m, int64_t g, const double* stats,
+                          double q_lo, double q_mid, double q_hi, int32_t regime, int64_t rows_per_wg, int32_t tile_cols,
+                          float* ostat, void* ws, int64_t ws_bytes, sgp_stream_t stream);
+int sgp_scaler_finish_f32(int32_t kind, const double* stats, const float* ostat, int64_t g, int32_t has_mask, double p0,
+                          double p1, double adjust, float* bias, float* scale, sgp_stream_t stream);
+int sgp_scaler_apply_f32(const float* x, float* out, const float* bias, const float* scale, int64_t n, int64_t n_params,
+                         int32_t inverse, sgp_stream_t stream);
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

@@ -9,6 +9,7 @@ from .graph import ShiftOperator
 from .nn.encoders import GESNEncoder, SGPEncoder, SGPSpatialEncoder, SGPTemporalEncoder
 from .nn.reservoir import GESNLayer, GraphESN, Reservoir, ReservoirLayer
 from .readout import RidgeReadout, closed_form_readout
+from .scalers import MinMaxScaler, RobustScaler, Scaler, StandardScaler
 from .metrics import (MaskedMAE, MaskedMAPE, MaskedMRE, MaskedMSE, MetricSet, masked_loss, masked_mae, masked_mape,
                       masked_mse)
 from .optim import FusedAdam

@@ -258,6 +258,13 @@ SIGNATURES = {
     "sgp_conn_dense_rows": (ctypes.c_int, [c_p, c_i32, c_i64, c_i64, c_i64, c_i32, c_i32, c_f64, c_p, c_p, c_p, c_p,
                                            c_p]),
     "sgp_correntropy_f32": (ctypes.c_int, [c_p, c_i64, c_i32, c_i32, c_i32, c_f64, c_p, c_p, c_i64, c_p]),
+    "sgp_scaler_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i64]),
+    "sgp_scaler_moments_f32": (ctypes.c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_i32, c_i64, c_i32, c_p, c_p, c_i64,
+                                              c_p]),
+    "sgp_scaler_select_f32": (ctypes.c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_f64, c_f64, c_f64, c_i32, c_i64, c_i32,
+                                             c_p, c_p, c_i64, c_p]),
+    "sgp_scaler_finish_f32": (ctypes.c_int, [c_i32, c_p, c_p, c_i64, c_i32, c_f64, c_f64, c_f64, c_p, c_p, c_p]),
+    "sgp_scaler_apply_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p]),
     "sgp_event_create": (ctypes.c_int, [ctypes.POINTER(c_p)]),
     "sgp_event_destroy": (ctypes.c_int, [c_p]),
     "sgp_event_record": (ctypes.c_int, [c_p, c_p]),
