@@ -13,19 +13,19 @@
 //                          needs its neighbours' previous hop is the next launch in stream order.
 //   sgp_dcrnn_gates_f32    [r | u] = sigmoid(Dh Wh_ru^T + G[:, 0 : 2 H]); stores r, u and r * h (slot 0 of Drh).
 //   sgp_dcrnn_update_f32   c = tanh(Drh Wh_c^T + G[:, 2 H : 3 H]), h' = u h + (1 - u) c.
-//                          Both are the dense kernel of decoder_mlp.hip (v_mfma_f32_16x16x4_f32, exact fp32 products, the
-//                          weight tile of a k chunk staged in LDS once per workgroup, rows in registers) with the cell's
-//                          elementwise step as the epilogue in the accumulator layout.
+//                          Both are the stage loop of dense_tile.h over plain rows of the concat buffer, with the
+//                          cell's elementwise step as the epilogue in the accumulator layout.
 //   sgp_dcrnn_bwd_f32      the elementwise half of one reversed step, two phases.
 //
 // Everything else of a step (d concat = dz W, the weight gradients) is sgp_dense_f32 / sgp_dense_wgrad_f32.
 #include "common.h"
-#include "reservoir_impl.h"
+#include "dense_tile.h"
+#include "device_math.h"
 
 namespace {
 using sgp::f32x4;
-
-__device__ __forceinline__ float sigmoid_f32(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
+using sgp::sigmoid_f32;
+using namespace sgp_dense;
 
 const char* domain_error(int H, int k) {
     if (H < 16 || H > 128 || H % 16 != 0) return "hidden size must be a multiple of 16 in 16 .. 128";
@@ -87,65 +87,39 @@ struct CellArgs {
     int n_rows, H, K;
 };
 
-constexpr int KCH = 4;                    // k blocks of 16 per LDS stage
-constexpr int JTW = 4;                    // 16-column tiles per workgroup
-
 // MODE 0: gates (n_out = 2 H), MODE 1: update (n_out = H).  64 rows x 64 output columns per workgroup.
 template <int MODE>
 __global__ __launch_bounds__(256) void cell_kernel(CellArgs a) {
-    __shared__ f32x4 wl[JTW * KCH * 64];
+    __shared__ f32x4 wl[DT_LDS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = lane & 15, q = lane >> 4;
     const int n_out = MODE == 0 ? 2 * a.H : a.H;
     const int JT = n_out / 16, KB = a.K / 16;
-    const int jt0 = blockIdx.y * JTW;
+    const int jt0 = blockIdx.y * DT_TILES;
     const long long row = (long long)blockIdx.x * 64 + wave * 16 + b;
     const bool ok = row < a.n_rows;
     const float* xp = a.d + (ok ? row : 0) * a.drs;
-    f32x4 acc[JTW];
-#pragma unroll
-    for (int c = 0; c < JTW; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int kb0 = 0; kb0 < KB; kb0 += KCH) {
-        f32x4 xv[KCH];
-#pragma unroll
-        for (int u = 0; u < KCH; ++u) {
-            const int kk = 16 * (kb0 + u) + 4 * q;
-            xv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (ok && kk < a.K) xv[u] = *reinterpret_cast<const f32x4*>(xp + kk);
-        }
-        __syncthreads();                                             // previous stage fully consumed
-        for (int i = threadIdx.x; i < JTW * KCH * 64; i += 256) {
-            const int l = i & 63, u = (i >> 6) % KCH, c = i / (64 * KCH);
+    f32x4 acc[1][DT_TILES];
+    dense_tile_loop<1>(
+        wl, a.wp, KB,
+        [xp, ok, q, K = a.K](int, int kb) {
+            const int kk = 16 * kb + 4 * q;
             f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (jt0 + c < JT && kb0 + u < KB)
-                v = *reinterpret_cast<const f32x4*>(a.wp + (((long long)(jt0 + c) * KB + kb0 + u) * 64 + l) * 4);
-            wl[i] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < KCH; ++u) {
-            if (kb0 + u >= KB) break;                                // wave-uniform
-#pragma unroll
-            for (int c = 0; c < JTW; ++c) {
-                const f32x4 wf = wl[(c * KCH + u) * 64 + lane];
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s], xv[u][s], acc[c], 0, 0, 0);
-            }
-        }
-    }
+            if (ok && kk < K) v = *reinterpret_cast<const f32x4*>(xp + kk);
+            return v;
+        },
+        [jt0, JT](int c) { return jt0 + c < JT ? jt0 + c : -1; }, acc);
     if (!ok) return;
     // D[col, row]: lane (q, b), register r -> column 16 (jt0 + c) + 4 q + r of row 16 wave + b
 #pragma unroll
-    for (int c = 0; c < JTW; ++c) {
+    for (int c = 0; c < DT_TILES; ++c) {
         const int col0 = 16 * (jt0 + c) + 4 * q;
         if (col0 >= n_out) continue;
         if (MODE == 0) {
             const f32x4 gx = *reinterpret_cast<const f32x4*>(a.g + row * a.grs + col0);
             f32x4 z;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) z[r] = sigmoid_f32(acc[c][r] + gx[r]);
+            for (int r = 0; r < 4; ++r) z[r] = sigmoid_f32(acc[0][c][r] + gx[r]);
             *reinterpret_cast<f32x4*>(a.ruc + row * a.rrs + col0) = z;
             if (col0 < a.H) {                                         // the r half: r * h into slot 0 of Drh
                 const f32x4 hv = *reinterpret_cast<const f32x4*>(a.h + row * a.hrs + col0);
@@ -158,7 +132,7 @@ __global__ __launch_bounds__(256) void cell_kernel(CellArgs a) {
             f32x4 cv, hn;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                cv[r] = sgp_res::tanh_f32(acc[c][r] + gx[r]);
+                cv[r] = sgp_res::tanh_f32(acc[0][c][r] + gx[r]);
                 hn[r] = uv[r] * hv[r] + (1.f - uv[r]) * cv[r];
             }
             *reinterpret_cast<f32x4*>(a.ruc + row * a.rrs + 2 * a.H + col0) = cv;

@@ -4,9 +4,8 @@
 // and backward, plus the MaskedMAE loss the experiments train with (tsl/nn/metrics/metric_base.py:79-96).
 //
 //   sgp_dense_f32         Y = epilogue(X . M^T): one kernel for every forward layer and every dX of the backward
-//                         pass.  v_mfma_f32_16x16x4_f32 (exact fp32 products), a workgroup = 4 waves x RT row tiles
-//                         of 16 rows (64 or 128 rows) x 64 output columns; the weight tile of each 64-wide k chunk is
-//                         staged in LDS once and serves all the workgroup's rows.
+//                         pass.  The stage loop of dense_tile.h over a workgroup's 64 or 128 rows (gathered, with a
+//                         scalar tail where a row cannot be read 16 bytes at a time) x 64 output columns.
 //   sgp_dense_wgrad_f32   dM = dZ^T X (+ db = column sums of dZ through a virtual ones column of X): the rows are the
 //                         contraction index; every row slice writes its own partial, a second kernel adds the
 //                         slices in slice order in fp64 -- no float atomics, the gradients are bit-identical run to run.
@@ -15,17 +14,14 @@
 //   sgp_masked_mae_f32 / _bwd_f32   the loss and its gradient, one kernel each, fp64 sums.
 #include "common.h"
 #include "decoder_ops.h"
+#include "dense_tile.h"
 
 using sgp::f32x4;
 
 namespace {
+using namespace sgp_dense;
 
-// packed M[N, K]: Mp[jt][kb][lane][s] = M[16 jt + (l & 15)][16 kb + 4 (l >> 4) + s] (zero outside), the A operand of
-// 4 consecutive MFMAs whose B operand is a lane's 16-byte piece of its row (the layout of decoder.hip).
-__host__ __device__ inline long long dense_packed_floats(int n_out, int k) {
-    return (long long)((n_out + 15) / 16) * ((k + 15) / 16) * 256;
-}
-
+// writes the packed layout described in dense_tile.h
 __global__ void dense_pack(const float* __restrict__ w, long long w_rs, int transpose, int n_out, int k,
                            float* __restrict__ out) {
     const int KB = (k + 15) / 16;
@@ -63,16 +59,13 @@ struct DenseArgs {
     bool xvec;
 };
 
-constexpr int DN_KCH = 4;             // k blocks of 16 per LDS stage
-constexpr int DN_JT = 4;              // 16-column tiles per workgroup (64 columns)
-
 template <int RT>
 __global__ __launch_bounds__(256) void dense_kernel(DenseArgs a) {
-    __shared__ f32x4 wl[DN_JT * DN_KCH * 64];                       // 16 KB: 64 columns x 64 k of M
+    __shared__ f32x4 wl[DT_LDS];                                    // 16 KB: 64 columns x 64 k of M
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = lane & 15, q = lane >> 4;
     const int JT = (a.n_out + 15) / 16, KB = (a.k + 15) / 16;
-    const int jt0 = blockIdx.y * DN_JT;
+    const int jt0 = blockIdx.y * DT_TILES;
     const long long row_base = (long long)blockIdx.x * (64 * RT) + wave * (16 * RT);
     const float* xp[RT];
     bool ok[RT];
@@ -82,53 +75,23 @@ __global__ __launch_bounds__(256) void dense_kernel(DenseArgs a) {
         ok[t] = row < a.n_rows;
         xp[t] = ok[t] ? a.x + source_row(a.gidx, a.row_mod, row) * a.xrs : a.x;
     }
-    f32x4 acc[RT][DN_JT];
-#pragma unroll
-    for (int t = 0; t < RT; ++t)
-#pragma unroll
-        for (int c = 0; c < DN_JT; ++c) acc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int kb0 = 0; kb0 < KB; kb0 += DN_KCH) {
-        f32x4 xv[RT][DN_KCH];                                        // row pieces first: in flight across the barrier
-#pragma unroll
-        for (int t = 0; t < RT; ++t) {
-#pragma unroll
-            for (int u = 0; u < DN_KCH; ++u) {
-                const int kk = 16 * (kb0 + u) + 4 * q;
-                xv[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (ok[t] && kk < a.k) {
-                    if (a.xvec) xv[t][u] = *reinterpret_cast<const f32x4*>(xp[t] + kk);
-                    else {
-#pragma unroll
-                        for (int s = 0; s < 4; ++s)
-                            if (kk + s < a.k) xv[t][u][s] = xp[t][kk + s];
-                    }
-                }
-            }
-        }
-        __syncthreads();                                             // previous stage fully consumed
-        for (int i = threadIdx.x; i < DN_JT * DN_KCH * 64; i += 256) {
-            const int l = i & 63, u = (i >> 6) % DN_KCH, c = i / (64 * DN_KCH);
+    f32x4 acc[RT][DT_TILES];
+    dense_tile_loop<RT>(
+        wl, a.wp, KB,
+        [xp, ok, q, k = a.k, xvec = a.xvec](int t, int kb) {
+            const int kk = 16 * kb + 4 * q;
             f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (jt0 + c < JT && kb0 + u < KB)
-                v = *reinterpret_cast<const f32x4*>(a.wp + (((long long)(jt0 + c) * KB + kb0 + u) * 64 + l) * 4);
-            wl[i] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < DN_KCH; ++u) {
-            if (kb0 + u >= KB) break;                                // wave-uniform
-#pragma unroll
-            for (int c = 0; c < DN_JT; ++c) {
-                const f32x4 wf = wl[(c * DN_KCH + u) * 64 + lane];
-#pragma unroll
-                for (int t = 0; t < RT; ++t)
+            if (ok[t] && kk < k) {
+                if (xvec) v = *reinterpret_cast<const f32x4*>(xp[t] + kk);
+                else {
 #pragma unroll
                     for (int s = 0; s < 4; ++s)
-                        acc[t][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s], xv[t][u][s], acc[t][c], 0, 0, 0);
+                        if (kk + s < k) v[s] = xp[t][kk + s];
+                }
             }
-        }
-    }
+            return v;
+        },
+        [jt0, JT](int c) { return jt0 + c < JT ? jt0 + c : -1; }, acc);
     // D[col, row]: lane (q, b), register r -> column 16 (jt0 + c) + 4 q + r, row 16 t + b
 #pragma unroll
     for (int t = 0; t < RT; ++t) {
@@ -136,7 +99,7 @@ __global__ __launch_bounds__(256) void dense_kernel(DenseArgs a) {
         const long long row = row_base + 16 * t + b;
         const long long orow = (row / a.o_rdiv) * a.o_r0 + (row % a.o_rdiv) * a.o_r1;
 #pragma unroll
-        for (int c = 0; c < DN_JT; ++c) {
+        for (int c = 0; c < DT_TILES; ++c) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int col = 16 * (jt0 + c) + 4 * q + r;
@@ -357,6 +320,7 @@ int sgp_dense_f32(const float* X, int64_t x_row_stride, const int32_t* gather, i
     SGP_REQUIRE(dropout_p == 0.0 || drop_width >= n_act, "sgp_dense_f32: drop_width below n_act");
     SGP_REQUIRE(out_map[0] > 0 && out_map[3] > 0, "sgp_dense_f32: out_map divisors must be positive");
     SGP_REQUIRE(sgp::aligned16(w_packed), "sgp_dense_f32: packed weights must be 16-byte aligned");
+    SGP_REQUIRE(dense_packed_floats(n_out, k) / 256 <= 0x7fffffffll, "sgp_dense_f32: packed weights too large");
     if (n_rows == 0) return 0;
     DenseArgs a;
     a.x = X; a.xrs = x_row_stride; a.gidx = gather; a.row_mod = row_mod;
@@ -372,7 +336,7 @@ int sgp_dense_f32(const float* X, int64_t x_row_stride, const int32_t* gather, i
     int32_t rows_per_wg, xvec;
     sgp_dense_form(n_rows, n_out, k, x_row_stride, sgp::aligned16(X) ? 1 : 0, &rows_per_wg, &xvec);   // sizes checked above
     a.xvec = xvec != 0;
-    const int gy = (n_out + 16 * DN_JT - 1) / (16 * DN_JT);
+    const int gy = (n_out + 16 * DT_TILES - 1) / (16 * DT_TILES);
     SGP_REQUIRE(gy <= 65535, "sgp_dense_f32: too many output columns");
     hipStream_t s = (hipStream_t)stream;
     const unsigned gx = (unsigned)(((long long)n_rows + rows_per_wg - 1) / rows_per_wg);
@@ -385,7 +349,7 @@ int sgp_dense_form(int32_t n_rows, int32_t n_out, int32_t k, int64_t x_row_strid
                    int32_t* rows_per_wg, int32_t* xvec) {
     SGP_REQUIRE(n_rows >= 0 && k > 0 && n_out > 0 && x_row_stride >= k, "sgp_dense_form: bad size");
     // 128 rows per workgroup when that still gives the chip two workgroups per CU, 64 otherwise
-    const long long g128 = ((long long)n_rows + 127) / 128, gy = (n_out + 16 * DN_JT - 1) / (16 * DN_JT);
+    const long long g128 = ((long long)n_rows + 127) / 128, gy = (n_out + 16 * DT_TILES - 1) / (16 * DT_TILES);
     if (rows_per_wg) *rows_per_wg = g128 * gy >= 512 ? 128 : 64;
     if (xvec) *xvec = (k % 4 == 0 && x_row_stride % 4 == 0 && x_aligned16) ? 1 : 0;
     return 0;

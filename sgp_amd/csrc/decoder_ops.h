@@ -4,6 +4,7 @@
 // scheme and the backward passes recompute it instead of storing it.
 #pragma once
 #include "common.h"
+#include "device_math.h"
 
 namespace {
 
@@ -27,13 +28,13 @@ __device__ __forceinline__ float keep_factor(unsigned long long idx, unsigned th
 
 __device__ __forceinline__ float activate(float v, int act) {
     if (act == 1) return fmaxf(v, 0.f);                                   // relu
-    if (act == 2) return v * __builtin_amdgcn_rcpf(1.f + __expf(-v));     // silu = x * sigmoid(x)
+    if (act == 2) return v * sgp::sigmoid_f32(v);                        // silu = x * sigmoid(x)
     return v;
 }
 
 __device__ __forceinline__ float dactivate(float z, int act) {
     if (act == 1) return z > 0.f ? 1.f : 0.f;
-    if (act == 2) { const float sg = __builtin_amdgcn_rcpf(1.f + __expf(-z)); return sg * (1.f + z * (1.f - sg)); }
+    if (act == 2) { const float sg = sgp::sigmoid_f32(z); return sg * (1.f + z * (1.f - sg)); }
     return 1.f;
 }
 

@@ -23,6 +23,7 @@
 #include "decoder_ops.h"
 
 using sgp::f32x4;
+using sgp::sigmoid_f32;
 
 namespace {
 
@@ -70,8 +71,6 @@ __device__ __forceinline__ void store_piece(float* row, int col, int width, bool
             if (col + s < width) row[col + s] = v[s];
     }
 }
-
-__device__ __forceinline__ float sigmoidf(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
 
 __device__ __forceinline__ f32x4 sum16(f32x4 v) {            // over the 16 edge lanes, fixed tree
 #pragma unroll
@@ -142,7 +141,7 @@ __global__ __launch_bounds__(64 * GG_WAVES) void edge_fwd(GgArgs a) {
             }
         dot += __shfl_xor(dot, 16);
         dot += __shfl_xor(dot, 32);
-        const float g = valid ? sigmoidf(dot + bg) : 0.f;
+        const float g = valid ? sigmoid_f32(dot + bg) : 0.f;
 #pragma unroll
         for (int ot = 0; ot < HT; ++ot)
 #pragma unroll
@@ -177,7 +176,7 @@ __global__ void fix_rows(const float* __restrict__ part, const int* __restrict__
 
 __device__ __forceinline__ void act_both(float z, int act, float& m, float& d) {
     if (act == 1) { m = fmaxf(z, 0.f); d = z > 0.f ? 1.f : 0.f; }
-    else if (act == 2) { const float sg = sigmoidf(z); m = z * sg; d = sg * (1.f + z * (1.f - sg)); }
+    else if (act == 2) { const float sg = sigmoid_f32(z); m = z * sg; d = sg * (1.f + z * (1.f - sg)); }
     else { m = z; d = 1.f; }
 }
 
@@ -264,7 +263,7 @@ __global__ __launch_bounds__(64 * GG_WAVES) void edge_bwd(GgArgs a) {
                 }
                 dotg += __shfl_xor(dotg, 16); dotg += __shfl_xor(dotg, 32);
                 dotd += __shfl_xor(dotd, 16); dotd += __shfl_xor(dotd, 32);
-                const float g = valid ? sigmoidf(dotg + bg) : 0.f;
+                const float g = valid ? sigmoid_f32(dotg + bg) : 0.f;
                 const float dgp = valid ? dotd * g * (1.f - g) : 0.f;     // gradient at the gate's pre-activation
                 if (q == 0) dbg += dgp;
 #pragma unroll

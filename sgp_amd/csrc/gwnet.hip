@@ -4,8 +4,8 @@
 // res[:, -S:] a contiguous suffix.
 //
 //   sgp_gwnet_tconv_f32       gated dilated temporal convolution: [a | g] = sum_j W_j x[r + j d M] + bias, y = tanh(a) *
-//                             sigmoid(g).  The dense kernel of decoder_mlp.hip with the taps as extra k chunks; column c
-//                             of a and of g sit in the same lane and register, so the gate is lane-local.
+//                             sigmoid(g).  The stage loop of dense_tile.h with the taps as extra k chunks; column c of a
+//                             and of g sit in the same lane and register, so the gate is lane-local.
 //   sgp_gwnet_tconv_bwd_f32   dz = [dy s (1 - t^2) | dy t s (1 - s)] over the saved [tanh a | sigmoid g]; the products of
 //                             the backward pass are sgp_dense_f32 / sgp_dense_wgrad_f32 per tap.
 //   sgp_adj_apply_f32         Y[i] (+)= A X[i] (or A^T X[i]) for a dense shared [n, n] operator: a workgroup owns 64 or
@@ -19,13 +19,13 @@
 //
 // Exact fp32 products (v_mfma_f32_16x16x4_f32), no float atomics, every sum has one fixed order.
 #include "common.h"
-#include "reservoir_impl.h"
 #include "decoder_ops.h"
+#include "dense_tile.h"
 
 namespace {
 using sgp::f32x4;
-
-__device__ __forceinline__ float sigmoid_f32(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
+using sgp::sigmoid_f32;
+using namespace sgp_dense;
 
 const char* domain_error(int H, int Kt) {
     if (H < 16 || H > 128 || H % 16 != 0) return "hidden size must be a multiple of 16 in 16 .. 128";
@@ -48,12 +48,10 @@ struct TcArgs {
     long long n_rows; int H, Kt;
 };
 
-constexpr int TC_KCH = 4;                         // k blocks of 16 per LDS stage
-
 // 64 rows x 32 columns of y per workgroup: LDS tiles 0, 1 are the a half's column tiles ct0, ct0 + 1, tiles 2, 3 the g
-// half's, so acc[c] and acc[c + 2] hold the same (row, column) of a and g.
+// half's, so acc[0][c] and acc[0][c + 2] hold the same (row, column) of a and g.
 __global__ __launch_bounds__(256) void tconv_kernel(TcArgs a) {
-    __shared__ f32x4 wl[4 * TC_KCH * 64];
+    __shared__ f32x4 wl[DT_LDS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = lane & 15, q = lane >> 4;
     const int HT = a.H / 16, KB = a.Kt * HT;
@@ -61,43 +59,22 @@ __global__ __launch_bounds__(256) void tconv_kernel(TcArgs a) {
     const long long row = (long long)blockIdx.x * 64 + wave * 16 + b;
     const bool ok = row < a.n_rows;
     const float* xp = a.x + (ok ? row : 0) * a.xrs;
-    f32x4 acc[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int kb0 = 0; kb0 < KB; kb0 += TC_KCH) {
-        f32x4 xv[TC_KCH];
-#pragma unroll
-        for (int u = 0; u < TC_KCH; ++u) {
-            const int kb = kb0 + u;
-            xv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[1][DT_TILES];
+    dense_tile_loop<1>(
+        wl, a.wp, KB,
+        [xp, ok, q, HT, KB, tap_rows = a.tap_rows, xrs = a.xrs](int, int kb) {
+            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
             if (ok && kb < KB) {
                 const int tap = kb / HT, col = 16 * (kb % HT) + 4 * q;
-                xv[u] = *reinterpret_cast<const f32x4*>(xp + (long long)tap * a.tap_rows * a.xrs + col);
+                v = *reinterpret_cast<const f32x4*>(xp + (long long)tap * tap_rows * xrs + col);
             }
-        }
-        __syncthreads();                                             // previous stage fully consumed
-        for (int i = threadIdx.x; i < 4 * TC_KCH * 64; i += 256) {
-            const int l = i & 63, u = (i >> 6) % TC_KCH, c = i / (64 * TC_KCH);
-            const int ct = ct0 + (c & 1), jt = (c >> 1) * HT + ct;
-            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (ct < HT && kb0 + u < KB)
-                v = *reinterpret_cast<const f32x4*>(a.wp + (((long long)jt * KB + kb0 + u) * 64 + l) * 4);
-            wl[i] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < TC_KCH; ++u) {
-            if (kb0 + u >= KB) break;                                // wave-uniform
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const f32x4 wf = wl[(c * TC_KCH + u) * 64 + lane];
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s], xv[u][s], acc[c], 0, 0, 0);
-            }
-        }
-    }
+            return v;
+        },
+        [ct0, HT](int c) {
+            const int ct = ct0 + (c & 1);
+            return ct < HT ? (c >> 1) * HT + ct : -1;
+        },
+        acc);
     if (!ok) return;
     // D[col, row]: lane (q, b), register r -> column 16 ct + 4 q + r of row b
 #pragma unroll
@@ -108,8 +85,8 @@ __global__ __launch_bounds__(256) void tconv_kernel(TcArgs a) {
         f32x4 tv, sv;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            tv[r] = sgp_res::tanh_f32(acc[c][r] + a.bias[col0 + r]);
-            sv[r] = sigmoid_f32(acc[c + 2][r] + a.bias[a.H + col0 + r]);
+            tv[r] = sgp_res::tanh_f32(acc[0][c][r] + a.bias[col0 + r]);
+            sv[r] = sigmoid_f32(acc[0][c + 2][r] + a.bias[a.H + col0 + r]);
         }
         *reinterpret_cast<f32x4*>(a.y + row * a.yrs + col0) = tv * sv;
         if (a.act) {

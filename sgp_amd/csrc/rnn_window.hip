@@ -23,21 +23,21 @@
 // and backward are bit-identical from run to run and independent of which tile a sequence falls into.
 #include "common.h"
 #include "decoder_ops.h"
-#include "reservoir_impl.h"
+#include "device_math.h"
 
 namespace {
 using sgp::f32x4;
+using sgp::sigmoid_f32;
+using sgp::ld4;
+using sgp::st4;
 
 constexpr int CELL_LSTM = 0, CELL_GRU = 1;
 constexpr int kPad = 4;                                     // floats of padding per LDS row (keeps rows 16-byte aligned)
 
-__device__ __forceinline__ float sigmoid_f32(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
 __device__ __forceinline__ f32x4 sigmoid4(f32x4 v) { return f32x4{sigmoid_f32(v[0]), sigmoid_f32(v[1]), sigmoid_f32(v[2]), sigmoid_f32(v[3])}; }
 __device__ __forceinline__ f32x4 tanh4(f32x4 v) {
     return f32x4{sgp_res::tanh_f32(v[0]), sgp_res::tanh_f32(v[1]), sgp_res::tanh_f32(v[2]), sgp_res::tanh_f32(v[3])};
 }
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 // ---- packed W_hh (floats): forward part, then backward part, G H H each ---------------------------------------
 //   fwd [G JT row tiles][JT kb][64 lanes][4 s] = W_hh[16 rt + (l & 15)][16 kb + 4 (l >> 4) + s]

@@ -14,16 +14,16 @@
 //                   per 16 edges and handed round the row with row_ror, so the only LDS
 //                   traffic in the inner loop is one ds_read_b128 per (edge, 4 features).
 #include "common.h"
+#include "device_math.h"
 #include <stdlib.h>
 
 using sgp::f32x4;
+using sgp::ld4;
+using sgp::st4;
 
 namespace {
 
 constexpr int kWave = 64;
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 struct Src {                      // where column c of step b lives
     const float* x;  long long xrs, xbs;
