@@ -1221,6 +1221,47 @@ int sgp_scaler_finish_f32(int32_t kind, const double* stats, const float* ostat,
 int sgp_scaler_apply_f32(const float* x, float* out, const float* bias, const float* scale, int64_t n, int64_t n_params,
                          int32_t inverse, sgp_stream_t stream);
 
+/* ------------------------------------------- per-batch edge tables ---
+ * The tables every model derives from an edge list, built on the stream: a stable sort of the list by node, the
+ * segment offsets, ordered degree sums, CSR gathers and the chunk tables of the gated graph network.  Edge endpoints
+ * come as int32 (flag 0) or int64 (flag 1) and are narrowed on the device.  No workgroup waits for another; integer
+ * arithmetic decides every position, so two runs give identical tables.
+ *
+ * sgp_edge_sort: LSD radix sort, 8-bit digits, sgp_edge_sort_passes(n_nodes) = max(1, ceil(bits(n_nodes - 1) / 8))
+ *   passes of three launches (tile histogram, scan, scatter) over tiles of sgp_edge_sort_tile() items.  Item i of the
+ *   list has the key keys[i], or keys[payload_in[i]] when payload_in is given (n_keys entries behind keys; the second
+ *   sort of an already sorted list: edge_plan's src_pos).  order[n_items]: the positions of the stable sort,
+ *   torch.sort(list, stable=True)[1]; ptr[n_nodes + 1]: the segment offsets, cumsum(bincount(list)), found from the
+ *   key boundaries of the sorted list.  A key outside [0, n_nodes) or a payload_in entry outside [0, n_keys) is
+ *   compared unsigned before it indexes anything, sets *err = 1 (the caller cleared it) and is dropped: ptr then
+ *   describes the remaining items and the tail of order is not written.  ws: sgp_edge_sort_workspace_bytes(n_items)
+ *   bytes (a pure function of n_items; sgp_amd.edgetables.sort_plan computes the same number).
+ *   replaces the stable torch.sort / bincount / cumsum of gated_gn.edge_plan and diff_conv._csr
+ * sgp_edge_segment_sum_f32: deg[k] = weight[order[ptr[k]]] + ... + weight[order[ptr[k + 1] - 1]] added one after the
+ *   other from 0 in fp32 (weight NULL: ones) -- the host's scatter_add_ in edge order, bit for bit, because the sort
+ *   is stable.  One thread per segment: a hub row is slow and correct.
+ *   replaces the host-side scatter_add_ of diff_conv.diffusion_plan (tsl/ops/connectivity.py:200-227)
+ * sgp_edge_gather_f32: with o = order[e]: col[e] = other[o], val_a[e] = weight[o] / deg_a[idx_a[o]], val_b likewise
+ *   (IEEE division; weight NULL: ones; deg_x NULL: val_x[e] = weight[o]; col, val_a, val_b may each be NULL).  An o
+ *   outside the list gives 0.
+ * sgp_edge_chunk_tables: from ptr (the target sort) and chunk, edge_plan's chunks[C][4] = (target, first, end, partial
+ *   row or -1) and fix[F][3] = (target, first partial row, count), and counts[0 .. 3) = (C, F, n_parts).  scan: 3 *
+ *   n_nodes int32 of scratch.  Rows at and beyond max_chunks / max_fix are not written (C <= n_nodes + n_edges /
+ *   chunk, F <= n_edges / chunk).  The caller keeps the sort's err word at counts[3]: one host read returns all four. */
+int32_t sgp_edge_sort_tile(void);
+int32_t sgp_edge_sort_passes(int64_t n_nodes);
+int64_t sgp_edge_sort_workspace_bytes(int64_t n_items);
+int sgp_edge_sort(const void* keys, int32_t keys64, int64_t n_keys, const int32_t* payload_in, int64_t n_items,
+                  int64_t n_nodes, int32_t* order, int32_t* ptr, int32_t* err, void* ws, int64_t ws_bytes,
+                  sgp_stream_t stream);
+int sgp_edge_segment_sum_f32(const int32_t* ptr, const int32_t* order, const float* weight, int64_t n_nodes,
+                             int64_t n_items, float* deg, sgp_stream_t stream);
+int sgp_edge_gather_f32(const int32_t* order, int64_t n_items, const void* other, int32_t other64, const float* weight,
+                        const void* idx_a, const float* deg_a, const void* idx_b, const float* deg_b, int32_t idx64,
+                        int64_t n_nodes, int32_t* col, float* val_a, float* val_b, sgp_stream_t stream);
+int sgp_edge_chunk_tables(const int32_t* ptr, int64_t n_nodes, int32_t chunk, int32_t* scan, int32_t* counts,
+                          int32_t* chunks, int64_t max_chunks, int32_t* fix, int64_t max_fix, sgp_stream_t stream);
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

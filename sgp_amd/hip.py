@@ -265,6 +265,14 @@ SIGNATURES = {
                                              c_p, c_p, c_i64, c_p]),
     "sgp_scaler_finish_f32": (ctypes.c_int, [c_i32, c_p, c_p, c_i64, c_i32, c_f64, c_f64, c_f64, c_p, c_p, c_p]),
     "sgp_scaler_apply_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p]),
+    "sgp_edge_sort_tile": (c_i32, []),
+    "sgp_edge_sort_passes": (c_i32, [c_i64]),
+    "sgp_edge_sort_workspace_bytes": (c_i64, [c_i64]),
+    "sgp_edge_sort": (ctypes.c_int, [c_p, c_i32, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "sgp_edge_segment_sum_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_p]),
+    "sgp_edge_gather_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_i64, c_p, c_p, c_p,
+                                           c_p]),
+    "sgp_edge_chunk_tables": (ctypes.c_int, [c_p, c_i64, c_i32, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p]),
     "sgp_event_create": (ctypes.c_int, [ctypes.POINTER(c_p)]),
     "sgp_event_destroy": (ctypes.c_int, [c_p]),
     "sgp_event_record": (ctypes.c_int, [c_p, c_p]),
@@ -1221,6 +1229,82 @@ def subgraph_take_edges(src, dst, weight, pos, keep, n_keep, relabel, n_nodes, o
                                        None if err is None else _flat(err, "err", torch.int32, 1), _stream(src)),
            "sgp_subgraph_take_edges")
     return out_index
+
+
+# ---------------------------------------------------------------- per-batch edge tables (edge_tables.hip)
+def _ids(t, name, numel=None):
+    """1-D contiguous int32 / int64 CUDA tensor -> ``(pointer, 1 if int64 else 0)``."""
+    if t.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}: expected int32 or int64, got {t.dtype}")
+    return _flat(t, name, t.dtype, numel), int(t.dtype == torch.int64)
+
+
+def _opt(t, name, dtype, numel=None):
+    return None if t is None else _flat(t, name, dtype, numel)
+
+
+@_on_device
+def edge_sort(keys, n, order, ptr, err, ws, payload=None):
+    """Stable sort by key on the device: item ``i`` has the key ``keys[i]`` (int32 / int64, in [0, n)), or
+    ``keys[payload[i]]`` when ``payload`` (int32) is given.  Writes ``order`` (int32, one entry per item) =
+    ``torch.sort(list, stable=True)[1]`` and ``ptr`` (int32 [n + 1]) = the segment offsets; a key out of range sets
+    ``err`` (a 1-element int32 view the caller cleared).  ``ws``: uint8, ``edgetables.sort_plan(n, E).workspace_bytes``."""
+    from . import edgetables
+    lib = require_gpu()
+    n_keys = keys.numel()
+    E = n_keys if payload is None else payload.numel()
+    need = edgetables.sort_plan(n, E).workspace_bytes
+    kp, k64 = _ids(keys, "keys")
+    _check(lib.sgp_edge_sort(kp, k64, n_keys, _opt(payload, "payload", torch.int32), E, int(n),
+                             _flat(order, "order", torch.int32, E), _flat(ptr, "ptr", torch.int32, n + 1),
+                             _flat(err, "err", torch.int32, 1), _flat(ws, "ws", torch.uint8, need), ws.numel(),
+                             _stream(keys)), "sgp_edge_sort")
+    return order, ptr
+
+
+@_on_device
+def edge_segment_sum(ptr, order, weight, n, deg):
+    """``deg[k]`` = the fp32 sum of ``weight[order[e]]`` (``None``: ones) over segment ``k``, added in list order."""
+    lib = require_gpu()
+    E = order.numel()
+    _check(lib.sgp_edge_segment_sum_f32(_flat(ptr, "ptr", torch.int32, n + 1), _flat(order, "order", torch.int32),
+                                        _opt(weight, "weight", torch.float32, E), int(n), E,
+                                        _flat(deg, "deg", torch.float32, n), _stream(ptr)), "sgp_edge_segment_sum_f32")
+    return deg
+
+
+@_on_device
+def edge_gather(order, n, other=None, weight=None, idx_a=None, deg_a=None, idx_b=None, deg_b=None, col=None, val_a=None,
+                val_b=None):
+    """With ``o = order[e]``: ``col[e] = other[o]``, ``val_x[e] = weight[o] / deg_x[idx_x[o]]`` (``deg_x`` None:
+    ``weight[o]``; ``weight`` None: ones).  ``other`` / ``idx_x``: int32 or int64 of one dtype."""
+    lib = require_gpu()
+    E = order.numel()
+    op, o64 = (None, 0) if other is None else _ids(other, "other", E)
+    i64 = {t.dtype for t in (idx_a, idx_b) if t is not None}
+    if len(i64) > 1:
+        raise ValueError("idx_a and idx_b must have one dtype")
+    ia = None if idx_a is None else _ids(idx_a, "idx_a", E)[0]
+    ib = None if idx_b is None else _ids(idx_b, "idx_b", E)[0]
+    _check(lib.sgp_edge_gather_f32(_flat(order, "order", torch.int32), E, op, o64, _opt(weight, "weight", torch.float32, E),
+                                   ia, _opt(deg_a, "deg_a", torch.float32, n), ib, _opt(deg_b, "deg_b", torch.float32, n),
+                                   int(torch.int64 in i64), int(n), _opt(col, "col", torch.int32, E),
+                                   _opt(val_a, "val_a", torch.float32, E), _opt(val_b, "val_b", torch.float32, E),
+                                   _stream(order)), "sgp_edge_gather_f32")
+
+
+@_on_device
+def edge_chunk_tables(ptr, n, chunk, scan, counts, chunks, fix):
+    """The gated graph network's ``chunks [<= max, 4]`` / ``fix [<= max, 3]`` (int32, contiguous; rows beyond their
+    capacity are not written) from the target sort's ``ptr``; ``counts[0 .. 3)`` = (C, F, n_parts) on the device."""
+    lib = require_gpu()
+    for t, w, name in ((chunks, 4, "chunks"), (fix, 3, "fix")):
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != w or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"{name}: expected a contiguous int32 CUDA [*, {w}], got {tuple(t.shape)} {t.dtype}")
+    _check(lib.sgp_edge_chunk_tables(_flat(ptr, "ptr", torch.int32, n + 1), int(n), int(chunk),
+                                     _flat(scan, "scan", torch.int32, 3 * n), _flat(counts, "counts", torch.int32, 3),
+                                     chunks.data_ptr(), chunks.shape[0], fix.data_ptr(), fix.shape[0], _stream(ptr)),
+           "sgp_edge_chunk_tables")
 
 
 GL_ACT_CODES = {None: 0, "linear": 0, "identity": 0, "relu": 1, "silu": 2}

@@ -19,7 +19,7 @@ Differences from the reference: ``edge_weight=None`` means unit weights (the ref
 import torch
 from torch import nn
 
-from ... import hip
+from ... import edgetables, hip
 from .. import dense
 from .gated_gn import checked_edge_index
 
@@ -28,13 +28,13 @@ class DiffusionPlan:
     """CSR tables ``(rowptr int32 [n + 1], col int32 [E], val float32 [E])`` of ``A_f``, ``A_b`` and their transposes
     ``A_f^T``, ``A_b^T`` (the same values indexed from the other side; the adjoint hops read them)."""
 
-    def __init__(self, n, fwd, bwd, fwd_t, bwd_t):
+    def __init__(self, n, fwd, bwd, fwd_t, bwd_t, n_edges=None):
         self.n, self.fwd, self.bwd, self.fwd_t, self.bwd_t = int(n), fwd, bwd, fwd_t, bwd_t
-        self.n_edges = int(fwd[0][-1])
+        self.n_edges = int(fwd[0][-1]) if n_edges is None else int(n_edges)    # given: no read of a device table
 
     def to(self, device):
         mv = lambda t3: tuple(t.to(device) for t in t3)
-        return DiffusionPlan(self.n, mv(self.fwd), mv(self.bwd), mv(self.fwd_t), mv(self.bwd_t))
+        return DiffusionPlan(self.n, mv(self.fwd), mv(self.bwd), mv(self.fwd_t), mv(self.bwd_t), self.n_edges)
 
 
 def _csr(rows, cols, vals, n):
@@ -73,6 +73,12 @@ def diffusion_plan(edge_index, edge_weight, n):
     return DiffusionPlan(n, _csr(dst, src, wf, n), _csr(src, dst, wb, n), _csr(src, dst, wf, n), _csr(dst, src, wb, n))
 
 
+def _on_device(edge_index, device):
+    """An edge list the device build takes as it is: int32 / int64 ``[2, E]`` already on ``device``."""
+    return (torch.is_tensor(edge_index) and edge_index.is_cuda and edge_index.device == torch.device(device)
+            and edge_index.dim() == 2 and edge_index.shape[0] == 2 and edge_index.dtype in (torch.int32, torch.int64))
+
+
 class _PlanCache:
     """Diffusion plans of the last two graphs (a training and a validation one), keyed by the identity and version of
     ``edge_index`` and ``edge_weight`` (both kept alive here)."""
@@ -85,11 +91,15 @@ class _PlanCache:
         ver = (edge_index._version, edge_weight._version if edge_weight is not None else 0)
         hit = self._d.get(key)
         if hit is None or hit[0] is not edge_index or hit[1] is not edge_weight or hit[2] != ver:
-            ei = checked_edge_index(edge_index, n).to(device)
-            ew = edge_weight.to(device) if edge_weight is not None else None
+            if _on_device(edge_index, device):                        # built on the stream, bit-identical
+                plan = edgetables.default_tables().diffusion(edge_index, edge_weight, n)
+            else:
+                ei = checked_edge_index(edge_index, n).to(device)
+                ew = edge_weight.to(device) if edge_weight is not None else None
+                plan = diffusion_plan(ei, ew, n)
             if len(self._d) >= self._size:
                 self._d.pop(next(iter(self._d)))
-            hit = (edge_index, edge_weight, ver, diffusion_plan(ei, ew, n))
+            hit = (edge_index, edge_weight, ver, plan)
             self._d[key] = hit
         return hit[3]
 

@@ -15,7 +15,7 @@ the reference's initial values and checkpoints load both ways.
 import torch
 from torch import nn
 
-from ... import hip
+from ... import edgetables, hip
 from .. import dense
 
 
@@ -95,14 +95,21 @@ class _PlanCache:
             key, ver = (id(edge_index), n, str(device)), edge_index._version
         hit = self._d.get(key)
         if hit is None or hit[0] is not edge_index or hit[1] != ver:
-            if edge_index is None:
-                nodes = torch.arange(n, device=device)
-                ei = torch.cartesian_prod(nodes, nodes).T
+            chunk = hip.load().sgp_gated_gn_chunk_edges()
+            if (edge_index is not None and edge_index.is_cuda and edge_index.device == torch.device(device)
+                    and edge_index.dim() == 2 and edge_index.shape[0] == 2
+                    and edge_index.dtype in (torch.int32, torch.int64)):
+                plan = edgetables.default_tables().gated(edge_index, n, chunk)    # on the stream, identical
             else:
-                ei = checked_edge_index(edge_index, n).to(device)
+                if edge_index is None:
+                    nodes = torch.arange(n, device=device)
+                    ei = torch.cartesian_prod(nodes, nodes).T
+                else:
+                    ei = checked_edge_index(edge_index, n).to(device)
+                plan = edge_plan(ei, n, chunk)
             if len(self._d) >= self._size:
                 self._d.pop(next(iter(self._d)))
-            hit = (edge_index, ver, edge_plan(ei, n, hip.load().sgp_gated_gn_chunk_edges()))
+            hit = (edge_index, ver, plan)
             self._d[key] = hit
         return hit[2]
 
