@@ -42,15 +42,17 @@
 extern "C" {
 #endif
 
-/* 3 (round 6): the launch predicate became the explicit trailing (pred, run_if) pair of every sgp_spmm_*_f32 entry
+/* 4: decoder_mlp.hip's one-workgroup MaskedMAE pair (forward, backward) removed; MaskedMAE is kind 0 of
+ * sgp_masked_loss_f32 / _bwd_f32.
+ * 3 (round 6): the launch predicate became the explicit trailing (pred, run_if) pair of every sgp_spmm_*_f32 entry
  * (sgp_launch_predicate removed); host-side planner sgp_split_plan_deal / sgp_split_plan_fill, the time-piece
  * reservoir entry sgp_reservoir_pieces_f32 and the wide split hop sgp_spmm_split_wide_f32 added.
  * 2 (round 5): sgp_spmm_split_f32 takes per-column scale tables and a per-row plan array; sgp_col_stats_f32,
  * sgp_split_prepare_f32, sgp_launch_predicate added; round 4 had already removed sgp_spmm_mfma / pipe / blk_*, widened
  * sgp_spmm_colblock_f32 by the halo arguments and grown sgp_reservoir_workspace_bytes (bf16-piece fragments). */
-/* (still 3: sgp_spmm_split_banded_f32 / _wide_banded_f32 and sgp_split_plan_bands were added, and the two planner
+/* (within 3: sgp_spmm_split_banded_f32 / _wide_banded_f32 and sgp_split_plan_bands were added, and the two planner
  * entries sgp_split_plan_deal / _fill gained `nnz` behind `col` -- their only caller is sgp_amd/splitplan.py) */
-#define SGP_ABI_VERSION 3
+#define SGP_ABI_VERSION 4
 
 #define SGP_EINVAL   (-1)  /* bad size / null pointer / misaligned stride */
 #define SGP_EUNSUP   (-2)  /* shape outside what the kernels are built for */
@@ -801,16 +803,6 @@ int sgp_dense_wgrad_f32(const float* dZ, int64_t dz_row_stride, const float* X, 
 int sgp_row_segsum_f32(const float* g, int64_t g_row_stride, int64_t n_rows, int32_t width,
                        const int32_t* perm, const int32_t* keys, int32_t n_seg, float* out, sgp_stream_t stream);
 
-/* loss[0] = sum of |y_hat - y| over the counted elements / their number (count[0], fp64; 0 when nothing counts, as
- * tsl's MaskedMetric.compute), one workgroup, fp64
- * sums: element e counts when mask[e] != 0 (mask != NULL) and, with mask_nans, when |y_hat - y| is not NaN.
- * grad[e] = grad_out[0] / count[0] * sign(y_hat - y) on the counted elements, 0 elsewhere.
- *   replaces MaskedMAE (tsl/nn/metrics/metric_base.py:79-96, metric_fn = F.l1_loss(reduction='none')) */
-int sgp_masked_mae_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t n, int32_t mask_nans,
-                       float* loss, double* count, sgp_stream_t stream);
-int sgp_masked_mae_bwd_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t n, int32_t mask_nans,
-                           const float* grad_out, const double* count, float* grad, sgp_stream_t stream);
-
 
 /* ------------------------------------------------ Training step: optimizer, losses, metrics -----
  * train.hip.  Every reduction adds fixed partials in a fixed order in fp64: no float atomics, bit-identical from
@@ -862,7 +854,8 @@ int sgp_masked_metrics_f32(const float* y_hat, const float* y, const uint8_t* ma
  * counts), over contiguous [batch, horizon, row]; kind 0: f = |d|, 1: d^2, 2: |d / y| (infinite values never count);
  * at >= 0: horizon step `at` only, -1: all.  grad[e] = grad_out[0] / count[0] * df/dy_hat on the counted elements
  * (sign(d), 2 d, sign(d) / |y|), 0 elsewhere.  `work`: sgp_masked_loss_workspace_doubles doubles.
- *   replaces MaskedMAE / MaskedMSE / MaskedMAPE as loss_fn of the reference's Predictor */
+ *   replaces MaskedMAE / MaskedMSE / MaskedMAPE (tsl/nn/metrics/metric_base.py:79-96) as the loss of every training
+ *   loop and as loss_fn of the reference's Predictor */
 int64_t sgp_masked_loss_workspace_doubles(int64_t batch, int32_t horizon, int64_t row, int32_t at);
 int sgp_masked_loss_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t batch, int32_t horizon,
                         int64_t row, int32_t kind, int32_t at, int32_t mask_nans, double* work, int64_t work_doubles,

@@ -41,7 +41,7 @@ SideLane* side_lane();
 // round trip); flag == nullptr: unconditional.
 struct Predicate { const int* flag; int want; };
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+__host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

@@ -21,7 +21,7 @@
 // Correntropy.  One workgroup owns a 64 x 64 output tile for ALL chunks: per chunk the Gram tile on
 // v_mfma_f32_32x32x2_f32 (exact fp32; 4 waves as 2 x 2 of 32 x 32), exp(-gamma max(0, n_a + n_b - 2 G)) in the
 // epilogue into a register accumulator, one store of acc / n_chunks.
-#include "common.h"
+#include "wg.h"
 #include <math.h>
 
 namespace {
@@ -29,10 +29,10 @@ namespace {
 constexpr int SEL_MAX_KNN = 512;
 constexpr int SEL_CAP = 1024;            // candidates one wave holds: k kept + entrants since the last trim
 constexpr long long MAX_N = 2147483647ll;
+constexpr long long MAX_ROW_GRID = 65535 * 16;     // one wave per row; longer inputs are walked by a grid stride
 constexpr double F32_ZERO = 0x1p-150;    // |v| <= 2^-150 rounds to 0 in fp32 (round to nearest even)
 constexpr double FP64_EXP_ZERO = 745.1332191019412;   // 1075 ln 2: exp(-a) <= 2^-1075 rounds to 0 in fp64
 
-inline unsigned grid_rows(long long n) { return (unsigned)(n < 1 ? 1 : (n > 65535 * 16 ? 65535 * 16 : n)); }
 
 struct Filter {
     double threshold;      // entries below it are dropped; -inf: none
@@ -289,7 +289,7 @@ int sgp_conn_geo_knn_f64(const double* unit, int64_t n, int32_t k, int32_t inclu
     SGP_REQUIRE(scale > 0.0 && chord_zero >= 0.0, "sgp_conn_geo_knn_f64: bad scale / chord bound");
     GeoSrc src{unit, unit + n, unit + 2 * n, chord_zero, 0.0, 0.0, scale, 0.0, 0.0, 0.0};
     Filter f{threshold, binary != 0, include_self != 0};
-    hipLaunchKernelGGL(knn_kernel<GeoSrc>, dim3(grid_rows(n)), dim3(64), 0, (hipStream_t)stream, src, (long long)n, (int)k,
+    hipLaunchKernelGGL(knn_kernel<GeoSrc>, dim3(sgp::grid_for(n, 1, MAX_ROW_GRID)), dim3(64), 0, (hipStream_t)stream, src, (long long)n, (int)k,
                        f, out_col, out_val);
     return sgp::check_launch("sgp_conn_geo_knn_f64");
 }
@@ -305,10 +305,10 @@ int sgp_conn_geo_rows_f64(const double* unit, int64_t n, int32_t include_self, i
     GeoSrc src{unit, unit + n, unit + 2 * n, 0.0, chord_lo, chord_hi, scale, 0.0, 0.0, 0.0};
     Filter f{threshold, binary != 0, include_self != 0};
     if (row_count)
-        hipLaunchKernelGGL((rows_kernel<GeoSrc, false>), dim3(grid_rows(n)), dim3(64), 0, (hipStream_t)stream, src,
+        hipLaunchKernelGGL((rows_kernel<GeoSrc, false>), dim3(sgp::grid_for(n, 1, MAX_ROW_GRID)), dim3(64), 0, (hipStream_t)stream, src,
                            (long long)n, f, row_count, (const long long*)nullptr, (int*)nullptr, (double*)nullptr);
     else
-        hipLaunchKernelGGL((rows_kernel<GeoSrc, true>), dim3(grid_rows(n)), dim3(64), 0, (hipStream_t)stream, src,
+        hipLaunchKernelGGL((rows_kernel<GeoSrc, true>), dim3(sgp::grid_for(n, 1, MAX_ROW_GRID)), dim3(64), 0, (hipStream_t)stream, src,
                            (long long)n, f, (int*)nullptr, (const long long*)rowptr, out_col, out_val);
     return sgp::check_launch("sgp_conn_geo_rows_f64");
 }
@@ -321,11 +321,11 @@ int sgp_conn_dense_knn(const void* sim, int32_t is_f64, int64_t row_stride, int6
     Filter f{threshold, binary != 0, include_self != 0};
     if (is_f64) {
         DenseSrc<double> src{(const double*)sim, (long long)row_stride, (long long)col_stride, nullptr};
-        hipLaunchKernelGGL(knn_kernel<DenseSrc<double>>, dim3(grid_rows(n)), dim3(64), 0, (hipStream_t)stream, src,
+        hipLaunchKernelGGL(knn_kernel<DenseSrc<double>>, dim3(sgp::grid_for(n, 1, MAX_ROW_GRID)), dim3(64), 0, (hipStream_t)stream, src,
                            (long long)n, (int)k, f, out_col, out_val);
     } else {
         DenseSrc<float> src{(const float*)sim, (long long)row_stride, (long long)col_stride, nullptr};
-        hipLaunchKernelGGL(knn_kernel<DenseSrc<float>>, dim3(grid_rows(n)), dim3(64), 0, (hipStream_t)stream, src,
+        hipLaunchKernelGGL(knn_kernel<DenseSrc<float>>, dim3(sgp::grid_for(n, 1, MAX_ROW_GRID)), dim3(64), 0, (hipStream_t)stream, src,
                            (long long)n, (int)k, f, out_col, out_val);
     }
     return sgp::check_launch("sgp_conn_dense_knn");
@@ -339,7 +339,7 @@ int sgp_conn_dense_rows(const void* sim, int32_t is_f64, int64_t row_stride, int
     SGP_REQUIRE(sim, "sgp_conn_dense_rows: null pointer");
     SGP_REQUIRE(row_count || (rowptr && out_col && out_val), "sgp_conn_dense_rows: null pointer");
     Filter f{threshold, binary != 0, include_self != 0};
-    const dim3 grid(grid_rows(n)), block(64);
+    const dim3 grid(sgp::grid_for(n, 1, MAX_ROW_GRID)), block(64);
     hipStream_t s = (hipStream_t)stream;
     const long long* rp = (const long long*)rowptr;
     if (is_f64) {

@@ -1,7 +1,7 @@
 // The rest of the SGP decoder (lib/nn/models/sgp_model.py:54-103): the dense layers of tsl's MLP /
 // ResidualMLP (tsl/nn/blocks/encoders/mlp.py, tsl/nn/base/dense.py), the positional encoding's
 // lin_emb (sgp_model.py:76,97) and the LinearReadout (tsl/nn/blocks/decoders/linear_readout.py), forward
-// and backward, plus the MaskedMAE loss the experiments train with (tsl/nn/metrics/metric_base.py:79-96).
+// and backward.  (The MaskedMAE loss the experiments train with is train.hip's sgp_masked_loss_f32.)
 //
 //   sgp_dense_f32         Y = epilogue(X . M^T): one kernel for every forward layer and every dX of the backward
 //                         pass.  The stage loop of dense_tile.h over a workgroup's 64 or 128 rows (gathered, with a
@@ -11,10 +11,10 @@
 //                         slices in slice order in fp64 -- no float atomics, the gradients are bit-identical run to run.
 //   sgp_row_segsum_f32    node_emb gradient: rows of G summed per node in a fixed order (strided over the batch, or
 //                         along a stably sorted index vector).
-//   sgp_masked_mae_f32 / _bwd_f32   the loss and its gradient, one kernel each, fp64 sums.
 #include "common.h"
 #include "decoder_ops.h"
 #include "dense_tile.h"
+#include "wg.h"
 
 using sgp::f32x4;
 
@@ -219,59 +219,7 @@ __global__ void row_segsum_kernel(const float* __restrict__ g, long long g_rs, l
     }
 }
 
-// MaskedMAE (tsl/nn/metrics/metric_base.py:79-96 with metric_fn = |y_hat - y|): element e counts when mask[e] (if a
-// mask is given) and, with mask_nans, when |y_hat - y| is not NaN.  One workgroup, fp64 sums in a fixed tree.
-__device__ __forceinline__ bool mae_counts(const float* yh, const float* y, const unsigned char* mask, int mask_nans,
-                                           long long e, float& d) {
-    d = yh[e] - y[e];
-    if (mask && !mask[e]) return false;
-    if (mask_nans && isnan(d)) return false;
-    return true;
-}
-
-constexpr int MAE_THREADS = 1024;
-
-__global__ __launch_bounds__(MAE_THREADS) void masked_mae_kernel(const float* __restrict__ yh, const float* __restrict__ y,
-                                                                 const unsigned char* __restrict__ mask, long long n,
-                                                                 int mask_nans, float* __restrict__ loss,
-                                                                 double* __restrict__ count) {
-    __shared__ double ls[MAE_THREADS], lc[MAE_THREADS];
-    double s = 0.0, cnt = 0.0;
-    for (long long e = threadIdx.x; e < n; e += MAE_THREADS) {
-        float d;
-        if (mae_counts(yh, y, mask, mask_nans, e, d)) { s += (double)fabsf(d); cnt += 1.0; }
-    }
-    ls[threadIdx.x] = s; lc[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int w = MAE_THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) { ls[threadIdx.x] += ls[threadIdx.x + w]; lc[threadIdx.x] += lc[threadIdx.x + w]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        // nothing counted: 0, as tsl's MaskedMetric.compute returns its (zero) value when numel == 0
-        loss[0] = lc[0] > 0.0 ? (float)(ls[0] / lc[0]) : 0.f;
-        count[0] = lc[0];
-    }
-}
-
-__global__ void masked_mae_bwd_kernel(const float* __restrict__ yh, const float* __restrict__ y,
-                                      const unsigned char* __restrict__ mask, long long n, int mask_nans,
-                                      const float* __restrict__ gout, const double* __restrict__ count,
-                                      float* __restrict__ grad) {
-    const float scale = gout[0] / (float)count[0];
-    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n;
-         e += (long long)gridDim.x * blockDim.x) {
-        float d, g = 0.f;
-        if (mae_counts(yh, y, mask, mask_nans, e, d)) g = d > 0.f ? scale : (d < 0.f ? -scale : 0.f * d);
-        grad[e] = g;
-    }
-}
-
-int grid_for(long long total, int block, int cap) {
-    long long g = (total + block - 1) / block;
-    if (g < 1) g = 1;
-    return (int)(g > cap ? cap : g);
-}
+using sgp::grid_for;
 
 // row slices of the wgrad pass: enough (o, i, slice) waves to fill the chip, each slice >= 64 rows (a multiple of 16)
 void wgrad_slices(long long n_rows, int n_out, int kp, int& rps, int& slices) {
@@ -413,25 +361,6 @@ int sgp_row_segsum_f32(const float* g, int64_t g_row_stride, int64_t n_rows, int
     hipLaunchKernelGGL(row_segsum_kernel, dim3(grid_for(total, 256, 8192)), dim3(256), 0, s,
                        g, (long long)g_row_stride, (long long)n_rows, width, perm, keys, n_seg, out);
     return sgp::check_launch("row_segsum");
-}
-
-int sgp_masked_mae_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t n, int32_t mask_nans,
-                       float* loss, double* count, sgp_stream_t stream) {
-    SGP_REQUIRE(y_hat && y && loss && count, "sgp_masked_mae_f32: null pointer");
-    SGP_REQUIRE(n >= 0, "sgp_masked_mae_f32: bad size");
-    hipLaunchKernelGGL(masked_mae_kernel, dim3(1), dim3(MAE_THREADS), 0, (hipStream_t)stream,
-                       y_hat, y, mask, (long long)n, (int)mask_nans, loss, count);
-    return sgp::check_launch("masked_mae");
-}
-
-int sgp_masked_mae_bwd_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t n, int32_t mask_nans,
-                           const float* grad_out, const double* count, float* grad, sgp_stream_t stream) {
-    SGP_REQUIRE(y_hat && y && grad_out && count && grad, "sgp_masked_mae_bwd_f32: null pointer");
-    SGP_REQUIRE(n >= 0, "sgp_masked_mae_bwd_f32: bad size");
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(masked_mae_bwd_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
-                       y_hat, y, mask, (long long)n, (int)mask_nans, grad_out, count, grad);
-    return sgp::check_launch("masked_mae_bwd");
 }
 
 }  // extern "C"

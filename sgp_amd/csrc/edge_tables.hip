@@ -15,9 +15,11 @@
 // before it indexes anything) sets the error word and is dropped in the first histogram AND the first scatter: the
 // later passes and ptr see the `valid` items that remain (a device word), the tail of `order` stays unwritten, and
 // every consumer below checks order[e] against the list length before it indexes with it.
-#include "common.h"
+#include "wg.h"
 
 namespace {
+using sgp::grid_for;
+using sgp::in_range;
 
 constexpr int THREADS = 256;                      // 4 waves
 constexpr int WAVES = THREADS / 64;
@@ -29,13 +31,6 @@ constexpr long long MAX_ITEMS = 2147483647ll;
 constexpr int SCAN_THREADS = 1024;
 
 static_assert(RADIX == THREADS, "thread d owns digit d");
-
-inline unsigned grid_for(long long items, int per_block, unsigned cap = 2048) {
-    long long g = (items + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
 
 inline long long align256(long long b) { return (b + 255) & ~255ll; }
 
@@ -78,17 +73,17 @@ __device__ __forceinline__ bool load_item(const SortIn& in, long long i, long lo
     long long at = i;
     if (in.via) {
         const int p = in.via[i];
-        if ((unsigned)p >= (unsigned long long)in.n_keys) { *err = 1; return false; }
+        if (!in_range(p, in.n_keys)) { *err = 1; return false; }
         at = p;
     }
     pay = (int)i;
     if (MODE == 1) {
         const long long k = static_cast<const long long*>(in.keys)[at];
-        if ((unsigned long long)k >= (unsigned long long)n) { *err = 1; return false; }
+        if (!in_range(k, n)) { *err = 1; return false; }
         key = (int)k;
     } else {
         const int k = static_cast<const int*>(in.keys)[at];
-        if ((unsigned)k >= (unsigned long long)n) { *err = 1; return false; }
+        if (!in_range(k, n)) { *err = 1; return false; }
         key = k;
     }
     return true;
@@ -138,34 +133,19 @@ __global__ __launch_bounds__(THREADS) void hist_kernel(SortIn in, long long n_it
 // workgroup d: exclusive scan of tile_hist[d][0 .. n_tiles) in place, started at the items of the digits below d
 __global__ __launch_bounds__(THREADS) void digit_scan_kernel(int* tile_hist, long long n_tiles, const int* __restrict__ totals,
                                                              int* valid) {
-    __shared__ int sums[THREADS];
+    __shared__ int sums[1][THREADS];
     const int d = blockIdx.x;
-    sums[threadIdx.x] = totals[threadIdx.x];
+    sums[0][threadIdx.x] = totals[threadIdx.x];
     __syncthreads();
     int base = 0;
-    for (int k = 0; k < d; ++k) base += sums[k];
-    if (valid && d == RADIX - 1 && threadIdx.x == 0) *valid = base + sums[RADIX - 1];
+    for (int k = 0; k < d; ++k) base += sums[0][k];
+    if (valid && d == RADIX - 1 && threadIdx.x == 0) *valid = base + sums[0][RADIX - 1];
     __syncthreads();
     int* row = tile_hist + d * n_tiles;
-    const long long per = (n_tiles + THREADS - 1) / THREADS;
-    const long long lo = threadIdx.x * per < n_tiles ? threadIdx.x * per : n_tiles;
-    const long long hi = lo + per < n_tiles ? lo + per : n_tiles;
-    int s = 0;
-    for (long long i = lo; i < hi; ++i) s += row[i];
-    sums[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < THREADS; off <<= 1) {
-        const int add = (int)threadIdx.x >= off ? sums[threadIdx.x - off] : 0;
-        __syncthreads();
-        sums[threadIdx.x] += add;
-        __syncthreads();
-    }
-    int run = base + sums[threadIdx.x] - s;
-    for (long long i = lo; i < hi; ++i) {
-        const int c = row[i];
-        row[i] = run;
-        run += c;
-    }
+    int tot[1];
+    sgp::wg_exclusive_scan<THREADS, 1>(
+        n_tiles, sums, [=](long long i, int (&v)[1]) { v[0] = row[i]; },
+        [=](long long i, const int (&run)[1]) { row[i] = base + run[0]; }, tot);
 }
 
 template <int MODE>
@@ -238,7 +218,7 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(const int* __restrict_
         float s = 0.f;
         for (long long e = e0; e < e1; ++e) {
             const int o = order[e];
-            if ((unsigned)o >= (unsigned long long)n_items) continue;
+            if (!in_range(o, n_items)) continue;
             s += w ? w[o] : 1.f;
         }
         deg[k] = s;
@@ -260,18 +240,18 @@ __global__ __launch_bounds__(256) void gather_kernel(const int* __restrict__ ord
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n_items;
          e += (long long)gridDim.x * blockDim.x) {
         const int o = order[e];
-        const bool ok = (unsigned)o < (unsigned long long)n_items;
+        const bool ok = in_range(o, n_items);
         if (col) col[e] = ok ? (int)load_id(other, other64, o) : 0;
         const float we = !ok ? 0.f : (w ? w[o] : 1.f);
         if (val_a && !deg_a) val_a[e] = we;
         else if (val_a) {
             const long long i = ok ? load_id(idx_a, idx64, o) : -1;
-            val_a[e] = (unsigned long long)i < (unsigned long long)n ? we / deg_a[i] : 0.f;
+            val_a[e] = in_range(i, n) ? we / deg_a[i] : 0.f;
         }
         if (val_b && !deg_b) val_b[e] = we;
         else if (val_b) {
             const long long i = ok ? load_id(idx_b, idx64, o) : -1;
-            val_b[e] = (unsigned long long)i < (unsigned long long)n ? we / deg_b[i] : 0.f;
+            val_b[e] = in_range(i, n) ? we / deg_b[i] : 0.f;
         }
     }
 }
@@ -288,40 +268,17 @@ __device__ __forceinline__ int chunks_of(const int* __restrict__ ptr, long long 
 __global__ __launch_bounds__(SCAN_THREADS) void chunk_scan_kernel(const int* __restrict__ ptr, long long n, int chunk,
                                                                   int* __restrict__ scan, int* counts) {
     __shared__ long long sums[3][SCAN_THREADS];
-    const long long per = (n + SCAN_THREADS - 1) / SCAN_THREADS;
-    const long long lo = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const long long hi = lo + per < n ? lo + per : n;
-    long long s[3] = {0, 0, 0};
-    for (long long k = lo; k < hi; ++k) {
-        const int c = chunks_of(ptr, k, chunk);
-        s[0] += c;
-        if (c > 1) { s[1] += c; s[2] += 1; }
-    }
-    for (int q = 0; q < 3; ++q) sums[q][threadIdx.x] = s[q];
-    __syncthreads();
-    for (int off = 1; off < SCAN_THREADS; off <<= 1) {
-        long long add[3] = {0, 0, 0};
-        if ((int)threadIdx.x >= off)
-            for (int q = 0; q < 3; ++q) add[q] = sums[q][threadIdx.x - off];
-        __syncthreads();
-        for (int q = 0; q < 3; ++q) sums[q][threadIdx.x] += add[q];
-        __syncthreads();
-    }
-    long long run[3];
-    for (int q = 0; q < 3; ++q) run[q] = sums[q][threadIdx.x] - s[q];
-    for (long long k = lo; k < hi; ++k) {
-        const int c = chunks_of(ptr, k, chunk);
-        scan[k] = (int)run[0];
-        scan[n + k] = (int)run[1];
-        scan[2 * n + k] = (int)run[2];
-        run[0] += c;
-        if (c > 1) { run[1] += c; run[2] += 1; }
-    }
-    if (threadIdx.x == SCAN_THREADS - 1) {
-        counts[0] = (int)sums[0][SCAN_THREADS - 1];
-        counts[1] = (int)sums[2][SCAN_THREADS - 1];
-        counts[2] = (int)sums[1][SCAN_THREADS - 1];
-    }
+    long long tot[3];
+    sgp::wg_exclusive_scan<SCAN_THREADS, 3>(
+        n, sums,
+        [=](long long k, long long (&v)[3]) {
+            const int c = chunks_of(ptr, k, chunk);
+            v[0] = c; v[1] = c > 1 ? c : 0; v[2] = c > 1 ? 1 : 0;
+        },
+        [=](long long k, const long long (&run)[3]) {
+            scan[k] = (int)run[0]; scan[n + k] = (int)run[1]; scan[2 * n + k] = (int)run[2];
+        }, tot);
+    if (threadIdx.x == 0) { counts[0] = (int)tot[0]; counts[1] = (int)tot[2]; counts[2] = (int)tot[1]; }
 }
 
 // chunk row c belongs to the last node whose first chunk is <= c (every node has at least one chunk)

@@ -21,6 +21,7 @@
 // no float atomics anywhere, results are bit-identical from run to run.
 #include "common.h"
 #include "decoder_ops.h"
+#include "wg.h"
 
 using sgp::f32x4;
 using sgp::sigmoid_f32;
@@ -476,11 +477,7 @@ BwdPlan bwd_plan(long long b, long long n_edges, long long n_chunks, int n_parts
     return p;
 }
 
-int grid_for(long long total, int block, int cap) {
-    long long g = (total + block - 1) / block;
-    if (g < 1) g = 1;
-    return (int)(g > cap ? cap : g);
-}
+using sgp::grid_for;
 
 template <int HT, int KT>
 int launch_bwd(const GgArgs& a, int n_wg, hipStream_t s) {

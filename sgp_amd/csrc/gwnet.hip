@@ -21,9 +21,11 @@
 #include "common.h"
 #include "decoder_ops.h"
 #include "dense_tile.h"
+#include "wg.h"
 
 namespace {
 using sgp::f32x4;
+using sgp::grid_for;
 using sgp::sigmoid_f32;
 using namespace sgp_dense;
 
@@ -31,12 +33,6 @@ const char* domain_error(int H, int Kt) {
     if (H < 16 || H > 128 || H % 16 != 0) return "hidden size must be a multiple of 16 in 16 .. 128";
     if (Kt < 1 || Kt > 4) return "temporal kernel size must lie in 1 .. 4";
     return nullptr;
-}
-
-int grid_for(long long total, int block, int cap) {
-    long long g = (total + block - 1) / block;
-    if (g < 1) g = 1;
-    return (int)(g > cap ? cap : g);
 }
 
 // ---------------------------------------------------------------------------------------------------- temporal conv
@@ -301,15 +297,7 @@ void adj_grad_slices(int n, int batch, int& ips, int& slices) {
 constexpr int SM_T = 256;
 
 __device__ __forceinline__ double block_sum(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = SM_T / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
+    return sgp::wg_reduce<SM_T>(v, sh, [](double a, double b) { return a + b; });
 }
 
 __global__ __launch_bounds__(SM_T) void row_softmax_kernel(const float* __restrict__ L, long long lrs, float* A,
@@ -320,13 +308,7 @@ __global__ __launch_bounds__(SM_T) void row_softmax_kernel(const float* __restri
     float* o = A + (long long)blockIdx.x * ars;
     float m = -INFINITY;
     for (int j = threadIdx.x; j < n; j += SM_T) m = fmaxf(m, l[j]);
-    mx[threadIdx.x] = m;
-    __syncthreads();
-    for (int w = SM_T / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) mx[threadIdx.x] = fmaxf(mx[threadIdx.x], mx[threadIdx.x + w]);
-        __syncthreads();
-    }
-    m = mx[0];
+    m = sgp::wg_reduce<SM_T>(m, mx, [](float a, float b) { return fmaxf(a, b); });
     double s = 0.0;
     for (int j = threadIdx.x; j < n; j += SM_T) s += (double)expf(l[j] - m);
     const float tot = (float)block_sum(s, sh);
@@ -470,7 +452,8 @@ __global__ void norm_apply_bwd(NmArgs a) {
     if (a.out2) a.out2[row * a.o2rs + col] = dz;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// butterfly: every lane gets the sum (the rows below need it in all of them)
+__device__ __forceinline__ float wave_sum_all(float v) {
 #pragma unroll
     for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
     return v;
@@ -491,14 +474,14 @@ __global__ __launch_bounds__(256) void norm_layer_kernel(NmArgs a, float eps) {
             v[k] = col < a.H ? nm_z(a, row, col) : 0.f;
             s += v[k];
         }
-        const float mean = wave_sum(s) / (float)a.H;
+        const float mean = wave_sum_all(s) / (float)a.H;
         float ss = 0.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int col = lane + 64 * k;
             if (col < a.H) { const float u = v[k] - mean; ss += u * u; }
         }
-        const float inv = 1.f / (sqrtf(wave_sum(ss) / (float)a.H) + eps);
+        const float inv = 1.f / (sqrtf(wave_sum_all(ss) / (float)a.H) + eps);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int col = lane + 64 * k;
@@ -520,8 +503,8 @@ __global__ __launch_bounds__(256) void norm_layer_kernel(NmArgs a, float eps) {
             }
             sg += g[k]; sgu += g[k] * v[k];
         }
-        sg = wave_sum(sg) / (float)a.H;
-        sgu = wave_sum(sgu);
+        sg = wave_sum_all(sg) / (float)a.H;
+        sgu = wave_sum_all(sgu);
         const float sd = 1.f / inv - eps;
         const float k2 = sd > 0.f ? inv * inv * sgu / ((float)a.H * sd) : 0.f;
 #pragma unroll

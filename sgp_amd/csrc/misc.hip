@@ -2,7 +2,7 @@
 // lib/nn/encoders/sgp_spatial_encoder.py:32-34), strided slot copy (the torch.cat of
 // sgp_spatial_encoder.py:35 when a block is produced elsewhere), and row gathers (halo packing
 // for the multi-GPU hop exchange; IID sampling of lib/datasets/iid_dataset.py:57-99).
-#include "common.h"
+#include "wg.h"
 
 using sgp::f32x4;
 
@@ -133,12 +133,6 @@ inline bool vec_ok(const void* p, long long s0, long long s1, int feat) {
     return feat % 4 == 0 && s0 % 4 == 0 && s1 % 4 == 0 && sgp::aligned16(p);
 }
 
-inline unsigned grid_for(long long work_items) {
-    long long g = (work_items + 255) / 256;
-    if (g < 1) g = 1;
-    if (g > 4096) g = 4096;
-    return (unsigned)g;
-}
 
 }  // namespace
 
@@ -192,10 +186,10 @@ int sgp_bcast_rows_f32(const float* src, float scale, float* Y, int64_t yrs, int
         hipLaunchKernelGGL(bcast_rows_wide_kernel, dim3((n_rows + rows_per_wg - 1) / rows_per_wg, batch), dim3(256),
                            0, s, src, scale, Y, yrs, ybs, n_rows, feat, rows_per_wg);
     } else if (vec_ok(Y, yrs, ybs, feat) && sgp::aligned16(src))
-        hipLaunchKernelGGL(bcast_rows_kernel<4>, dim3(grid_for((long long)n_rows * feat / 4), batch), dim3(256),
+        hipLaunchKernelGGL(bcast_rows_kernel<4>, dim3(sgp::grid_for((long long)n_rows * feat / 4, 256, 4096), batch), dim3(256),
                            0, s, src, scale, Y, yrs, ybs, n_rows, feat);
     else
-        hipLaunchKernelGGL(bcast_rows_kernel<1>, dim3(grid_for((long long)n_rows * feat), batch), dim3(256),
+        hipLaunchKernelGGL(bcast_rows_kernel<1>, dim3(sgp::grid_for((long long)n_rows * feat, 256, 4096), batch), dim3(256),
                            0, s, src, scale, Y, yrs, ybs, n_rows, feat);
     return sgp::check_launch("bcast_rows");
 }
@@ -244,10 +238,10 @@ int sgp_copy_rows_f32(const float* X, int64_t xrs, int64_t xbs, float* Y, int64_
     if (!n_rows || !batch || !feat) return 0;
     hipStream_t s = (hipStream_t)stream;
     if (vec_ok(X, xrs, xbs, feat) && vec_ok(Y, yrs, ybs, feat))
-        hipLaunchKernelGGL(copy_rows_kernel<4>, dim3(grid_for((long long)n_rows * feat / 4), batch), dim3(256),
+        hipLaunchKernelGGL(copy_rows_kernel<4>, dim3(sgp::grid_for((long long)n_rows * feat / 4, 256, 4096), batch), dim3(256),
                            0, s, X, xrs, xbs, Y, yrs, ybs, n_rows, feat);
     else
-        hipLaunchKernelGGL(copy_rows_kernel<1>, dim3(grid_for((long long)n_rows * feat), batch), dim3(256),
+        hipLaunchKernelGGL(copy_rows_kernel<1>, dim3(sgp::grid_for((long long)n_rows * feat, 256, 4096), batch), dim3(256),
                            0, s, X, xrs, xbs, Y, yrs, ybs, n_rows, feat);
     return sgp::check_launch("copy_rows");
 }
@@ -262,10 +256,10 @@ int sgp_gather_rows_f32(const float* X, int64_t xrs, int64_t xbs,
     if (!n_index || !batch || !feat) return 0;
     hipStream_t s = (hipStream_t)stream;
     if (vec_ok(X, xrs, xbs, feat) && vec_ok(out, ors, obs, feat))
-        hipLaunchKernelGGL(gather_rows_kernel<4>, dim3(grid_for((long long)n_index * feat / 4), batch),
+        hipLaunchKernelGGL(gather_rows_kernel<4>, dim3(sgp::grid_for((long long)n_index * feat / 4, 256, 4096), batch),
                            dim3(256), 0, s, X, xrs, xbs, step, node, n_index, out, ors, obs, feat);
     else
-        hipLaunchKernelGGL(gather_rows_kernel<1>, dim3(grid_for((long long)n_index * feat), batch), dim3(256),
+        hipLaunchKernelGGL(gather_rows_kernel<1>, dim3(sgp::grid_for((long long)n_index * feat, 256, 4096), batch), dim3(256),
                            0, s, X, xrs, xbs, step, node, n_index, out, ors, obs, feat);
     return sgp::check_launch("gather_rows");
 }

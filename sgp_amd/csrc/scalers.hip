@@ -9,7 +9,7 @@
 //                    neighbouring columns); everything stays in LDS: 8 passes on 4-bit digits, no global merge.
 // Order-preserving keys: negatives have all bits flipped, the rest the sign bit.  Up to 6 ranks per group (floor and
 // ceil of three quantiles); ranks that still share a prefix share a histogram slot.  No float atomics anywhere.
-#include "common.h"
+#include "wg.h"
 #include <math.h>
 #include <limits.h>
 
@@ -94,17 +94,13 @@ __global__ __launch_bounds__(THREADS) void moments_long_kernel(const float* __re
         if (u < g) {                                             // (g is uniform: the barriers below are too)
             s_sum[tid] = sum[u];
             if (PASS == 1) { s_mn[tid] = mn[u]; s_mx[tid] = mx[u]; s_cnt[tid] = cnt[u]; s_nan[tid] = (nanf >> u) & 1u; }
-            __syncthreads();
-            for (int s = THREADS / 2; s > 0; s >>= 1) {
-                if (tid < s) {
-                    s_sum[tid] += s_sum[tid + s];
-                    if (PASS == 1) {
-                        s_mn[tid] = fminf(s_mn[tid], s_mn[tid + s]); s_mx[tid] = fmaxf(s_mx[tid], s_mx[tid + s]);
-                        s_cnt[tid] += s_cnt[tid + s]; s_nan[tid] |= s_nan[tid + s];
-                    }
+            sgp::wg_reduce<THREADS>([&](int a, int b) {
+                s_sum[a] += s_sum[b];
+                if (PASS == 1) {
+                    s_mn[a] = fminf(s_mn[a], s_mn[b]); s_mx[a] = fmaxf(s_mx[a], s_mx[b]);
+                    s_cnt[a] += s_cnt[b]; s_nan[a] |= s_nan[b];
                 }
-                __syncthreads();
-            }
+            });
             if (tid == 0) {
                 if (PASS == 1) {
                     double* p = part + ((long long)blockIdx.x * g + u) * 5;
@@ -134,15 +130,11 @@ __global__ __launch_bounds__(THREADS) void moments_reduce_kernel(const double* _
         }
     }
     s_a[tid] = a; s_b[tid] = b; s_mn[tid] = mn; s_mx[tid] = mx; s_nan[tid] = nf;
-    __syncthreads();
-    for (int s = THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            s_a[tid] += s_a[tid + s]; s_b[tid] += s_b[tid + s];
-            s_mn[tid] = fmin(s_mn[tid], s_mn[tid + s]); s_mx[tid] = fmax(s_mx[tid], s_mx[tid + s]);
-            s_nan[tid] = fmax(s_nan[tid], s_nan[tid + s]);
-        }
-        __syncthreads();
-    }
+    sgp::wg_reduce<THREADS>([&](int a, int b) {
+        s_a[a] += s_a[b]; s_b[a] += s_b[b];
+        s_mn[a] = fmin(s_mn[a], s_mn[b]); s_mx[a] = fmax(s_mx[a], s_mx[b]);
+        s_nan[a] = fmax(s_nan[a], s_nan[b]);
+    });
     if (tid == 0) {
         const long long G = g;
         if (PASS == 1) {

@@ -13,24 +13,19 @@
 //            takes bit l: rank = tile offset + words before + popcll(word & lanes below).  Consecutive lanes touch
 //            consecutive indices, so the edge pass reads the edge list coalesced.
 // Every flag array is a bit array in 64-bit words (the node mask itself is one); bits at and beyond n are ignored.
-#include "common.h"
+#include "wg.h"
 
 namespace {
+using sgp::grid_for;
+using sgp::in_range;
 
 typedef unsigned long long u64;
 
 constexpr int TILE_WORDS = 256;          // words of one compaction tile = threads of its workgroup (4 waves)
 constexpr int SCAN_THREADS = 1024;
 
-inline unsigned grid_for(long long items, int per_block, unsigned cap = 2048) {
-    long long g = (items + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
-
 __device__ __forceinline__ bool in_mask(const u64* __restrict__ mask, int v, long long n) {
-    return (unsigned)v < (unsigned long long)n && ((mask[(unsigned)v >> 6] >> (v & 63)) & 1ull);
+    return in_range(v, n) && ((mask[(unsigned)v >> 6] >> (v & 63)) & 1ull);
 }
 
 // word w of an n-bit array with the bits at and beyond n cleared
@@ -46,7 +41,7 @@ __global__ __launch_bounds__(256) void mark_kernel(const int* __restrict__ ids, 
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n_ids;
          i += (long long)gridDim.x * blockDim.x) {
         const int v = ids[i];
-        if ((unsigned)v < (unsigned long long)n) atomicOr(&mask[(unsigned)v >> 6], 1ull << (v & 63));
+        if (in_range(v, n)) atomicOr(&mask[(unsigned)v >> 6], 1ull << (v & 63));
         else if (err) *err = 1;
     }
 }
@@ -61,7 +56,7 @@ __global__ __launch_bounds__(256) void expand_kernel(const int* __restrict__ src
          e += (long long)gridDim.x * blockDim.x) {
         if (!in_mask(mask_in, src[e], n)) continue;
         const int v = dst[e];
-        if ((unsigned)v >= (unsigned long long)n) continue;
+        if (!in_range(v, n)) continue;
         const u64 bit = 1ull << (v & 63);
         u64* word = &mask_out[(unsigned)v >> 6];
         if (!(*word & bit)) atomicOr(word, bit);
@@ -97,17 +92,12 @@ __global__ __launch_bounds__(256) void pack_u8_kernel(const unsigned char* __res
     }
 }
 
-__device__ __forceinline__ int wave_sum(int v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;                                                                   // lane 0 holds the sum
-}
-
 __global__ __launch_bounds__(TILE_WORDS) void count_kernel(const u64* __restrict__ bits, long long n, long long n_tiles,
                                                            int* __restrict__ tile_counts) {
     __shared__ int part[TILE_WORDS / 64];
     const long long n_words = (n + 63) >> 6;
     for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {      // block-uniform
-        const int c = wave_sum(__popcll(load_word(bits, tile * TILE_WORDS + threadIdx.x, n_words, n)));
+        const int c = sgp::wave_sum(__popcll(load_word(bits, tile * TILE_WORDS + threadIdx.x, n_words, n)));
         if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
         __syncthreads();
         if (threadIdx.x == 0) tile_counts[tile] = part[0] + part[1] + part[2] + part[3];
@@ -115,29 +105,15 @@ __global__ __launch_bounds__(TILE_WORDS) void count_kernel(const u64* __restrict
     }
 }
 
-// exclusive scan of counts[0 .. n) in place by ONE workgroup: a contiguous chunk per thread, a Hillis-Steele scan of
-// the 1024 chunk sums in LDS, then the chunk again.  n <= 2^17 for 2^31 flags: 128 entries per thread.
+// exclusive scan of counts[0 .. n) in place by ONE workgroup (wg.h), the total to a device word.  n <= 2^17 for 2^31
+// flags: 128 entries per thread.
 __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(int* counts, long long n, int* total) {
-    __shared__ long long sums[SCAN_THREADS];
-    const long long per = (n + SCAN_THREADS - 1) / SCAN_THREADS;
-    const long long lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-    long long s = 0;
-    for (long long i = lo; i < hi; ++i) s += counts[i];
-    sums[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < SCAN_THREADS; off <<= 1) {
-        const long long add = threadIdx.x >= off ? sums[threadIdx.x - off] : 0;
-        __syncthreads();
-        sums[threadIdx.x] += add;
-        __syncthreads();
-    }
-    long long run = sums[threadIdx.x] - s;                                      // exclusive prefix of this chunk
-    for (long long i = lo; i < hi; ++i) {
-        const int c = counts[i];
-        counts[i] = (int)run;
-        run += c;
-    }
-    if (threadIdx.x == SCAN_THREADS - 1) *total = (int)sums[SCAN_THREADS - 1];
+    __shared__ long long sums[1][SCAN_THREADS];
+    long long tot[1];
+    sgp::wg_exclusive_scan<SCAN_THREADS, 1>(
+        n, sums, [=](long long i, long long (&v)[1]) { v[0] = counts[i]; },
+        [=](long long i, const long long (&run)[1]) { counts[i] = (int)run[0]; }, tot);
+    if (threadIdx.x == 0) *total = (int)tot[0];
 }
 
 // emit(i, r) for every set bit i of `bits`, r its exclusive rank, in ascending i within each wave's words
@@ -195,7 +171,7 @@ __global__ __launch_bounds__(TILE_WORDS) void scatter_edges_kernel(const u64* __
     scatter_tiles(flags, n_edges, n_tiles, tile_offsets, [=](long long e, long long r) {
         if (r >= cap) return;
         const int s = src[e], d = dst[e];
-        const bool ok = (unsigned)s < (unsigned long long)n && (unsigned)d < (unsigned long long)n;
+        const bool ok = in_range(s, n) && in_range(d, n);
         out_src[r] = ok ? relabel[s] : -1;
         out_dst[r] = ok ? relabel[d] : -1;
         if (out_w) out_w[r] = w[e];
@@ -217,7 +193,7 @@ __global__ __launch_bounds__(256) void take_edges_kernel(const int* __restrict__
         if (r >= 0 && r < n_pos) e = pos ? (long long)pos[r] : r;
         int s = -1, d = -1;
         if (e >= 0 && e < n_edges) { s = src[e]; d = dst[e]; }
-        const bool ok = (unsigned)s < (unsigned long long)n && (unsigned)d < (unsigned long long)n;
+        const bool ok = in_range(s, n) && in_range(d, n);
         out_src[j] = ok ? (relabel ? relabel[s] : s) : -1;
         out_dst[j] = ok ? (relabel ? relabel[d] : d) : -1;
         if (out_w) out_w[j] = ok ? w[e] : 0.f;

@@ -12,7 +12,8 @@
 // tensor's four base pointers come from four device pointer arrays indexed by the id.  Tensors need 4-byte alignment
 // only: a chunk is walked as (head of up to 3 scalars until the walk's lead pointer is 16-byte aligned, 16-byte
 // vectors, tail of up to 3 scalars); an operand that is misaligned relative to the lead is read by scalars.
-#include "common.h"
+#include "device_math.h"
+#include "wg.h"
 #include <math.h>
 
 namespace {
@@ -24,42 +25,16 @@ constexpr int TR_WAVES = TR_THREADS / 64;
 constexpr int MET_SEG = 2048;              // elements of one (horizon step, segment) unit of the metric / loss passes
 constexpr int MET_COLS = 6;                // |d| sum, |d| count, d^2 sum, |d / y| sum, |d / y| count, masked y sum
 
-// Sum of NV doubles per thread over the workgroup, in a fixed order (xor-free shuffle tree per wave, then the waves in
-// order); the result is valid in thread 0.
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double* lds /* [NV * TR_WAVES] */) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();                                          // (the caller may reuse lds from a previous sum)
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < NV; ++k) lds[k * TR_WAVES + wave] = v[k];
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            double s = lds[k * TR_WAVES];
-#pragma unroll
-            for (int w = 1; w < TR_WAVES; ++w) s += lds[k * TR_WAVES + w];
-            v[k] = s;
-        }
-}
+// every sum below: NV doubles per thread over the workgroup in a fixed order, valid in thread 0; lds [NV * TR_WAVES]
+using sgp::wg_sum_waves;
 
 __device__ __forceinline__ int head_of(const float* p, long long len) {
     const int h = (int)((4u - (unsigned)((reinterpret_cast<uintptr_t>(p) >> 2) & 3u)) & 3u);
     return (long long)h < len ? h : (int)len;
 }
-__device__ __forceinline__ bool vec_ok(const float* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-__device__ __forceinline__ f32x4 load4(const float* p, bool vec) {
-    if (vec) return *reinterpret_cast<const f32x4*>(p);
-    f32x4 r = {p[0], p[1], p[2], p[3]};
-    return r;
-}
+__device__ __forceinline__ f32x4 load4(const float* p, bool vec) { return vec ? sgp::ld4(p) : f32x4{p[0], p[1], p[2], p[3]}; }
 __device__ __forceinline__ void store4(float* p, bool vec, f32x4 x) {
-    if (vec) { *reinterpret_cast<f32x4*>(p) = x; return; }
+    if (vec) { sgp::st4(p, x); return; }
     p[0] = x.x; p[1] = x.y; p[2] = x.z; p[3] = x.w;
 }
 
@@ -80,7 +55,7 @@ __global__ __launch_bounds__(TR_THREADS) void multi_sqnorm_kernel(const long lon
         s[0] += (double)x.x * x.x + (double)x.y * x.y + (double)x.z * x.z + (double)x.w * x.w;
     }
     if (tail0 + threadIdx.x < len) { const double x = g[tail0 + threadIdx.x]; s[0] += x * x; }
-    block_sum<1>(s, lds);
+    wg_sum_waves<TR_THREADS>(s, lds);
     if (threadIdx.x == 0) partial[c] = s[0];
 }
 
@@ -90,7 +65,7 @@ __global__ __launch_bounds__(TR_THREADS) void sqnorm_final_kernel(const double* 
     __shared__ double lds[TR_WAVES];
     double s[1] = {0.0};
     for (long long i = threadIdx.x; i < n; i += TR_THREADS) s[0] += partial[i];
-    block_sum<1>(s, lds);
+    wg_sum_waves<TR_THREADS>(s, lds);
     if (threadIdx.x == 0) {
         const double nrm = sqrt(s[0]);
         if (norm_f64) norm_f64[0] = nrm;
@@ -142,7 +117,7 @@ __global__ __launch_bounds__(TR_THREADS) void adam_step_kernel(const long long* 
     const int head = head_of(p, len);
     const long long nvec = (len - head) >> 2, tail0 = head + 4 * nvec;
     if ((int)threadIdx.x < head) adam_one(p[threadIdx.x], g[threadIdx.x], m[threadIdx.x], v[threadIdx.x], coef, clip, k);
-    const bool gv = vec_ok(g + head), mv = vec_ok(m + head), vv = vec_ok(v + head);
+    const bool gv = sgp::aligned16(g + head), mv = sgp::aligned16(m + head), vv = sgp::aligned16(v + head);
     for (long long i = threadIdx.x; i < nvec; i += TR_THREADS) {
         const long long e = head + 4 * i;
         const f32x4 P = *reinterpret_cast<f32x4*>(p + e), G = load4(g + e, gv), M = load4(m + e, mv), V = load4(v + e, vv);
@@ -201,7 +176,7 @@ __global__ __launch_bounds__(TR_THREADS) void masked_metrics_kernel(const float*
         const float q = fabsf(d / t);
         if (counts(m, q, mask_nans, 1)) { s[3] += (double)q; s[4] += 1.0; }
     }
-    block_sum<MET_COLS>(s, lds);
+    wg_sum_waves<TR_THREADS>(s, lds);
     if (threadIdx.x == 0)
 #pragma unroll
         for (int k = 0; k < MET_COLS; ++k) partial[u * MET_COLS + k] = s[k];
@@ -216,7 +191,7 @@ __global__ __launch_bounds__(TR_THREADS) void masked_metrics_final_kernel(const 
     for (long long i = threadIdx.x; i < nseg; i += TR_THREADS)
 #pragma unroll
         for (int k = 0; k < MET_COLS; ++k) s[k] += partial[(h * nseg + i) * MET_COLS + k];
-    block_sum<MET_COLS>(s, lds);
+    wg_sum_waves<TR_THREADS>(s, lds);
     if (threadIdx.x == 0)
 #pragma unroll
         for (int k = 0; k < MET_COLS; ++k) state[h * MET_COLS + k] += s[k];
@@ -242,7 +217,7 @@ __global__ __launch_bounds__(TR_THREADS) void masked_loss_kernel(const float* __
         const float t = y[a], val = loss_value(kind, yh[a] - t, t);
         if (counts(mask ? mask[a] != 0 : true, val, mask_nans, kind == LOSS_MAPE)) { s[0] += (double)val; s[1] += 1.0; }
     }
-    block_sum<2>(s, lds);
+    wg_sum_waves<TR_THREADS>(s, lds);
     if (threadIdx.x == 0) { partial[2 * seg] = s[0]; partial[2 * seg + 1] = s[1]; }
 }
 
@@ -251,7 +226,7 @@ __global__ __launch_bounds__(TR_THREADS) void masked_loss_final_kernel(const dou
     __shared__ double lds[2 * TR_WAVES];
     double s[2] = {0.0, 0.0};
     for (long long i = threadIdx.x; i < nseg; i += TR_THREADS) { s[0] += partial[2 * i]; s[1] += partial[2 * i + 1]; }
-    block_sum<2>(s, lds);
+    wg_sum_waves<TR_THREADS>(s, lds);
     if (threadIdx.x == 0) {
         loss[0] = s[1] > 0.0 ? (float)(s[0] / s[1]) : (float)s[0];      // MaskedMetric.compute: value when numel == 0
         count[0] = s[1];
@@ -392,9 +367,7 @@ int sgp_masked_loss_bwd_f32(const float* y_hat, const float* y, const uint8_t* m
     SGP_REQUIRE(mask_nans == 0 || mask_nans == 1, "sgp_masked_loss_bwd_f32: mask_nans is 0 or 1");
     const long long n = batch * horizon * row;
     if (n == 0) return 0;
-    long long grid = (n + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(masked_loss_bwd_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(masked_loss_bwd_kernel, dim3(sgp::grid_for(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
                        y_hat, y, mask, n, (long long)horizon, (long long)row, (long long)at, kind, mask_nans, grad_out,
                        count, grad);
     return sgp::check_launch("masked_loss_bwd");

@@ -186,8 +186,6 @@ SIGNATURES = {
     "sgp_dense_wgrad_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_i32,
                                            c_p, c_i64, c_p, c_p, c_i64, c_p]),
     "sgp_row_segsum_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i32, c_p, c_p, c_i32, c_p, c_p]),
-    "sgp_masked_mae_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p]),
-    "sgp_masked_mae_bwd_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p, c_p]),
     "sgp_multi_sqnorm_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
     "sgp_adam_step_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_f64,
                                          c_f64, c_f64, c_f64, c_f64, c_f64, c_i64, c_i32, c_p]),
@@ -316,7 +314,7 @@ def load():
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sgp_abi_version() != 3:
+    if lib.sgp_abi_version() != 4:
         raise RuntimeError("libsgp_amd.so ABI version mismatch; rebuild it")
     _lib = lib
     return lib
@@ -1521,32 +1519,6 @@ def row_segsum(g, n_seg, perm=None, keys=None):
     return out
 
 
-@_on_device
-def masked_mae(y_hat, y, mask=None, mask_nans=False):
-    """(loss [] float32, count [1] float64) of MaskedMAE over contiguous float32 tensors of one shape."""
-    lib = require_gpu()
-    if not y_hat.numel():                                               # nothing counts: 0, as tsl's MaskedMetric.compute
-        return (torch.zeros((), dtype=torch.float32, device=y_hat.device),
-                torch.zeros(1, dtype=torch.float64, device=y_hat.device))
-    loss = torch.empty((), dtype=torch.float32, device=y_hat.device)
-    count = torch.empty(1, dtype=torch.float64, device=y_hat.device)
-    _check(lib.sgp_masked_mae_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), y_hat.numel(), int(mask_nans),
-                                  loss.data_ptr(), count.data_ptr(), _stream(loss)), "sgp_masked_mae_f32")
-    return loss, count
-
-
-@_on_device
-def masked_mae_bwd(y_hat, y, mask, mask_nans, grad_out, count):
-    lib = require_gpu()
-    grad = torch.empty_like(y_hat)
-    if not y_hat.numel():
-        return grad
-    _check(lib.sgp_masked_mae_bwd_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), y_hat.numel(), int(mask_nans),
-                                      grad_out.data_ptr(), count.data_ptr(), grad.data_ptr(), _stream(grad)),
-           "sgp_masked_mae_bwd_f32")
-    return grad
-
-
 # ---------------------------------------------------------------- training step (train.hip)
 LOSS_KINDS = {"mae": 0, "mse": 1, "mape": 2}
 METRIC_COLS = 6     # per horizon step: sum |d|, its count, sum d^2, sum |d / y|, its count, sum of the counted y
@@ -1624,6 +1596,8 @@ def masked_loss(y_hat, y, mask=None, kind="mae", at=None, mask_nans=False):
     lib = require_gpu()
     _bhr(y_hat, y, mask, "masked_loss")
     B, H, R, at = _loss_dims(y, at)
+    if not y.numel():                                                   # nothing counts (and no address): 0, as tsl
+        return torch.zeros((), dtype=torch.float32, device=y.device), torch.zeros(1, dtype=torch.float64, device=y.device)
     loss = torch.empty((), dtype=torch.float32, device=y.device)
     count = torch.empty(1, dtype=torch.float64, device=y.device)
     work = torch.empty(max(1, lib.sgp_masked_loss_workspace_doubles(B, H, R, at)), dtype=torch.float64, device=y.device)

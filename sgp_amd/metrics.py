@@ -11,7 +11,6 @@ import copy
 import torch
 
 from . import hip
-from .nn.models.sgp_model import masked_mae
 from .readout import TSL_EPSILON, _scaler_param
 
 # columns of the state (hip.METRIC_COLS)
@@ -226,8 +225,8 @@ def masked_loss(y_hat, y, mask=None, kind="mae", at=None, mask_nans=False):
     if y_hat.shape != y.shape or (mask is not None and mask.shape != y.shape):
         raise ValueError(f"masked_{kind}: shapes differ: {tuple(y_hat.shape)}, {tuple(y.shape)}"
                          + ("" if mask is None else f", mask {tuple(mask.shape)}"))
-    if y.dim() < 2:
-        raise ValueError(f"masked_{kind}: expected [batch, horizon, ...]")
+    if y.dim() < 2 and at is not None:
+        raise ValueError(f"masked_{kind}: at={at} needs [batch, horizon, ...]")
     dev = y_hat.device
     if not y_hat.is_cuda:
         hip.require_gpu()
@@ -235,8 +234,15 @@ def masked_loss(y_hat, y, mask=None, kind="mae", at=None, mask_nans=False):
     yh = y_hat.to(dev, torch.float32).contiguous()
     yt = y.to(dev, torch.float32).contiguous()
     m = None if mask is None else mask.to(dev).bool().to(torch.uint8).contiguous()
+    if y.dim() < 2:                                                     # without `at` the kernel sees one flat row anyway
+        yh, yt, m = (None if t is None else t.reshape(1, 1, t.numel()) for t in (yh, yt, m))
     loss = _MaskedLossFn.apply(yh, yt, m, kind, at, bool(mask_nans))
     return loss if y_hat.is_cuda else loss.cpu()
+
+
+def masked_mae(y_hat, y, mask=None, mask_nans=False):
+    """tsl ``MaskedMAE`` as a loss over a tensor of any rank: the loss every model here trains with."""
+    return masked_loss(y_hat, y, mask, "mae", None, mask_nans)
 
 
 def masked_mse(y_hat, y, mask=None, mask_nans=False, at=None):

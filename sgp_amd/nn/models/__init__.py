@@ -1,9 +1,10 @@
 from .esn_model import ESNModel
-from .sgp_model import OnlineSGPModel, SGPInputEncoder, SGPModel, masked_mae
+from .sgp_model import OnlineSGPModel, SGPInputEncoder, SGPModel
 from .gated_gn_model import GatedGraphNetwork, GatedGraphNetworkMLPModel, GatedGraphNetworkModel
 from .rnn_model import FCRNNModel, RNNModel
 from .dcrnn_model import DCRNNModel
 from .gwnet_model import GraphWaveNetModel
+from ...metrics import masked_mae        # the loss every model trains with lives with the other losses
 
 __all__ = ["SGPInputEncoder", "SGPModel", "OnlineSGPModel", "ESNModel", "masked_mae", "GatedGraphNetwork",
            "GatedGraphNetworkModel", "GatedGraphNetworkMLPModel", "RNNModel", "FCRNNModel", "DCRNNModel",

@@ -367,38 +367,3 @@ class OnlineSGPModel(SGPModel):
         opt_list(parser, '--undirected', type=str_to_bool, nargs='?', const=True, default=False)
         opt_list(parser, '--add-self-loops', type=str_to_bool, nargs='?', const=True, default=False)
         return parser
-
-
-class _MaskedMAEFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, y_hat, y, mask, mask_nans):
-        loss, count = hip.masked_mae(y_hat, y, mask, mask_nans)
-        ctx.save_for_backward(y_hat, y, mask, count)
-        ctx.mask_nans = mask_nans
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        y_hat, y, mask, count = ctx.saved_tensors
-        g = g.to(torch.float32).reshape(1).contiguous()
-        grad = hip.masked_mae_bwd(y_hat, y, mask, ctx.mask_nans, g, count)
-        gy = -grad if ctx.needs_input_grad[1] else None
-        return grad, gy, None, None
-
-
-def masked_mae(y_hat, y, mask=None, mask_nans=False):
-    """tsl ``MaskedMAE`` as a loss (tsl/nn/metrics/metric_base.py:79-96): sum of ``|y_hat - y|`` over the elements
-    the mask keeps (and, with ``mask_nans``, whose difference is not NaN) divided by their number; forward and
-    backward are one HIP kernel each with fp64 sums.  ``mask`` must have the shape of ``y``."""
-    if y_hat.shape != y.shape or (mask is not None and mask.shape != y.shape):
-        raise ValueError(f"masked_mae: shapes differ: {tuple(y_hat.shape)}, {tuple(y.shape)}"
-                         + ("" if mask is None else f", mask {tuple(mask.shape)}"))
-    dev = y_hat.device
-    if not y_hat.is_cuda:
-        hip.require_gpu()
-        dev = torch.device("cuda")
-    yh = y_hat.to(dev, torch.float32).contiguous()
-    yt = y.to(dev, torch.float32).contiguous()
-    m = None if mask is None else mask.to(dev).bool().to(torch.uint8).contiguous()
-    loss = _MaskedMAEFn.apply(yh, yt, m, bool(mask_nans))
-    return loss if y_hat.is_cuda else loss.cpu()

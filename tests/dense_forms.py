@@ -1,6 +1,6 @@
 """Case list of the dense decoder kernels' launch forms and epilogues (tests/test_dense_forms.py on the host,
 tests/test_gpu_dense_forms.py on the device): ``sgp_dense_f32``, ``sgp_dense_wgrad_f32``, ``sgp_row_segsum_f32``,
-``sgp_masked_mae_f32`` / ``_bwd_f32`` (csrc/decoder_mlp.hip) and the grouped input layer ``sgp_grouped_linear_fwd_f32``,
+``sgp_masked_loss_f32`` / ``_bwd_f32`` with kind mae (csrc/train.hip) and the grouped input layer ``sgp_grouped_linear_fwd_f32``,
 ``_dact``, ``_transpose``, ``_wgrad`` (csrc/decoder.hip), each at the smallest shapes found to reach a form.
 
 A FORM is a tuple:
@@ -336,7 +336,7 @@ SEGSUM = [SegsumCase(f"strided-b{b}-w{w}", "strided", b * 13, w, 13, pad)
 
 MaeCase = namedtuple("MaeCase", "id n mask nans mask_nans grad_out")
 MAE = [MaeCase(f"n{n}-{'mask' if m else 'nomask'}-{'nan' if nn_ else 'fin'}{'-skipnan' if mn else ''}", n, m, nn_, mn, go)
-       for n in (0, 1, 1023, 1024, 1025, 5000)
+       for n in (0, 1, 255, 256, 257, 2047, 2048, 2049, 5000)    # the workgroup (256) and the segment (2048) +- 1
        for (m, nn_, mn, go) in ((False, False, False, 1.0), (True, False, True, 0.37), (True, True, True, -2.5),
                                 (False, True, False, 1.0))]
 

@@ -35,7 +35,7 @@ def test_binding_covers_header(lib):
 
 
 def test_version_and_arch(lib):
-    assert lib.sgp_abi_version() == 3
+    assert lib.sgp_abi_version() == 4
     assert lib.sgp_build_arch() == b"gfx950"
 
 

@@ -122,7 +122,7 @@ def test_header_declares_and_library_exports_the_window_entries():
         assert name in hip.SIGNATURES and hasattr(lib, name)
     for cite in ("esn_model.py:41-43", "reservoir.py:158-186"):
         assert cite in header
-    assert lib.sgp_abi_version() == 3
+    assert lib.sgp_abi_version() == 4
 
 
 def test_window_planner_domain():

@@ -1,6 +1,6 @@
 """One numerical case per launch form and epilogue of the dense decoder kernels (tests/dense_forms.py; the host half,
 tests/test_dense_forms.py, shows that every case reaches the forms it names), through the BINDINGS ``hip.dense``,
-``hip.dense_wgrad``, ``hip.row_segsum``, ``hip.masked_mae`` / ``_bwd`` and ``hip.grouped_linear`` / ``_dact`` / ``_transpose``
+``hip.dense_wgrad``, ``hip.row_segsum``, ``hip.masked_loss`` / ``_bwd`` (kind mae) and ``hip.grouped_linear`` / ``_dact`` / ``_transpose``
 / ``_wgrad``.
 
 Every operand and every output a caller can hand over is a view with its row padding inside a buffer with GUARD floats
@@ -258,14 +258,16 @@ def test_masked_mae_matches_fp64(case):
     n_counted = int(counts.sum())
     want = total / n_counted if n_counted else 0.0
     m = dev(mask.astype(np.uint8)) if mask is not None else None
-    loss, count = launch(hip.masked_mae, dev(yh), dev(y), m, c.mask_nans)
+    flat = lambda t: None if t is None else t.view(1, 1, c.n)             # noqa: E731  ([B, H, row]: one flat row)
+    loss, count = launch(hip.masked_loss, flat(dev(yh)), flat(dev(y)), flat(m), "mae", None, c.mask_nans)
     assert float(count.item()) == n_counted
     got = float(loss.item())
     if np.isnan(want):
         assert np.isnan(got)
     else:
         assert abs(got - want) <= 1e-6 * abs(want), (got, want)
-    grad = launch(hip.masked_mae_bwd, dev(yh), dev(y), m, c.mask_nans, torch.tensor([c.grad_out], device="cuda"), count)
+    grad = launch(hip.masked_loss_bwd, flat(dev(yh)), flat(dev(y)), flat(m), "mae", None, c.mask_nans,
+                  torch.tensor([c.grad_out], device="cuda"), count).view(-1)
     scale = np.float32(c.grad_out) / np.float32(max(n_counted, 1))
     sign = np.where(np.isnan(d32), np.nan, np.sign(d32)).astype(np.float64)
     ref = np.where(counts, sign * float(scale), 0.0)

@@ -71,6 +71,20 @@ def test_sort_matches_torch_stable_sort(n):
     assert seen == {{1: 1, 2: 1, 255: 1, 256: 1, 257: 2, 65_536: 2, 65_537: 3}[n]}
 
 
+@pytest.mark.parametrize("E", [1, TILE, TILE + 1, 256 * TILE + 1])
+def test_sort_at_the_edges_of_the_digit_scan(E):
+    """n = 300: two digit passes.  256 threads scan a digit's row of tile counts, so 256 tiles + 1 item give a scan
+    thread two tiles and the last threads none."""
+    n = 300
+    assert ET.sort_plan(n, E).passes == 2
+    keys = torch.randint(0, n, (E,), generator=torch.Generator().manual_seed(E))
+    want = torch.sort(keys, stable=True)[1].to(torch.int32)
+    want_ptr = torch.searchsorted(keys[want.long()], torch.arange(n + 1)).to(torch.int32)
+    for dtype in (torch.int32, torch.int64):
+        order, ptr = ET.stable_sort_by_key(keys.to(dtype).cuda(), n)
+        assert torch.equal(order.cpu(), want) and torch.equal(ptr.cpu(), want_ptr), (E, dtype)
+
+
 @pytest.mark.parametrize("n,E", [(37, 500), (300, 2 * TILE + 1), (70_000, 3000)])
 def test_payload_chaining_gives_src_pos(n, E):
     g = torch.Generator().manual_seed(E)
@@ -249,6 +263,21 @@ def test_gated_equals_the_torch_build(chunk, dtype):
     same_edge_plan(t.gated(none.to(dtype).cuda(), 7, chunk), edge_plan(none, 7, chunk), "empty")
     strided = torch.cartesian_prod(torch.arange(9), torch.arange(9)).T  # [2, E] with strides (1, 2)
     same_edge_plan(t.gated(strided.to(dtype).cuda(), 9, chunk), edge_plan(strided, 9, chunk), "strided")
+
+
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 2049])
+def test_chunk_tables_at_the_edges_of_the_node_scan(n):
+    """1024 threads scan the nodes' chunk counts: one node, one short of / exactly / one past a node per thread, and
+    two nodes per thread with the last threads idle.  In-degrees cycle through chunk + 1, 0, 1 and chunk."""
+    chunk = 4
+    g = torch.Generator().manual_seed(n)
+    deg = torch.tensor([chunk + 1, 0, 1, chunk])[torch.arange(n) % 4]
+    dst = torch.repeat_interleave(torch.arange(n), deg)
+    dst = dst[torch.randperm(dst.numel(), generator=g)]
+    ei = torch.stack([torch.randint(0, n, (dst.numel(),), generator=g), dst])
+    ref = edge_plan(ei, n, chunk, keep_order=True)
+    assert ref.n_fix == (n + 3) // 4 and ref.n_chunks == n + ref.n_fix     # only chunk + 1 splits, into two
+    same_edge_plan(ET.EdgeTables().gated(ei.cuda(), n, chunk, keep_order=True), ref, f"n={n}", order=True)
 
 
 # --------------------------------------------------------------------------------------------------------- routing

@@ -93,7 +93,7 @@ def test_library_exports_subgraph_entry_points():
     for name in NEW_SYMBOLS:
         assert hasattr(raw, name), name
         assert name in hip.SIGNATURES, name
-    assert lib.sgp_abi_version() == 3
+    assert lib.sgp_abi_version() == 4
     # 16 384 flags per tile; sizes up to 2^31 - 1
     assert [lib.sgp_compact_tiles(n) for n in (0, 1, 16384, 16385, 2 ** 31 - 1, 2 ** 31)] == [0, 1, 1, 2, 2 ** 17, -1]
     # argument checks come before anything touches a device
