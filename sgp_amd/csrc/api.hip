@@ -14,6 +14,22 @@ int fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
+int check_hop_operands(const char* entry, const HopOperands& o, const HopLimits& lim) {
+    SGP_REQUIRE(o.X && o.Y, "%s: null pointer", entry);
+    SGP_REQUIRE(o.n_rows >= 0 && o.n_cols >= 0 && o.batch >= 0 && o.feat >= 0, "%s: negative size", entry);
+    SGP_REQUIRE(o.Xh || !lim.own_needs_halo || o.n_own >= o.n_cols, "%s: n_own < n_cols needs X_halo", entry);
+    SGP_REQUIRE(!o.Xh || (o.n_own >= 0 && o.n_own <= o.n_cols), "%s: n_own = %d outside 0 .. n_cols = %d", entry,
+                o.n_own, o.n_cols);
+    const int64_t own = o.Xh ? o.n_own : o.n_cols, far = o.n_cols - own;
+    SGP_REQUIRE((!lim.own_floats || own * o.xrs < lim.own_floats) && (!lim.far_floats || far * o.xhrs < lim.far_floats) &&
+                (!lim.y_floats || o.n_rows * o.yrs < lim.y_floats),
+                "%s: rows x row stride beyond the kernel's offset range (use sgp_spmm_csr_f32)", entry);
+    if (o.empty()) return 0;
+    if (lim.feat_multiple && o.feat % lim.feat_multiple != 0)
+        return fail(lim.feat_code, "%s: feat=%d is not a multiple of %d", entry, o.feat, lim.feat_multiple);
+    SGP_REQUIRE(!lim.aligned16 || o.aligned(), "%s: strides/pointers must be 16-byte aligned", entry);
+    return 0;
+}
 long tune(const char* key, long dflt) {
     const char* e = getenv("SGP_TUNE");
     if (!e) return dflt;

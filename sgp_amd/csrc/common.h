@@ -43,9 +43,35 @@ struct Predicate { const int* flag; int want; };
 
 __host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The operand block every hop entry takes (include/sgp_amd.h), in the ABI's order; strides in floats.
+struct HopOperands {
+    const float* X;  int64_t xrs, xbs;                    // owned source rows
+    const float* Xh; int64_t xhrs, xhbs; int32_t n_own;   // halo rows (columns >= n_own), or nullptr: every column is in X
+    float* Y;        int64_t yrs, ybs;
+    int32_t n_rows, n_cols, batch, feat;
+    const int32_t* pred; int32_t run_if; sgp_stream_t stream;
+    bool empty() const { return n_rows == 0 || batch == 0 || feat == 0; }
+    bool aligned() const {                                // 16-byte bases, strides in whole float4s
+        return aligned16(X) && aligned16(Y) && xrs % 4 == 0 && xbs % 4 == 0 && yrs % 4 == 0 && ybs % 4 == 0 &&
+               (!Xh || (aligned16(Xh) && xhrs % 4 == 0 && xhbs % 4 == 0));
+    }
+};
+// What a hop kernel asks of the block beyond the common rules (DESIGN.md 4.5 has the table and the reason for every value)
+struct HopLimits {
+    int64_t own_floats, far_floats, y_floats;   // rows x row stride of X | X_halo | Y stays below this; 0: no bound
+    bool aligned16;                             // HopOperands::aligned() required
+    int feat_multiple, feat_code;               // feat % feat_multiple != 0 fails with feat_code
+    bool own_needs_halo;                        // without a halo n_own must cover n_cols (else it is ignored)
+};
+// The one judge of a hop operand block: 0, or sgp::fail(...) with a message that starts with `entry`.  Null pointers,
+// sizes, n_own and row offsets are judged always; feat and alignment only where there is work (!o.empty()).
+int check_hop_operands(const char* entry, const HopOperands& o, const HopLimits& lim);
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 }  // namespace sgp
 
+#define SGP_STR_(x) #x
+#define SGP_STR(x) SGP_STR_(x)        // the spelling of a macro's expansion (entry names built by SGP_SPLIT_NAME)
 #define SGP_REQUIRE(cond, ...) \
     do { if (!(cond)) return sgp::fail(SGP_EINVAL, __VA_ARGS__); } while (0)

@@ -489,15 +489,14 @@ int sgp_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val
                      int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
                      const int32_t* pred, int32_t run_if, sgp_stream_t stream) {
     const sgp::Predicate pr{pred, run_if};
-    SGP_REQUIRE(rowptr && col && val && X && Y, "sgp_spmm_csr_f32: null pointer");
-    SGP_REQUIRE(n_rows >= 0 && n_cols >= 0 && batch >= 0 && feat >= 0, "sgp_spmm_csr_f32: negative size");
-    SGP_REQUIRE(Xh != nullptr || n_own >= n_cols, "sgp_spmm_csr_f32: n_own < n_cols needs X_halo");
-    if (n_rows == 0 || batch == 0 || feat == 0) return 0;
+    const sgp::HopOperands o{X, xrs, xbs, Xh, xhrs, xhbs, n_own, Y, yrs, ybs, n_rows, n_cols, batch, feat, pred, run_if, stream};
+    SGP_REQUIRE(rowptr && col && val, "sgp_spmm_csr_f32: null pointer");
+    // 64-bit addressing and a scalar kernel for what is not aligned: no limit but this entry's reading of n_own
+    if (int rc = sgp::check_hop_operands("sgp_spmm_csr_f32", o, {0, 0, 0, false, 0, 0, true})) return rc;
+    if (o.empty()) return 0;
     hipStream_t s = (hipStream_t)stream;
     Src src{X, xrs, xbs, Xh ? Xh : X, xhrs, xhbs, Xh ? n_own : 0x7fffffff, pr.flag, pr.want};
-    const bool vec = feat % 4 == 0 && xrs % 4 == 0 && xbs % 4 == 0 && yrs % 4 == 0 && ybs % 4 == 0 &&
-                     sgp::aligned16(X) && sgp::aligned16(Y) &&
-                     (!Xh || (xhrs % 4 == 0 && xhbs % 4 == 0 && sgp::aligned16(Xh)));
+    const bool vec = feat % 4 == 0 && o.aligned();
     const unsigned gx = (n_rows + 3) / 4;
     if (sgp_spmm_csr_form(feat, vec, pr.flag != nullptr) == 0) {
         SGP_REQUIRE(batch <= 65535, "sgp_spmm_csr_f32: scalar path supports batch <= 65535");
@@ -539,28 +538,21 @@ int sgp_spmm_tiled_f32(const int32_t* trow, const int32_t* uptr, const int32_t* 
                        int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
                        const int32_t* pred, int32_t run_if, sgp_stream_t stream) {
     const sgp::Predicate pr{pred, run_if};
-    SGP_REQUIRE(trow && uptr && ucol && erow && ecol && eval && X && Y, "sgp_spmm_tiled_f32: null pointer");
-    SGP_REQUIRE(tile_rows > 0 && n_tiles >= 0 && n_rows >= 0 && batch >= 0 && max_union >= 0 &&
-                max_row_edges >= 0 && max_row_edges % 16 == 0, "sgp_spmm_tiled_f32: bad size");
+    const sgp::HopOperands o{X, xrs, xbs, Xh, xhrs, xhbs, n_own, Y, yrs, ybs, n_rows, n_cols, batch, feat, pred, run_if, stream};
+    SGP_REQUIRE(trow && uptr && ucol && erow && ecol && eval, "sgp_spmm_tiled_f32: null pointer");
+    SGP_REQUIRE(tile_rows > 0 && n_tiles >= 0 && max_union >= 0 && max_row_edges >= 0 && max_row_edges % 16 == 0,
+                "sgp_spmm_tiled_f32: bad size");
     SGP_REQUIRE((long long)tile_rows * n_tiles >= n_rows, "sgp_spmm_tiled_f32: tiles do not cover rows");
-    {
-        const long long own = Xh ? n_own : n_cols, far = Xh ? n_cols - n_own : 0;
-        SGP_REQUIRE(n_cols >= 0 && own >= 0 && far >= 0 && own * xrs < (1ll << 31) && far * xhrs < (1ll << 31),
-                    "sgp_spmm_tiled_f32: row offsets exceed 32 bits (use sgp_spmm_csr_f32)");
-    }
-    if (n_rows == 0 || batch == 0 || feat == 0) return 0;
-    if (feat % 64 != 0)
-        return sgp::fail(SGP_EUNSUP, "sgp_spmm_tiled_f32: feat=%d is not a multiple of 64", feat);
+    // source rows at signed 32-bit float offsets (soff), result rows through 64-bit pointers
+    if (int rc = sgp::check_hop_operands("sgp_spmm_tiled_f32", o, {1ll << 31, 1ll << 31, 0, true, 64, SGP_EUNSUP, false}))
+        return rc;
+    if (o.empty()) return 0;
     if (max_union > kTiledCapacity)
         return sgp::fail(SGP_EUNSUP, "sgp_spmm_tiled_f32: a tile references %d distinct rows, LDS stage holds %d",
                          max_union, kTiledCapacity);
     int32_t rpg = 0, nb = 0;
     const int form_rc = sgp_spmm_tiled_form(tile_rows, max_row_edges, &rpg, &nb);
     if (form_rc && rpg == 0) return form_rc;               // beyond the limits (a pair without a kernel: below, as before)
-    SGP_REQUIRE(xrs % 4 == 0 && xbs % 4 == 0 && yrs % 4 == 0 && ybs % 4 == 0 &&
-                sgp::aligned16(X) && sgp::aligned16(Y) &&
-                (!Xh || (xhrs % 4 == 0 && xhbs % 4 == 0 && sgp::aligned16(Xh))),
-                "sgp_spmm_tiled_f32: strides/pointers must be 16-byte aligned");
     TiledArgs a;
     a.trow = trow; a.uptr = uptr; a.ucol = ucol; a.erow = erow; a.ecol = ecol; a.eval = eval;
     a.tile_rows = tile_rows; a.n_tiles = n_tiles;

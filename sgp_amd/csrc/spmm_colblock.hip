@@ -156,19 +156,15 @@ int sgp_spmm_colblock_f32(const int32_t* plan, const int32_t* segptr, const int3
                           int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
                           const int32_t* pred, int32_t run_if, sgp_stream_t stream) {
     const sgp::Predicate pr{pred, run_if};
-    SGP_REQUIRE(plan && segptr && wg_row0 && X && Y, "sgp_spmm_colblock_f32: null pointer");
-    SGP_REQUIRE(n_wg >= 0 && n_blocks >= 0 && n_rows >= 0 && n_cols >= 0 && batch >= 0 && feat >= 0,
-                "sgp_spmm_colblock_f32: bad size");
+    const sgp::HopOperands o{X, xrs, xbs, X_halo, xhrs, xhbs, n_own, Y, yrs, ybs, n_rows, n_cols, batch, feat, pred, run_if, stream};
+    SGP_REQUIRE(plan && segptr && wg_row0, "sgp_spmm_colblock_f32: null pointer");
+    SGP_REQUIRE(n_wg >= 0 && n_blocks >= 0, "sgp_spmm_colblock_f32: bad size");
     SGP_REQUIRE(n_cols < (1 << 22), "sgp_spmm_colblock_f32: more than 2^22 columns (use sgp_spmm_csr_f32)");
-    if (n_rows == 0 || batch == 0 || feat == 0 || n_wg == 0) return 0;
-    if (feat % 64 != 0)
-        return sgp::fail(SGP_EUNSUP, "sgp_spmm_colblock_f32: feat=%d is not a multiple of 64", feat);
-    SGP_REQUIRE(xrs % 4 == 0 && xbs % 4 == 0 && yrs % 4 == 0 && ybs % 4 == 0 && sgp::aligned16(X) && sgp::aligned16(Y),
-                "sgp_spmm_colblock_f32: strides/pointers must be 16-byte aligned");
-    SGP_REQUIRE((long long)n_cols * xrs < (1ll << 40) && feat / 64 <= 65535, "sgp_spmm_colblock_f32: operand too large");
-    SGP_REQUIRE(!X_halo || (n_own >= 0 && n_own <= n_cols && xhrs % 4 == 0 && xhbs % 4 == 0 && sgp::aligned16(X_halo) &&
-                            (long long)(n_cols - n_own) * xhrs < (1ll << 40)),
-                "sgp_spmm_colblock_f32: halo rows must be 16-byte aligned, n_own within the columns");
+    // 64-bit addressing: 2^40 floats is a bound on nonsense, not on the kernel
+    if (int rc = sgp::check_hop_operands("sgp_spmm_colblock_f32", o, {1ll << 40, 1ll << 40, 0, true, 64, SGP_EUNSUP, false}))
+        return rc;
+    if (o.empty() || n_wg == 0) return 0;
+    SGP_REQUIRE(feat / 64 <= 65535, "sgp_spmm_colblock_f32: feat = %d beyond the grid's 65535 column blocks", feat);
     CbArgs a;
     a.plan = reinterpret_cast<const uint2*>(plan); a.segptr = segptr; a.wg_row0 = wg_row0;
     a.x = X; a.xrs = xrs; a.xbs = xbs; a.y = Y; a.yrs = yrs; a.ybs = ybs;

@@ -486,25 +486,16 @@ int sgp_spmm_res_f32(const int32_t* uptr, const int32_t* ucol, const int32_t* us
                      int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
                      const int32_t* pred, int32_t run_if, sgp_stream_t stream) {
     const sgp::Predicate pr{pred, run_if};
-    SGP_REQUIRE(uptr && ucol && usplit && gptr && gsup && gidx && gw && rowmap && X && Y,
-                "sgp_spmm_res_f32: null pointer");
-    SGP_REQUIRE(n_tiles >= 0 && n_rows >= 0 && batch >= 0 && max_union >= 0 && max_tile_quads >= 0,
-                "sgp_spmm_res_f32: bad size");
-    {
-        const long long own = Xh ? n_own : n_cols, far = Xh ? n_cols - n_own : 0;
-        SGP_REQUIRE(n_cols >= 0 && own >= 0 && far >= 0 && own * xrs < (1ll << 30) && far * xhrs < (1ll << 30) &&
-                    (long long)n_rows * yrs < (1ll << 30),
-                    "sgp_spmm_res_f32: row offsets exceed 32 bits (use sgp_spmm_csr_f32)");
-    }
-    if (n_rows == 0 || batch == 0 || feat == 0) return 0;
-    if (feat % 64 != 0)
-        return sgp::fail(SGP_EUNSUP, "sgp_spmm_res_f32: feat=%d is not a multiple of 64", feat);
+    const sgp::HopOperands o{X, xrs, xbs, Xh, xhrs, xhbs, n_own, Y, yrs, ybs, n_rows, n_cols, batch, feat, pred, run_if, stream};
+    SGP_REQUIRE(uptr && ucol && usplit && gptr && gsup && gidx && gw && rowmap, "sgp_spmm_res_f32: null pointer");
+    SGP_REQUIRE(n_tiles >= 0 && max_union >= 0 && max_tile_quads >= 0, "sgp_spmm_res_f32: bad size");
+    // source and result rows at unsigned 32-bit BYTE offsets (voff, the result stores): 2^30 floats
+    if (int rc = sgp::check_hop_operands("sgp_spmm_res_f32", o, {1ll << 30, 1ll << 30, 1ll << 30, true, 64, SGP_EUNSUP, false}))
+        return rc;
+    if (o.empty()) return 0;
     if (max_union > sgp_spmm_res_max_union() || max_tile_quads > sgp_spmm_res_max_quads())
         return sgp::fail(SGP_EUNSUP, "sgp_spmm_res_f32: tile working set (%d rows, %d quads) exceeds LDS (%d, %d)",
                          max_union, max_tile_quads, sgp_spmm_res_max_union(), sgp_spmm_res_max_quads());
-    SGP_REQUIRE(xrs % 4 == 0 && xbs % 4 == 0 && yrs % 4 == 0 && ybs % 4 == 0 && sgp::aligned16(X) &&
-                sgp::aligned16(Y) && (!Xh || (xhrs % 4 == 0 && xhbs % 4 == 0 && sgp::aligned16(Xh))),
-                "sgp_spmm_res_f32: strides/pointers must be 16-byte aligned");
     ResArgs a;
     a.uptr = uptr; a.ucol = ucol; a.usplit = usplit; a.gptr = gptr; a.gsup = gsup; a.gidx = gidx; a.gw = gw;
     a.rowmap = rowmap;

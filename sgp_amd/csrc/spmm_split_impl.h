@@ -579,42 +579,28 @@ extern "C" int32_t SGP_SPLIT_NAME(rows_per_wave)(void) { return 16; }
 extern "C" int32_t SGP_SPLIT_NAME(max_feat)(void) { return MAXFEAT; }
 
 namespace {
-int launch_split(const int32_t* hdr, const int32_t* rowid, const int32_t* ucol, const void* afr,
-                 const int32_t* adr, const float* rinv,
-                 int32_t n_tiles,
-                 const float* X, int64_t x_row_stride, int64_t x_batch_stride,
-                 const float* X_halo, int64_t xh_row_stride, int64_t xh_batch_stride, int32_t n_own,
-                 float* Y, int64_t y_row_stride, int64_t y_batch_stride,
-                 int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
+int launch_split(const char* entry, const int32_t* hdr, const int32_t* rowid, const int32_t* ucol, const void* afr,
+                 const int32_t* adr, const float* rinv, int32_t n_tiles, const sgp::HopOperands& o,
                  const float* x_tab, int32_t accumulate, int32_t t_chunk,
-                 int32_t walk, const int32_t* band_first, int32_t n_bands,
-                 const int32_t* pred, int32_t run_if, sgp_stream_t stream) {
-    const sgp::Predicate pr{pred, run_if};
-    SGP_REQUIRE(n_tiles >= 0 && batch >= 0 && n_rows >= 0 && n_cols >= 0, "spmm_split: negative size");
+                 int32_t walk, const int32_t* band_first, int32_t n_bands) {
+    const int32_t n_rows = o.n_rows, n_cols = o.n_cols, batch = o.batch, feat = o.feat;
+    SGP_REQUIRE(n_tiles >= 0 && batch >= 0 && n_rows >= 0 && n_cols >= 0, "%s: negative size", entry);
     if (n_tiles == 0 || batch == 0 || n_rows == 0) return 0;
-    SGP_REQUIRE(walk >= 0 && walk <= 3, "spmm_split: walk = %d (0 chosen here, 1 tile-major, 2 time-major, 3 banded)", walk);
+    SGP_REQUIRE(walk >= 0 && walk <= 3, "%s: walk = %d (0 chosen here, 1 tile-major, 2 time-major, 3 banded)", entry, walk);
     SGP_REQUIRE(walk != 3 || (band_first != nullptr && n_bands >= 1 && n_bands <= n_tiles),
-                "spmm_split: band table of %d bands for %d tiles", n_bands, n_tiles);
-    SGP_REQUIRE(hdr && rowid && ucol && afr && adr && rinv && X && Y && x_tab, "spmm_split: null pointer");
-    SGP_REQUIRE(feat > 0 && feat % 16 == 0 && feat <= MAXFEAT, "spmm_split: feat = %d is not a multiple of 16 up to %d", feat, MAXFEAT);
-    SGP_REQUIRE(sgp::aligned16(X) && x_row_stride % 4 == 0 && x_batch_stride % 4 == 0 &&
-                sgp::aligned16(Y) && y_row_stride % 4 == 0 && y_batch_stride % 4 == 0,
-                "spmm_split: X and Y rows must be 16-byte aligned");
-    {
-        const long long own = X_halo ? n_own : n_cols, far = X_halo ? n_cols - n_own : 0;
-        SGP_REQUIRE(own >= 0 && far >= 0 && own * x_row_stride < (1ll << 29) && far * xh_row_stride < (1ll << 29) &&
-                    (long long)n_rows * y_row_stride < (1ll << 30), "spmm_split: rows beyond 32-bit byte offsets");
-        SGP_REQUIRE(!X_halo || (sgp::aligned16(X_halo) && xh_row_stride % 4 == 0 && xh_batch_stride % 4 == 0),
-                    "spmm_split: halo rows must be 16-byte aligned");
-    }
+                "%s: band table of %d bands for %d tiles", entry, n_bands, n_tiles);
+    SGP_REQUIRE(hdr && rowid && ucol && afr && adr && rinv && x_tab, "%s: null pointer", entry);
+    // 32-bit byte offsets: result rows below 2^32 bytes; source rows below 2^31, bit 31 of xoff marks a halo row
+    if (int rc = sgp::check_hop_operands(entry, o, {1ll << 29, 1ll << 29, 1ll << 30, true, 16, SGP_EINVAL, false})) return rc;
+    SGP_REQUIRE(feat > 0 && feat <= MAXFEAT, "%s: feat = %d outside 16 .. %d (the scale table's LDS)", entry, feat, MAXFEAT);
     SplitArgs a;
     a.hdr = hdr; a.rowid = rowid; a.ucol = ucol; a.afr = (const h8*)afr; a.adr = adr; a.rinv = rinv;
     a.n_tiles = n_tiles; a.tiles_per_xcd = (n_tiles + 7) / 8;
-    a.X = X; a.xrs = x_row_stride; a.xbs = x_batch_stride;
-    a.XH = X_halo; a.xhrs = xh_row_stride; a.xhbs = xh_batch_stride; a.n_own = X_halo ? n_own : 0x7fffffff;
-    a.Y = Y; a.yrs = y_row_stride; a.ybs = y_batch_stride;
+    a.X = o.X; a.xrs = o.xrs; a.xbs = o.xbs;
+    a.XH = o.Xh; a.xhrs = o.xhrs; a.xhbs = o.xhbs; a.n_own = o.Xh ? o.n_own : 0x7fffffff;
+    a.Y = o.Y; a.yrs = o.yrs; a.ybs = o.ybs;
     a.batch = batch; a.nslice = feat / 16;
-    a.xtab = x_tab; a.pred = pr.flag; a.pred_want = pr.want;
+    a.xtab = x_tab; a.pred = o.pred; a.pred_want = o.run_if;
     const bool auto_tc = t_chunk <= 0;
     if (t_chunk <= 0) {
         // time steps per workgroup: long chunks amortise the plan load (A fragments: ~1.6 units' worth of staging per
@@ -662,14 +648,14 @@ int launch_split(const int32_t* hdr, const int32_t* rowid, const int32_t* ucol, 
     const int n_tchunks = (batch + t_chunk - 1) / t_chunk;
     a.chunks_per_xcd = (n_tchunks + 7) / 8;
     SGP_REQUIRE(8ll * n_tiles * a.chunks_per_xcd < (1ll << 31), "spmm_split: %d tiles x %d time chunks beyond one launch", n_tiles, n_tchunks);
-    auto kern = X_halo ? (accumulate ? spmm_split<true, true> : spmm_split<true, false>)
+    auto kern = o.Xh ? (accumulate ? spmm_split<true, true> : spmm_split<true, false>)
                        : (accumulate ? spmm_split<false, true> : spmm_split<false, false>);
     const int lds_bytes = NBUF * BUF + 2 * feat * 4;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, NBUF * BUF + 2 * MAXFEAT * 4);
     if (e != hipSuccess) return sgp::fail((int)e, "spmm_split: LDS attribute: %s", hipGetErrorString(e));
     const unsigned grid = a.time_major ? 8u * (unsigned)n_tiles * (unsigned)((n_tchunks + 7) / 8)
                                        : 8u * (unsigned)a.tiles_per_xcd * (unsigned)n_tchunks;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, (hipStream_t)o.stream, a);
     if (abl & 256) {
         unsigned long long h[8 * NW * 8];
         (void)hipDeviceSynchronize();
@@ -695,9 +681,10 @@ extern "C" int SGP_SPLIT_NAME(f32)(const int32_t* hdr, const int32_t* rowid, con
                                   float* Y, int64_t y_row_stride, int64_t y_batch_stride,
                                   int32_t n_rows, int32_t n_cols, int32_t batch, int32_t feat,
                                   const float* x_tab, int32_t accumulate, int32_t t_chunk, const int32_t* pred, int32_t run_if, sgp_stream_t stream) {
-    return launch_split(hdr, rowid, ucol, afr, adr, rinv, n_tiles, X, x_row_stride, x_batch_stride, X_halo, xh_row_stride,
-                        xh_batch_stride, n_own, Y, y_row_stride, y_batch_stride, n_rows, n_cols, batch, feat, x_tab, accumulate,
-                        t_chunk, 0, nullptr, 0, pred, run_if, stream);
+    return launch_split(SGP_STR(SGP_SPLIT_NAME(f32)), hdr, rowid, ucol, afr, adr, rinv, n_tiles,
+                        {X, x_row_stride, x_batch_stride, X_halo, xh_row_stride, xh_batch_stride, n_own, Y, y_row_stride,
+                         y_batch_stride, n_rows, n_cols, batch, feat, pred, run_if, stream},
+                        x_tab, accumulate, t_chunk, 0, nullptr, 0);
 }
 
 extern "C" int SGP_SPLIT_NAME(banded_f32)(const int32_t* hdr, const int32_t* rowid, const int32_t* ucol, const void* afr,
@@ -710,7 +697,8 @@ extern "C" int SGP_SPLIT_NAME(banded_f32)(const int32_t* hdr, const int32_t* row
                                          const float* x_tab, int32_t accumulate, int32_t t_chunk,
                                          int32_t walk, const int32_t* band_first, int32_t n_bands,
                                          const int32_t* pred, int32_t run_if, sgp_stream_t stream) {
-    return launch_split(hdr, rowid, ucol, afr, adr, rinv, n_tiles, X, x_row_stride, x_batch_stride, X_halo, xh_row_stride,
-                        xh_batch_stride, n_own, Y, y_row_stride, y_batch_stride, n_rows, n_cols, batch, feat, x_tab, accumulate,
-                        t_chunk, walk, band_first, n_bands, pred, run_if, stream);
+    return launch_split(SGP_STR(SGP_SPLIT_NAME(banded_f32)), hdr, rowid, ucol, afr, adr, rinv, n_tiles,
+                        {X, x_row_stride, x_batch_stride, X_halo, xh_row_stride, xh_batch_stride, n_own, Y, y_row_stride,
+                         y_batch_stride, n_rows, n_cols, batch, feat, pred, run_if, stream},
+                        x_tab, accumulate, t_chunk, walk, band_first, n_bands);
 }

@@ -45,7 +45,7 @@ def _coalesce(row, col, val, n):
 class _Operands(NamedTuple):
     """What the hop dispatch (``ShiftOperator._select``) needs to know about the operands of a call."""
     batch: int
-    fits32: bool          # the rows of x, y and halo lie within 32-bit element offsets (the LDS-staged kernels)
+    fits32: bool          # the rows of x, y and halo lie below 2^30 floats (res / mix; DESIGN.md 4.5, "The operand block")
     split_layout: bool    # x, y and halo are CUDA views in the split-fp16 hop's alignment and stride range
     halo_aligned: bool    # no halo, or one with a 16-byte aligned pointer and strides (the column-blocked kernel)
     bound: str            # what the caller knows about max |x|: "measured", "finite" or "nonfinite"
@@ -55,6 +55,8 @@ class _Operands(NamedTuple):
 _NOMINAL = _Operands(batch=4, fits32=True, split_layout=True, halo_aligned=True, bound="measured")
 
 
+# The two offset limits the dispatch needs, once each (rows x row stride in floats; table in DESIGN.md 4.5): the split-fp16
+# hop's 2^29 with its alignment rule, and the 2^30 of res / mix, the stricter of the LDS-staged kernels
 def _split_layout_ok(t):
     return t.is_cuda and t.stride(1) % 4 == 0 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 and \
         t.shape[1] * max(t.stride(1), 1) < 2 ** 29
@@ -523,9 +525,9 @@ class ShiftOperator:
         # they ran; until then the generic CSR kernel (exact fp32, no plan) stands in
         if split is not None and tune.get("exact_plans", "lazy") != "eager" and not self._exact_seen:
             return _Choice("spmm_csr_rows", self.device_csr(device), split, lazy=True)
-        # the LDS-staged kernels address rows with 32-bit element offsets (SGP_REQUIRE in csrc: own * xrs,
-        # far * xhrs, n_rows * yrs < 2^30); beyond that -- e.g. a [rows, T, D] halo receive buffer of a
-        # long time chunk, whose row stride is T * D -- the generic CSR kernel (64-bit addressing) serves
+        # the LDS-staged kernels address rows with 32-bit byte offsets (ops.fits32: the 2^30 of the table in DESIGN.md
+        # 4.5); beyond that -- e.g. a [rows, T, D] halo receive buffer of a long time chunk, whose row stride is
+        # T * D -- the generic CSR kernel (64-bit addressing) serves
         tile = None if force in ("csr", "colblock") else self.tile_plan(feat, device, tall=force in (None, "tiled"))
         plan = tile if ops.fits32 or force is not None else None
         # 2. exact fp32 on the matrix cores: the mixed dense (16x16x4) / sparse (4x4x1) kernel where the planner

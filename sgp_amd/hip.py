@@ -1,4 +1,5 @@
-"""ctypes binding of ``libsgp_amd.so`` (C ABI declared in ``include/sgp_amd.h``).
+"""ctypes binding of ``libsgp_amd.so``.  The C ABI is declared in ``include/sgp_amd.h`` and nowhere else: the prototypes
+(``SIGNATURES``), the error and activation codes and the ABI version are parsed from that header at import.
 
 The library is the ONLY compute path of this package: there is no CPU
 fallback.  Importing :mod:`sgp_amd` works without it (so host-side logic can be
@@ -8,6 +9,7 @@ tested on a CPU box), but the first call that needs a kernel raises
 import ctypes
 import json
 import os
+import re
 import subprocess
 
 import torch
@@ -21,266 +23,46 @@ c_i32, c_i64, c_f32, c_f64, c_p = (ctypes.c_int32, ctypes.c_int64,
                                    ctypes.c_void_p)
 c_u64 = ctypes.c_uint64
 
-# name -> (restype, argtypes); mirrors include/sgp_amd.h one to one
-SIGNATURES = {
-    "sgp_abi_version": (ctypes.c_int, []),
-    "sgp_last_error": (ctypes.c_char_p, []),
-    "sgp_build_arch": (ctypes.c_char_p, []),
-    "sgp_tune_value": (c_i64, [ctypes.c_char_p, c_i64]),
-    "sgp_spmm_csr_f32": (ctypes.c_int, [c_p, c_p, c_p,
-                                        c_p, c_i64, c_i64,
-                                        c_p, c_i64, c_i64, c_i32,
-                                        c_p, c_i64, c_i64,
-                                        c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_p]),
-    "sgp_spmm_tiled_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p,
-                                          c_i32, c_i32, c_i32, c_i32,
-                                          c_p, c_i64, c_i64,
-                                          c_p, c_i64, c_i64, c_i32,
-                                          c_p, c_i64, c_i64,
-                                          c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_p]),
-    "sgp_spmm_res_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                        c_i32, c_i32, c_i32,
-                                        c_p, c_i64, c_i64,
-                                        c_p, c_i64, c_i64, c_i32,
-                                        c_p, c_i64, c_i64,
-                                        c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_p]),
-    "sgp_spmm_res_max_union": (c_i32, []),
-    "sgp_spmm_res_max_quads": (c_i32, []),
-    "sgp_spmm_res_tune": (ctypes.c_int, [c_i32]),
-    "sgp_spmm_mix_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                        c_p, c_p, c_p,
-                                        c_i32, c_i32, c_i32,
-                                        c_p, c_i64, c_i64,
-                                        c_p, c_i64, c_i64, c_i32,
-                                        c_p, c_i64, c_i64,
-                                        c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_p]),
-    "sgp_spmm_mix_max_union": (c_i32, []),
-    "sgp_spmm_mix_max_dense": (c_i32, [c_i32]),
-    "sgp_spmm_tiled_max_union": (c_i32, [c_i32]),
-    "sgp_spmm_tiled_max_tile_rows": (c_i32, []),
-    "sgp_spmm_tiled_max_row_edges": (c_i32, []),
-    "sgp_spmm_tiled_form": (ctypes.c_int, [c_i32, c_i32, c_p, c_p]),
-    "sgp_spmm_csr_form": (c_i32, [c_i32, c_i32, c_i32]),
-    "sgp_reservoir_workspace_bytes": (c_i64, [c_i32, c_i32]),
-    "sgp_reservoir_f32": (ctypes.c_int, [c_p, c_i64, c_i64,
-                                         c_p, c_p, c_p,
-                                         c_f64, c_i32,
-                                         c_p, c_i64, c_i64,
-                                         c_p, c_p,
-                                         c_i32, c_i32, c_i32, c_i32, c_p]),
-    "sgp_reservoir_pieces_f32": (ctypes.c_int, [c_p, c_i64, c_i64,
-                                                c_p, c_p, c_p,
-                                                c_f64, c_i32,
-                                                c_p, c_i64, c_i64,
-                                                c_p, c_p,
-                                                c_i32, c_i32, c_i32, c_i64, c_i64, c_i32,
-                                                c_i32, c_i32, c_i32, c_p, c_i32, c_p]),
-    "sgp_reservoir_describe": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_i32,
-                                              c_i32, c_i32, c_i32,
-                                              c_i64, c_i64, c_i32, c_i64, c_i64, c_i32,
-                                              c_p, c_i64]),
-    "sgp_reservoir_fused_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
-    "sgp_reservoir_fused_supported": (c_i32, [c_i32, c_i32, c_i32]),
-    "sgp_reservoir_fused_f32": (ctypes.c_int, [c_p, c_i64, c_i64,
-                                               c_p, c_p, c_p,
-                                               c_p, c_i32,
-                                               c_p, c_i64, c_i64,
-                                               c_p, c_p,
-                                               c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
-    "sgp_reservoir_fused_sums_f32": (ctypes.c_int, [c_p, c_i64, c_i64,
-                                                    c_p, c_p, c_p,
-                                                    c_p, c_i32,
-                                                    c_p, c_i64, c_i64,
-                                                    c_p, c_p, c_p,
-                                                    c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
-    "sgp_reservoir_window_supported": (c_i32, [c_i32, c_i32, c_i32]),
-    "sgp_reservoir_window_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i64]),
-    "sgp_reservoir_window_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_i32,
-                                                c_p, c_i64, c_i64, c_i64, c_i32,
-                                                c_p,
-                                                c_p, c_p, c_p, c_p, c_i32,
-                                                c_p, c_p, c_i64,
-                                                c_p, c_i32,
-                                                c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
-    "sgp_gesn_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
-    "sgp_gesn_tune": (ctypes.c_int, [c_i32]),
-    "sgp_gesn_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i32,
-                                    c_p, c_i64, c_i64, c_p, c_p,
-                                    c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
-    "sgp_gemm_nt_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64,
-                                       c_i32, c_i32, c_i32, c_p]),
-    "sgp_gesn_update_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_i32,
-                                           c_p, c_p, c_i64, c_i32, c_i32, c_p]),
-    "sgp_node_mean_bcast_f32": (ctypes.c_int, [c_p, c_i64, c_i64,
-                                               c_p, c_i64, c_i64, c_p,
-                                               c_i32, c_i32, c_i32, c_p]),
-    "sgp_bcast_rows_f32": (ctypes.c_int, [c_p, c_f32, c_p, c_i64, c_i64,
-                                          c_i32, c_i32, c_i32, c_p]),
-    "sgp_copy_rows_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_i64,
-                                         c_i32, c_i32, c_i32, c_p]),
-    "sgp_gather_rows_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_p, c_p, c_i32,
-                                           c_p, c_i64, c_i64, c_i32, c_i32, c_p]),
-    "sgp_grouped_linear_packed_floats": (c_i64, [c_i32, c_i32, c_i32]),
-    "sgp_grouped_linear_pack_f32": (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_p]),
-    "sgp_grouped_linear_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i32,
-                                              c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p]),
-    "sgp_grouped_linear_fwd_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i32,
-                                                  c_p, c_i64, c_p, c_f64, c_u64,
-                                                  c_i32, c_i32, c_i32, c_i32, c_p]),
-    "sgp_grouped_linear_dact_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i32, c_f64, c_u64, c_p, c_i64, c_i32, c_p]),
-    "sgp_grouped_linear_transpose_f32": (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_p]),
-    "sgp_grouped_linear_wgrad_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p,
-                                                    c_i32, c_i32, c_i32, c_i32, c_p]),
-    "sgp_grouped_linear_form": (ctypes.c_int, [c_i32, c_i32, c_i64, c_i64, c_i32, c_p, c_p]),
-    "sgp_grouped_linear_wgrad_form": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
-    "sgp_abs_max_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_p, c_p]),
-    "sgp_spmm_split_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_p, c_i64, c_i64,
-                                          c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_i64,
-                                          c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_i32, c_p]),
-    "sgp_col_stats_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
-    "sgp_split_prepare_f32": (ctypes.c_int, [c_p, c_f64, c_f64, c_i32, c_p, c_f32, c_f32, c_i32, c_p, c_p, c_p, c_p]),
-    "sgp_spmm_split_wide_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_p, c_i64, c_i64,
-                                               c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_i64,
-                                               c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_i32, c_p]),
-    "sgp_spmm_split_wide_chunks": (c_i32, []),
-    "sgp_spmm_split_wide_max_union": (c_i32, []),
-    "sgp_spmm_split_wide_waves": (c_i32, []),
-    "sgp_spmm_split_wide_rows_per_wave": (c_i32, []),
-    "sgp_spmm_split_wide_max_feat": (c_i32, []),
-    "sgp_spmm_split_chunks": (c_i32, []),
-    "sgp_spmm_split_max_union": (c_i32, []),
-    "sgp_spmm_split_waves": (c_i32, []),
-    "sgp_spmm_split_rows_per_wave": (c_i32, []),
-    "sgp_spmm_split_max_feat": (c_i32, []),
-    "sgp_split_plan_deal": (c_i64, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p]),
-    "sgp_split_plan_fill": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64,
-                                           c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32]),
-    "sgp_split_plan_bands": (c_i64, [c_p, c_i64, c_i32, c_i64, c_i64, c_p]),
-    "sgp_spmm_split_banded_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_p, c_i64, c_i64,
-                                                 c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_i64,
-                                                 c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_i32, c_p, c_i32,
-                                                 c_p, c_i32, c_p]),
-    "sgp_spmm_split_wide_banded_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_p, c_i64, c_i64,
-                                                      c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_i64,
-                                                      c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_i32, c_p, c_i32,
-                                                      c_p, c_i32, c_p]),
-    "sgp_spmm_colblock_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_p, c_i64, c_i64,
-                                             c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_i64,
-                                             c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_p]),
-    "sgp_spmm_colblock_rows_cap": (c_i32, []),
-    "sgp_spmm_colblock_round_pad": (c_i32, []),
-    "sgp_ridge_workspace_bytes": (c_i64, [c_i32, c_i64, c_i32, c_i32]),
-    "sgp_ridge_form": (ctypes.c_int, [c_i32, c_i64, c_i32, c_i32, c_p]),
-    "sgp_ridge_colmeans_f32": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p]),
-    "sgp_ridge_gram_f32": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_i64, c_p, c_i32, c_p, c_i64, c_p, c_i64, c_p]),
-    "sgp_ridge_predict_score_f32": (ctypes.c_int, [c_p, c_i32, c_p, c_i64, c_i64, c_p, c_p, c_i32, c_i32,
-                                                   c_p, c_p, c_i64, c_p, c_i64, c_i64,
-                                                   c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p]),
-    "sgp_dense_packed_floats": (c_i64, [c_i32, c_i32]),
-    "sgp_dense_pack_f32": (ctypes.c_int, [c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p]),
-    "sgp_dense_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i32, c_i32, c_i32,
-                                     c_i32, c_i32, c_i32, c_p, c_i64, c_p, c_i64, c_f64, c_u64, c_i64,
-                                     c_p, c_i64, c_p, c_p, c_p]),
-    "sgp_dense_form": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i64, c_i32, c_p, c_p]),
-    "sgp_dense_wgrad_workspace_floats": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
-    "sgp_dense_wgrad_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_i32,
-                                           c_p, c_i64, c_p, c_p, c_i64, c_p]),
-    "sgp_row_segsum_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i32, c_p, c_p, c_i32, c_p, c_p]),
-    "sgp_multi_sqnorm_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
-    "sgp_adam_step_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_f64,
-                                         c_f64, c_f64, c_f64, c_f64, c_f64, c_i64, c_i32, c_p]),
-    "sgp_masked_metrics_workspace_doubles": (c_i64, [c_i64, c_i32, c_i64, c_i32]),
-    "sgp_masked_metrics_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_i64, c_i32, c_p, c_p, c_i64, c_i32, c_i32,
-                                              c_p, c_i64, c_p, c_p]),
-    "sgp_masked_loss_workspace_doubles": (c_i64, [c_i64, c_i32, c_i64, c_i32]),
-    "sgp_masked_loss_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_i64, c_i32, c_i32, c_i32, c_p, c_i64,
-                                           c_p, c_p, c_p]),
-    "sgp_masked_loss_bwd_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i32, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_p,
-                                               c_p]),
-    "sgp_gated_gn_supported": (c_i32, [c_i32, c_i32]),
-    "sgp_gated_gn_chunk_edges": (c_i32, []),
-    "sgp_gated_gn_workspace_bytes": (c_i64, [c_i32, c_i64, c_i64, c_i64, c_i32, c_i32]),
-    "sgp_gated_gn_edge_f32": (ctypes.c_int, [c_p, c_i64, c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_p, c_i64,
-                                             c_p, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p]),
-    "sgp_gated_gn_edge_bwd_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_i32, c_i32,
-                                                 c_p, c_i32, c_p, c_i64, c_p, c_i32, c_i32, c_p, c_p,
-                                                 c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p,
-                                                 c_p, c_i64, c_p]),
-    "sgp_rnn_window_supported": (c_i32, [c_i32, c_i32]),
-    "sgp_rnn_window_packed_floats": (c_i64, [c_i32, c_i32]),
-    "sgp_rnn_window_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i64]),
-    "sgp_rnn_window_pack_f32": (ctypes.c_int, [c_p, c_i32, c_i32, c_p, c_p]),
-    "sgp_rnn_window_fwd_f32": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_f64, c_u64,
-                                              c_p, c_i32, c_p]),
-    "sgp_rnn_window_bwd_f32": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i64, c_p, c_p, c_p, c_p, c_p, c_i32, c_p]),
-    "sgp_dcrnn_supported": (c_i32, [c_i32, c_i32]),
-    "sgp_diffuse_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_i64,
-                                       c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_p]),
-    "sgp_dcrnn_gates_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i32, c_i32,
-                                           c_p]),
-    "sgp_dcrnn_update_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p,
-                                            c_i64, c_i32, c_i32, c_p]),
-    "sgp_dcrnn_bwd_f32": (ctypes.c_int, [c_i32, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i32,
-                                         c_p]),
-    "sgp_gwnet_supported": (c_i32, [c_i32, c_i32]),
-    "sgp_gwnet_tconv_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_i32, c_i32,
-                                           c_p]),
-    "sgp_gwnet_tconv_bwd_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_i32, c_p]),
-    "sgp_adj_apply_f32": (ctypes.c_int, [c_p, c_i64, c_i32, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64,
-                                         c_i32, c_i32, c_i32, c_i32, c_p]),
-    "sgp_adj_grad_workspace_floats": (c_i64, [c_i32, c_i32]),
-    "sgp_adj_grad_f32": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64,
-                                        c_i32, c_i32, c_i32, c_i32, c_p, c_i64, c_p]),
-    "sgp_row_softmax_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_p]),
-    "sgp_row_softmax_bwd_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i32, c_i32, c_p]),
-    "sgp_gwnet_norm_workspace_doubles": (c_i64, [c_i64, c_i32]),
-    "sgp_gwnet_norm_f32": (ctypes.c_int, [c_i32, c_i32, c_p, c_i64, c_p, c_i64, c_f64, c_u64, c_p, c_p, c_p, c_p,
-                                          c_f64, c_f64, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_p]),
-    "sgp_gwnet_norm_bwd_f32": (ctypes.c_int, [c_i32, c_i32, c_p, c_i64, c_p, c_p, c_p, c_f64, c_u64, c_f64, c_p, c_i64,
-                                              c_p, c_i64, c_p, c_p, c_i64, c_i32, c_p, c_i64, c_p]),
-    "sgp_subgraph_mark": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p]),
-    "sgp_subgraph_expand": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_p, c_i64, c_p]),
-    "sgp_subgraph_edge_flags": (ctypes.c_int, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p]),
-    "sgp_compact_tiles": (c_i64, [c_i64]),
-    "sgp_compact_pack_u8": (ctypes.c_int, [c_p, c_i64, c_p, c_p]),
-    "sgp_compact_count": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p]),
-    "sgp_compact_scatter": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
-    "sgp_subgraph_edges": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p]),
-    "sgp_subgraph_take_edges": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p,
-                                               c_p, c_p, c_p]),
-    "sgp_conn_max_knn": (c_i32, []),
-    "sgp_conn_geo_knn_f64": (ctypes.c_int, [c_p, c_i64, c_i32, c_i32, c_i32, c_f64, c_f64, c_f64, c_p, c_p, c_p]),
-    "sgp_conn_geo_rows_f64": (ctypes.c_int, [c_p, c_i64, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64, c_p, c_p, c_p, c_p,
-                                             c_p]),
-    "sgp_conn_dense_knn": (ctypes.c_int, [c_p, c_i32, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_f64, c_p, c_p, c_p]),
-    "sgp_conn_dense_rows": (ctypes.c_int, [c_p, c_i32, c_i64, c_i64, c_i64, c_i32, c_i32, c_f64, c_p, c_p, c_p, c_p,
-                                           c_p]),
-    "sgp_correntropy_f32": (ctypes.c_int, [c_p, c_i64, c_i32, c_i32, c_i32, c_f64, c_p, c_p, c_i64, c_p]),
-    "sgp_scaler_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i64]),
-    "sgp_scaler_moments_f32": (ctypes.c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_i32, c_i64, c_i32, c_p, c_p, c_i64,
-                                              c_p]),
-    "sgp_scaler_select_f32": (ctypes.c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_f64, c_f64, c_f64, c_i32, c_i64, c_i32,
-                                             c_p, c_p, c_i64, c_p]),
-    "sgp_scaler_finish_f32": (ctypes.c_int, [c_i32, c_p, c_p, c_i64, c_i32, c_f64, c_f64, c_f64, c_p, c_p, c_p]),
-    "sgp_scaler_apply_f32": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p]),
-    "sgp_edge_sort_tile": (c_i32, []),
-    "sgp_edge_sort_passes": (c_i32, [c_i64]),
-    "sgp_edge_sort_workspace_bytes": (c_i64, [c_i64]),
-    "sgp_edge_sort": (ctypes.c_int, [c_p, c_i32, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "sgp_edge_segment_sum_f32": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i64, c_p, c_p]),
-    "sgp_edge_gather_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_i64, c_p, c_p, c_p,
-                                           c_p]),
-    "sgp_edge_chunk_tables": (ctypes.c_int, [c_p, c_i64, c_i32, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p]),
-    "sgp_event_create": (ctypes.c_int, [ctypes.POINTER(c_p)]),
-    "sgp_event_destroy": (ctypes.c_int, [c_p]),
-    "sgp_event_record": (ctypes.c_int, [c_p, c_p]),
-    "sgp_event_elapsed_ms": (ctypes.c_int, [c_p, c_p, ctypes.POINTER(c_f32)]),
-}
+_HEADER = os.path.join(os.path.dirname(_CSRC), "..", "include", "sgp_amd.h")
+_CTYPES = {"int": ctypes.c_int, "int32_t": c_i32, "int64_t": c_i64, "uint64_t": c_u64, "float": c_f32, "double": c_f64,
+           "sgp_stream_t": c_p, "const char *": ctypes.c_char_p}
+_DECL = re.compile(r"([\w\s*]+?)\b(sgp_\w+)\s*\(([\w\s*,]*)\)")
 
-SGP_EINVAL, SGP_EUNSUP, SGP_ENOMEM = -1, -2, -3       # error codes of include/sgp_amd.h
 
-ACT_CODES = {"tanh": 0, "relu": 1, "self_norm": 2, "identity": 3,
-             "tanh_rel": 4}     # tanh with relative accuracy near zero (layers whose bias is tiny: ReservoirLayer.kernel_activation)
+def parse_header(text):
+    """``({name: (restype, [argtypes])}, {macro: int})`` of a header in the plain C of include/sgp_amd.h: every
+    ``ret sgp_name(args);`` declaration and every ``#define SGP_X <integer>``.  Value types map through ``_CTYPES``,
+    ``const char*`` is ``c_char_p``, every other pointer ``c_void_p``; anything else raises, naming the declaration."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    defines = {k: int(v) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(SGP_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#ifdef __cplusplus\n.*?#endif[ \t]*$|^[ \t]*#[^\n]*$", " ", text, flags=re.S | re.M)
+
+    def ctype(tokens, decl):
+        spelled = " ".join(tokens)
+        if spelled not in _CTYPES and "*" not in tokens:
+            raise ValueError(f"include/sgp_amd.h: no ctypes rule for '{spelled}' in: {decl}")
+        return _CTYPES.get(spelled, c_p)
+
+    signatures = {}
+    for decl in (" ".join(d.split()) for d in text.split(";")):
+        if not decl or decl.startswith("typedef "):
+            continue
+        m = _DECL.fullmatch(decl)
+        if m is None:
+            raise ValueError(f"include/sgp_amd.h: cannot parse the declaration: {decl}")
+        args = [a.replace("*", " * ").split() for a in m.group(3).split(",")]
+        args = [] if args == [["void"]] else [a[:-1] if len(a) > 1 and a[-1] != "*" else a for a in args]    # (drop the names)
+        signatures[m.group(2)] = (ctype(m.group(1).replace("*", " * ").split(), decl), [ctype(a, decl) for a in args])
+    return signatures, defines
+
+
+# name -> (restype, argtypes), and the header's integer macros: include/sgp_amd.h is the only place a prototype is written
+with open(_HEADER) as _f:
+    SIGNATURES, _DEFINES = parse_header(_f.read())
+
+SGP_EINVAL, SGP_EUNSUP, SGP_ENOMEM = (_DEFINES[k] for k in ("SGP_EINVAL", "SGP_EUNSUP", "SGP_ENOMEM"))
+# "tanh_rel": tanh with relative accuracy near zero (layers whose bias is tiny: ReservoirLayer.kernel_activation)
+ACT_CODES = {k[len("SGP_ACT_"):].lower(): v for k, v in _DEFINES.items() if k.startswith("SGP_ACT_")}
 
 _lib = None
 
@@ -314,7 +96,7 @@ def load():
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.sgp_abi_version() != 4:
+    if lib.sgp_abi_version() != _DEFINES["SGP_ABI_VERSION"]:
         raise RuntimeError("libsgp_amd.so ABI version mismatch; rebuild it")
     _lib = lib
     return lib
@@ -660,7 +442,7 @@ def spmm_split(plan, x, y, profile, t_chunk=0, halo=None, n_own=None, predicated
             p.hdr.data_ptr(), p.rowid.data_ptr(), p.ucol.data_ptr(), p.afr.data_ptr(), p.adr.data_ptr(),
             p.rinv.data_ptr(), p.n_tiles,
             *ops, p.n_rows, p.n_cols, x.shape[0], x.shape[2],
-            profile.tab.data_ptr(), int(p.accumulate), t_chunk, *how, *pr, _stream(x)), "sgp_spmm_split_f32")
+            profile.tab.data_ptr(), int(p.accumulate), t_chunk, *how, *pr, _stream(x)), entry.__name__)
     return profile
 
 
