@@ -338,8 +338,17 @@ int32_t sgp_spmm_split_wide_max_feat(void);
  * consecutive tiles for sgp_spmm_split_banded_f32: a band closes when the next tile would take its distinct staged
  * rows over col_budget (a tile beyond the budget on its own is a band of one).  Writes band_first (capacity
  * n_tiles + 1): first tile of every band, then n_tiles; returns the number of bands.
- * All three check their CSR (rowptr[0] == 0, non-decreasing, rowptr[n_rows] <= nnz = the length of col / val) and
+ * sgp_split_plan_order: a dealing order for a SQUARE operator's rows (row ids = column ids) worked out from the graph
+ * alone: tiles are grown from the lowest-numbered unplaced row by adding, among the unplaced rows the tile's staged
+ * columns name, the one that brings the fewest new columns (ties: most columns already staged, then lowest number) until
+ * max_union columns or waves * rows_per_wave rows are reached; the tile's rows are cut into waves of at most
+ * rows_per_wave rows / 32 * chunks columns by the same rule, waves beyond `waves` go back to the unplaced rows.  Writes
+ * the permutation order[n_rows] (tiles in the order of their seeds, so the sequence keeps the numbering's locality
+ * for the banded walk); returns 0.  Single-threaded and deterministic.
+ * All four check their CSR (rowptr[0] == 0, non-decreasing, rowptr[n_rows] <= nnz = the length of col / val) and
  * let no C++ exception out: SGP_EINVAL / SGP_ENOMEM instead. */
+int sgp_split_plan_order(const int64_t* rowptr, const int64_t* col, int64_t nnz, int64_t n_rows, int64_t n_cols,
+                         int32_t waves, int32_t chunks, int32_t max_union, int32_t rows_per_wave, int64_t* order);
 int64_t sgp_split_plan_deal(const int64_t* rowptr, const int64_t* col, int64_t nnz, int64_t n_rows, int64_t n_cols,
                             const int64_t* order, int64_t n_order,
                             int32_t waves, int32_t chunks, int32_t max_union, int32_t rows_per_wave,

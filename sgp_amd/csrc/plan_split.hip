@@ -257,6 +257,201 @@ extern "C" int64_t sgp_split_plan_deal(const int64_t* rowptr, const int64_t* col
   });
 }
 
+namespace {
+
+// The graph as the ordering pass sees it: the sorted DISTINCT columns of every row, and the rows of every column.
+struct OrderGraph {
+    std::vector<int64_t> rp, cp;           // rp[n_rows + 1] into rc, cp[n_cols + 1] into cr
+    std::vector<int32_t> rc, cr;
+    int32_t deg(int64_t r) const { return (int32_t)(rp[r + 1] - rp[r]); }
+};
+
+// 0, or the message of what is wrong with a column
+const char* order_graph(const int64_t* rowptr, const int64_t* col, int64_t n_rows, int64_t n_cols, OrderGraph& g) {
+    g.rp.assign(n_rows + 1, 0);
+    g.rc.reserve((size_t)rowptr[n_rows]);
+    std::vector<int64_t> c;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        c.assign(col + rowptr[r], col + rowptr[r + 1]);
+        std::sort(c.begin(), c.end());
+        c.erase(std::unique(c.begin(), c.end()), c.end());
+        if (!c.empty() && (c.front() < 0 || c.back() >= n_cols)) return "column out of range";
+        for (int64_t v : c) g.rc.push_back((int32_t)v);
+        g.rp[r + 1] = (int64_t)g.rc.size();
+    }
+    g.cp.assign(n_cols + 1, 0);
+    for (int32_t v : g.rc) ++g.cp[v + 1];
+    for (int64_t v = 0; v < n_cols; ++v) g.cp[v + 1] += g.cp[v];
+    g.cr.resize(g.rc.size());
+    std::vector<int64_t> at(g.cp.begin(), g.cp.end() - 1);
+    for (int64_t r = 0; r < n_rows; ++r)
+        for (int64_t e = g.rp[r]; e < g.rp[r + 1]; ++e) g.cr[at[g.rc[e]]++] = (int32_t)r;
+    return nullptr;
+}
+
+// The greedy of sgp_split_plan_order.  One instance grows tiles (level 0: candidates come from a frontier bucketed by
+// the number of new columns) and, inside a finished tile, waves (level 1: candidates are the tile's own rows).  Both
+// keep, per row, the number of its columns already in the current union -- counted incrementally: a column that
+// joins the union bumps the rows that hold it.
+struct Orderer {
+    const OrderGraph& g;
+    const int64_t n_rows;
+    const int32_t waves, wave_cols, max_union, rows_per_wave;
+    std::vector<uint8_t> placed;
+    std::vector<int32_t> t_mark, t_cnt, t_cnt_at, t_cand;         // tile level: stamps are tile numbers
+    std::vector<int32_t> w_mark, w_cnt, w_cnt_at, in_tile;        // wave level: stamps are wave numbers
+    std::vector<std::vector<int32_t>> bucket;                     // frontier rows by new-column count (lazily updated)
+    std::vector<int32_t> rows, rest, wave_rows, wave_first;
+    int32_t tile = -1, wave = -1, lo = 0;
+    int64_t t_union = 0, w_union = 0, next_row = 0;
+
+    Orderer(const OrderGraph& g_, int64_t n_rows_, int64_t n_cols, int32_t waves_, int32_t chunks, int32_t max_union_, int32_t rpw)
+        : g(g_), n_rows(n_rows_), waves(waves_), wave_cols(32 * chunks), max_union(max_union_), rows_per_wave(rpw),
+          placed(n_rows_, 0), t_mark(n_cols, -1), t_cnt(n_rows_, 0), t_cnt_at(n_rows_, -1), t_cand(n_rows_, -1),
+          w_mark(n_cols, -1), w_cnt(n_rows_, 0), w_cnt_at(n_rows_, -1), in_tile(n_rows_, -1) {
+        int32_t dmax = 0;
+        for (int64_t r = 0; r < n_rows; ++r) dmax = std::max(dmax, g.deg(r));
+        bucket.resize((size_t)dmax + 1);
+    }
+    int32_t t_have(int32_t r) const { return t_cnt_at[r] == tile ? t_cnt[r] : 0; }
+    int32_t w_have(int32_t r) const { return w_cnt_at[r] == wave ? w_cnt[r] : 0; }
+    void t_push(int32_t r) {
+        const int32_t k = g.deg(r) - t_have(r);
+        bucket[k].push_back(r);
+        lo = std::min(lo, k);
+    }
+    void tile_take(int32_t r) {
+        placed[r] = 1;
+        rows.push_back(r);
+        for (int64_t e = g.rp[r]; e < g.rp[r + 1]; ++e) {
+            const int32_t c = g.rc[e];
+            if (t_mark[c] == tile) continue;
+            t_mark[c] = tile;
+            ++t_union;
+            for (int64_t i = g.cp[c]; i < g.cp[c + 1]; ++i) {
+                const int32_t q = g.cr[i];
+                if (placed[q]) continue;
+                if (t_cnt_at[q] != tile) { t_cnt_at[q] = tile; t_cnt[q] = 0; }
+                ++t_cnt[q];
+                if (t_cand[q] == tile) t_push(q);
+            }
+            if (c < n_rows && !placed[c] && t_cand[c] != tile) { t_cand[c] = tile; t_push(c); }    // square: column c names row c
+        }
+    }
+    // best frontier row: fewest new columns, then most columns in the union, then lowest number; -1: none
+    int32_t tile_best() {
+        for (; lo < (int32_t)bucket.size(); ++lo) {
+            std::vector<int32_t>& b = bucket[lo];
+            size_t keep = 0;
+            int32_t best = -1;
+            for (int32_t q : b) {
+                if (placed[q] || t_cand[q] != tile || g.deg(q) - t_have(q) != lo) continue;       // stale entry
+                b[keep++] = q;
+                if (best < 0 || t_have(q) > t_have(best) || (t_have(q) == t_have(best) && q < best)) best = q;
+            }
+            b.resize(keep);
+            if (best >= 0) return best;
+        }
+        return -1;
+    }
+    void grow_tile() {
+        ++tile;
+        rows.clear();
+        t_union = 0;
+        for (auto& b : bucket) b.clear();
+        lo = (int32_t)bucket.size();
+        while (placed[next_row]) ++next_row;
+        tile_take((int32_t)next_row);                              // the seed, whatever its size
+        const size_t cap_rows = (size_t)waves * rows_per_wave;
+        while (rows.size() < cap_rows) {
+            int32_t r = tile_best();
+            if (r < 0) {                                           // nothing on the frontier: the numbering's next row
+                while (next_row < n_rows && placed[next_row]) ++next_row;
+                if (next_row == n_rows) break;
+                r = (int32_t)next_row;
+            }
+            if (t_union + g.deg(r) - t_have(r) > max_union) break;
+            tile_take(r);
+        }
+    }
+    void wave_take(int32_t r) {
+        in_tile[r] = -1;
+        wave_rows.push_back(r);
+        for (int64_t e = g.rp[r]; e < g.rp[r + 1]; ++e) {
+            const int32_t c = g.rc[e];
+            if (w_mark[c] == wave) continue;
+            w_mark[c] = wave;
+            ++w_union;
+            for (int64_t i = g.cp[c]; i < g.cp[c + 1]; ++i) {
+                const int32_t q = g.cr[i];
+                if (in_tile[q] != tile) continue;
+                if (w_cnt_at[q] != wave) { w_cnt_at[q] = wave; w_cnt[q] = 0; }
+                ++w_cnt[q];
+            }
+        }
+    }
+    // cuts rows[] into waves (wave_rows / wave_first); returns their number
+    int32_t cut_waves() {
+        rest.assign(rows.begin(), rows.end());
+        std::sort(rest.begin(), rest.end());
+        for (int32_t r : rest) in_tile[r] = tile;
+        wave_rows.clear();
+        wave_first.assign(1, 0);
+        while (!rest.empty()) {
+            ++wave;
+            w_union = 0;
+            int32_t n_in = 0;
+            size_t at = 0;                                         // the seed: the lowest-numbered row left
+            for (;;) {
+                const int32_t r = rest[at];
+                rest.erase(rest.begin() + (int64_t)at);
+                wave_take(r);
+                if (++n_in == rows_per_wave || rest.empty()) break;
+                at = 0;
+                for (size_t i = 1; i < rest.size(); ++i) {         // (rest is sorted: the first of equals has the lowest number)
+                    const int32_t q = rest[i], b = rest[at];
+                    const int32_t nq = g.deg(q) - w_have(q), nb = g.deg(b) - w_have(b);
+                    if (nq < nb || (nq == nb && w_have(q) > w_have(b))) at = i;
+                }
+                if (w_union + g.deg(rest[at]) - w_have(rest[at]) > wave_cols) break;
+            }
+            wave_first.push_back((int32_t)wave_rows.size());
+        }
+        return (int32_t)wave_first.size() - 1;
+    }
+    void run(int64_t* order) {
+        int64_t n_out = 0;
+        while (n_out < n_rows) {
+            grow_tile();
+            const int32_t n_waves = cut_waves();
+            const int32_t kept = std::min(n_waves, waves);
+            for (int32_t i = 0; i < wave_first[kept]; ++i) order[n_out++] = wave_rows[i];
+            for (int32_t i = wave_first[kept]; i < wave_first[n_waves]; ++i) {     // waves beyond the tile's: unplaced again
+                placed[wave_rows[i]] = 0;
+                next_row = std::min<int64_t>(next_row, wave_rows[i]);
+            }
+        }
+    }
+};
+
+}  // namespace
+
+extern "C" int sgp_split_plan_order(const int64_t* rowptr, const int64_t* col, int64_t nnz, int64_t n_rows, int64_t n_cols,
+                                    int32_t waves, int32_t chunks, int32_t max_union, int32_t rows_per_wave, int64_t* order) {
+  return guarded<int>("sgp_split_plan_order", [&]() -> int {
+    SGP_REQUIRE(rowptr && (col || nnz <= 0) && order, "sgp_split_plan_order: null pointer");
+    SGP_REQUIRE(n_rows >= 0 && n_cols >= 0 && n_rows < (1ll << 31) - 1 && n_cols < (1ll << 31) - 1 && waves >= 1 && chunks >= 1 &&
+                chunks <= (1 << 24) && max_union >= 1 && rows_per_wave >= 1 && (int64_t)waves * rows_per_wave < (1ll << 31),
+                "sgp_split_plan_order: bad size");
+    if (const char* f = rowptr_fault(rowptr, n_rows, nnz)) return sgp::fail(SGP_EINVAL, "sgp_split_plan_order: malformed CSR: %s", f);
+    if (n_rows == 0) return 0;
+    OrderGraph g;
+    if (const char* f = order_graph(rowptr, col, n_rows, n_cols, g)) return sgp::fail(SGP_EINVAL, "sgp_split_plan_order: %s", f);
+    Orderer(g, n_rows, n_cols, waves, chunks, max_union, rows_per_wave).run(order);
+    return 0;
+  });
+}
+
 extern "C" int sgp_split_plan_fill(const int64_t* rowptr, const int64_t* col, const float* val, int64_t nnz, int64_t n_rows, int64_t n_cols,
                                    const int64_t* wave_of_row, const int64_t* slot_of_row, const int64_t* tile_of_wave,
                                    const int64_t* rows_of_wave, int64_t n_waves, int64_t n_tiles,

@@ -357,7 +357,7 @@ class ShiftOperator:
                 if tune.get("split_wide", 1, int) == 0:
                     wide = None
                 plan = plancache.fetch(self, "split", (sorted(lim.items()), wide and sorted(wide.items()),
-                                                       tune.get("split_passes", 1, int)),
+                                                       tune.get("split_passes", 1, int), _split_order_mode()),
                                        lambda: self._build_split_plan(lim, wide))
                 if isinstance(plan, list):
                     plan = SplitPasses(p.to(device) for p in plan)
@@ -384,6 +384,19 @@ class ShiftOperator:
                 self.rowptr.numpy(), self.col.numpy(), self.num_nodes), **lim, **bands)
             if alt is not None and alt.stats["staged_per_row"] < plan.stats["staged_per_row"]:
                 plan = alt
+                plan.stats["order"] = "locality"
+        # square operators: deal the rows as compact blobs of the graph (splitplan.blob_order) where that takes fewer
+        # tiles than the order above -- the hop's time is its tile count (Plan)
+        mode = _split_order_mode()
+        if plan is not None and mode != "off" and self.num_cols == self.num_nodes:
+            given = plan.stats["tiles"]
+            blob = splitplan.blob_order(*args[:2], *args[3:], **lim)
+            tiles = splitplan.deal_tiles(*args[:2], *args[3:], order=blob, **lim)
+            if tiles is not None and (tiles < given or mode == "on"):
+                plan = splitplan.build_split_plan(*args, order=blob, **lim, **bands)
+                plan.stats["order"] = "blob"
+            plan.stats.setdefault("order", "numbering")
+            plan.stats.update(split_order=mode, tiles_given=given, tiles_blob=tiles)
         # a plan that stages many rows per result row (no locality at all) loses to the other kernels
         if plan is not None and (plan.stats["rows_per_wave"] < 0.375 * lim["rows_per_wave"] or
                                  plan.stats["staged_per_row"] > 8):
@@ -656,6 +669,14 @@ class ShiftOperator:
         if on_cpu:
             y = y.cpu()
         return y.reshape(*lead, self.num_nodes, x.shape[-1])
+
+
+def _split_order_mode():
+    """``SGP_TUNE=split_order=off|on|auto``: never / always / where it takes strictly fewer tiles (default)."""
+    mode = tune.get("split_order", "auto")
+    if mode not in ("off", "on", "auto"):
+        raise ValueError(f"SGP_TUNE: split_order={mode!r} is not one of off, on, auto")
+    return mode
 
 
 class SplitPasses(list):

@@ -9,7 +9,7 @@ import tempfile
 
 import torch
 
-VERSION = 8          # (8: split plans carry their band tables) bump when a plan format or a planner's output changes
+VERSION = 9          # (9: split plans may be dealt in blob order and say so in their stats; 8: band tables) bump when a plan format or a planner's output changes
 _dir = None
 stats = {"hits": 0, "misses": 0, "stores": 0}
 

@@ -64,6 +64,16 @@ class SplitPlan:
             self.bands[col_budget] = (first.to(self.ucol.device), int((first[1:] - first[:-1]).max()))
         return self.bands[col_budget]
 
+    def describe(self):
+        """One line on the plan: its size, and which dealing order it took against which tile counts (``split_order``)."""
+        st = self.stats
+        line = (f"split plan: {st['tiles']} tiles, {st['rows_per_tile']:.1f} rows per tile, {st['rows_per_wave']:.2f} rows per wave, "
+                f"{st['staged_per_row']:.2f} staged rows per result row")
+        if "order" in st:
+            line += (f"; rows dealt in {st['order']} order (SGP_TUNE split_order={st['split_order']}: "
+                     f"{st['tiles_given']} tiles in the given order, {st['tiles_blob']} in blob order)")
+        return line
+
 
 def build_bands(ucol, n_cols, col_budget):
     """Band boundaries of a plan's tile list (``ucol[n_tiles, max_union]``, host): consecutive tiles join a band until the
@@ -79,6 +89,49 @@ def build_bands(ucol, n_cols, col_budget):
     if n < 0:
         raise (MemoryError if n == -3 else RuntimeError)("sgp_split_plan_bands: " + lib.sgp_last_error().decode())
     return first[:n + 1].clone()
+
+
+def _host_csr(rowptr, col, n_rows):
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
+    col = np.ascontiguousarray(col, dtype=np.int64)
+    if rowptr.size < n_rows + 1:
+        raise ValueError("rowptr is shorter than n_rows + 1")
+    return rowptr, col
+
+
+def blob_order(rowptr, col, n_rows, n_cols, waves=16, chunks=7, max_union=768, rows_per_wave=16):
+    """Dealing order that makes every tile a compact blob of the graph instead of a run of the numbering (native
+    ``sgp_split_plan_order``; square operators: a tile's candidates are the rows its staged columns name): a
+    permutation of the rows (int64), the same for the same arguments.  A malformed CSR raises ValueError."""
+    import ctypes
+    from . import hip
+    lib = hip.load()
+    rowptr, col = _host_csr(rowptr, col, n_rows)
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    order = np.empty(n_rows, dtype=np.int64)
+    rc = lib.sgp_split_plan_order(ptr(rowptr), ptr(col), col.size, n_rows, n_cols, waves, chunks, max_union, rows_per_wave, ptr(order))
+    if rc != 0:
+        raise (MemoryError if rc == -3 else ValueError)("sgp_split_plan_order: " + lib.sgp_last_error().decode())
+    return order
+
+
+def deal_tiles(rowptr, col, n_rows, n_cols, waves=16, chunks=7, max_union=768, rows_per_wave=16, order=None):
+    """Number of tiles the native deal makes of the rows taken in ``order`` (None: the numbering), without filling a
+    plan; None when a row exceeds a wave's column budget."""
+    import ctypes
+    from . import hip
+    lib = hip.load()
+    rowptr, col = _host_csr(rowptr, col, n_rows)
+    seq = None if order is None else np.ascontiguousarray(order, dtype=np.int64)
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    out = [np.empty(max(n_rows, 1), dtype=np.int64) for _ in range(4)]
+    n_waves = lib.sgp_split_plan_deal(ptr(rowptr), ptr(col), col.size, n_rows, n_cols, None if seq is None else ptr(seq),
+                                      0 if seq is None else seq.size, waves, chunks, max_union, rows_per_wave, *map(ptr, out))
+    if n_waves == -2 or n_waves == 0:
+        return None
+    if n_waves < 0:
+        raise (MemoryError if n_waves == -3 else RuntimeError)("sgp_split_plan_deal: " + lib.sgp_last_error().decode())
+    return int(out[2][n_waves - 1]) + 1
 
 
 def deal_rows(rowptr, col, n_rows, n_cols, waves, chunks, max_union, rows_per_wave=32, order=None):

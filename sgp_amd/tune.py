@@ -14,6 +14,8 @@ Python layer
     split_banded=on|off|<bytes>   split-fp16 hop, banded time-major walk: ``on`` (default) for operators whose source rows of
                             one step exceed an L2 (band budget: graph.SPLIT_BAND_BYTES), a byte count = that band budget for EVERY
                             operator with a split plan (tests, A/B runs); off: the library's rule alone (split_time_major below)
+    split_order=auto|on|off   split-fp16 hop, square operators: deal the rows to tiles as compact blobs of the graph (native
+                            ``sgp_split_plan_order``) where that takes strictly fewer tiles than the given order (auto), always, or never
     mix_thr=4               a column goes through the dense 16x16x4 part when >= thr of a block's 4 groups use it
     mix_min_share=0.25      least share of (group, column) pairs in the dense part for the mixed kernel to be chosen
     colblock=1|0            column-blocked hop for graphs without locality (0: generic CSR kernel)
