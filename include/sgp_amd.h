@@ -1264,6 +1264,35 @@ int sgp_edge_gather_f32(const int32_t* order, int64_t n_items, const void* other
 int sgp_edge_chunk_tables(const int32_t* ptr, int64_t n_nodes, int32_t chunk, int32_t* scan, int32_t* counts,
                           int32_t* chunks, int64_t max_chunks, int32_t* fix, int64_t max_fix, sgp_stream_t stream);
 
+/* ------------------------------------- graph-shift operator from an edge list ---
+ * The normalised operator of SGP's spatial embedding, built on the stream from a device-resident edge list, bit for
+ * bit what sgp_amd.graph.ShiftOperator.from_edges builds on the host (shift_operator.hip).  A[i, j] is the weight of
+ * edge j -> i: row = dst, column = src; SGP_SHIFT_TRANSPOSE swaps them; SGP_SHIFT_UNDIRECTED appends the swapped list
+ * behind the original one (n_items = 2 n_edges, else n_edges).  The items are sorted stably by (row, column) with two
+ * chained sgp_edge_sort passes (by column, then by row through the first order); a run of equal (row, column) becomes
+ * one entry whose value is +0.0f + w_1 + w_2 + ... in list order (weight NULL: ones), added by the head of the run;
+ * the positions come from a scan of the head flags (tile counts, one scan over the tiles, a scan inside each tile).
+ * SGP_SHIFT_SET_DIAG / SGP_SHIFT_REMOVE_DIAG drop the coalesced entries with row == column; SET_DIAG (it wins) gives
+ * every row one diagonal entry of value 1 at its sorted column position.  deg[i] = the fp32 sum of row i's values in
+ * column order from +0.0f; d = 1 / deg, or 1 / sqrt(deg) with SGP_SHIFT_GCN_NORM (correctly rounded division and
+ * square root; +inf becomes 0, NaN stays); val = d[row] * val, then * d[column] with GCN_NORM, in that order.
+ *
+ * Outputs: rowptr[n_nodes + 1], col / val of `capacity` >= n_items + (SET_DIAG ? n_nodes : 0) entries, of which the
+ * first rowptr[n_nodes] are written, *nnz = rowptr[n_nodes], and *err = 1 (the caller cleared it) for an endpoint
+ * outside [0, n_nodes): such an edge is dropped before it indexes anything and nothing is written outside the buffers.
+ * ws: sgp_shift_operator_workspace_bytes(n_items, n_nodes) bytes.  No host read, no workgroup waits for another.
+ *   replaces to_undirected / SparseTensor(...).set_diag / remove_diag / the degree normalisation of preprocess_adj
+ *   (lib/sgp_preprocessing.py:67-105) and of sgp_spatial_embedding (:177-192, :205-216) */
+#define SGP_SHIFT_GCN_NORM    1
+#define SGP_SHIFT_SET_DIAG    2
+#define SGP_SHIFT_REMOVE_DIAG 4
+#define SGP_SHIFT_UNDIRECTED  8
+#define SGP_SHIFT_TRANSPOSE   16
+int64_t sgp_shift_operator_workspace_bytes(int64_t n_items, int64_t n_nodes);
+int sgp_shift_operator_f32(const void* src, const void* dst, int32_t idx64, const float* weight, int64_t n_edges,
+                           int64_t n_nodes, int32_t flags, int32_t* rowptr, int32_t* col, float* val, int64_t capacity,
+                           int32_t* nnz, int32_t* err, void* ws, int64_t ws_bytes, sgp_stream_t stream);
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

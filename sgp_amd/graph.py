@@ -9,8 +9,13 @@ the diagonal by ones, ``remove_diag`` drops it; rows are normalised by their
 weighted in-degree (``D^-1 A``, zero-degree rows stay zero) or symmetrically
 (``D^-1/2 A D^-1/2``) when ``gcn_norm``.
 
-All of this is one-off work per graph (E <= a few 10^7) and runs on the host
-with torch CPU ops; only the resulting arrays travel to the GPU.
+For a graph that stays -- the encoders, ``preprocess_adj``, every CPU or numpy edge
+list -- this is one-off work (E <= a few 10^7) and runs on the host with torch CPU
+ops; only the resulting arrays travel to the GPU, and the hop plans are built from
+the host CSR.  A device-resident edge list that changes per training step (the online
+model on sampled subgraphs) is built on the device instead, to the same arrays bit
+for bit: ``sgp_amd.devgraph.DeviceShiftOperator``.  This module stays
+the specification of that build.
 """
 from typing import NamedTuple
 

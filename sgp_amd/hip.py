@@ -1087,6 +1087,46 @@ def edge_chunk_tables(ptr, n, chunk, scan, counts, chunks, fix):
            "sgp_edge_chunk_tables")
 
 
+# ---------------------------------------------------------------- graph-shift operator (shift_operator.hip)
+SHIFT_FLAGS = {k[len("SGP_SHIFT_"):].lower(): v for k, v in _DEFINES.items() if k.startswith("SGP_SHIFT_")}
+
+
+def shift_operator_workspace_bytes(n_items, n):
+    """Workspace of :func:`shift_operator` for ``n_items`` sorted items (edges, twice that when undirected)."""
+    need = load().sgp_shift_operator_workspace_bytes(int(n_items), int(n))
+    if need < 0:
+        raise ValueError(f"shift_operator: n_items={n_items}, n={n} outside [0, 2^31)")
+    return need
+
+
+@_on_device
+def shift_operator(src, dst, weight, n, flags, rowptr, col, val, nnz, err, ws):
+    """The normalised graph-shift operator of the edges ``src -> dst`` (int32 / int64 of one dtype; ``weight`` float32
+    or ``None``: ones) in CSR, as ``graph.ShiftOperator.from_edges`` builds it: ``flags`` is a set of ``SHIFT_FLAGS``
+    names.  Writes ``rowptr`` (int32 [n + 1]), the first ``rowptr[n]`` entries of ``col`` (int32) / ``val`` (float32),
+    whose capacity is ``items + (n if "set_diag" in flags else 0)`` (at least 1), ``nnz`` and, for an endpoint outside
+    ``[0, n)``, ``err`` (1-element int32 views; the caller cleared ``err``).  Reads nothing back."""
+    lib = require_gpu()
+    unknown = set(flags) - set(SHIFT_FLAGS)
+    if unknown:
+        raise ValueError(f"shift_operator: unknown flags {sorted(unknown)}")
+    if src.dtype != dst.dtype:
+        raise ValueError("shift_operator: src and dst must have one dtype")
+    E = src.numel()
+    sp, s64 = _ids(src, "src", E)
+    dp, _ = _ids(dst, "dst", E)
+    need = shift_operator_workspace_bytes(E * (2 if "undirected" in flags else 1), n)
+    if col.numel() != val.numel():
+        raise ValueError("shift_operator: col and val differ in size")
+    _check(lib.sgp_shift_operator_f32(sp, dp, s64, _opt(weight, "weight", torch.float32, E), E, int(n),
+                                      sum(SHIFT_FLAGS[f] for f in set(flags)), _flat(rowptr, "rowptr", torch.int32, n + 1),
+                                      _flat(col, "col", torch.int32, 1), _flat(val, "val", torch.float32, 1), col.numel(),
+                                      _flat(nnz, "nnz", torch.int32, 1), _flat(err, "err", torch.int32, 1),
+                                      _flat(ws, "ws", torch.uint8, need), ws.numel(), _stream(src)),
+           "sgp_shift_operator_f32")
+    return rowptr, col, val
+
+
 GL_ACT_CODES = {None: 0, "linear": 0, "identity": 0, "relu": 1, "silu": 2}
 
 

@@ -2,6 +2,7 @@ import torch
 from torch import nn
 
 from ... import hip
+from ...devgraph import DeviceShiftOperator
 from ...sgp_preprocessing import propagate_into, spatial_operators
 from ._args import add_spatial_args
 
@@ -28,10 +29,13 @@ class SGPSpatialEncoder(nn.Module):
         return 1 + dirs * self.receptive_field + (1 if self.global_attr else 0)
 
     def operators(self, num_nodes, edge_index, edge_weight):
-        return spatial_operators(edge_index, edge_weight, num_nodes,
-                                 undirected=self.undirected,
-                                 add_self_loops=self.add_self_loops,
-                                 bidirectional=self.bidirectional)
+        ops = spatial_operators(edge_index, edge_weight, num_nodes,
+                                undirected=self.undirected,
+                                add_self_loops=self.add_self_loops,
+                                bidirectional=self.bidirectional)
+        # the encoders run many hops on a graph that stays: they want the planned hop kernels, i.e. the host operator
+        # (a CUDA edge list is built on its device; the arrays are the host build's, bit for bit)
+        return [op.to_host() if isinstance(op, DeviceShiftOperator) else op for op in ops]
 
     def encode_into(self, out, feat, ops, timeline=None, col_sums=None, x_bound=None):
         """Device path.  ``out[B, N, P * feat]`` with slot 0 already filled: run the hops

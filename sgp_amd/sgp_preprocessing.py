@@ -8,6 +8,7 @@ import torch
 from torch import Tensor
 
 from . import hip
+from .devgraph import DeviceShiftOperator
 from .graph import ShiftOperator
 from .nn.reservoir import Reservoir
 
@@ -48,9 +49,15 @@ def preprocess_adj(edge_index, edge_weight=None, num_nodes: Optional[int] = None
                        "or SparseTensor.")
 
 
+def _is_device_list(edge_index):
+    return torch.is_tensor(edge_index) and edge_index.is_cuda
+
+
 def spatial_operators(edge_index, edge_weight, num_nodes, undirected=False,
-                      add_self_loops=False, remove_self_loops=False, bidirectional=False):
-    """Forward (and backward) operators of sgp_spatial_embedding (:182-192, :205-216)."""
+                      add_self_loops=False, remove_self_loops=False, bidirectional=False, check=True):
+    """Forward (and backward) operators of sgp_spatial_embedding (:182-192, :205-216).  A CUDA ``edge_index`` (a
+    sampler's batch) gets :class:`~sgp_amd.devgraph.DeviceShiftOperator`s, built on its device without a copy of the
+    list to the host (``check=False``: without any host read); everything else ``ShiftOperator``s built on the host."""
     if undirected:
         assert bidirectional is False
     if _is_sparse_like(edge_index):
@@ -60,13 +67,17 @@ def spatial_operators(edge_index, edge_weight, num_nodes, undirected=False,
     if not isinstance(edge_index, (np.ndarray, Tensor)):
         raise RuntimeError("Edge index must be (edge_index, edge_weight) tuple "
                            "or SparseTensor.")
-    ops = [ShiftOperator.from_edges(edge_index, edge_weight, num_nodes, gcn_norm=undirected,
-                                    set_diag=add_self_loops, remove_diag=remove_self_loops,
-                                    undirected=undirected)]
+    if _is_device_list(edge_index):
+        build, extra = DeviceShiftOperator.from_edges, dict(check=check)
+    else:
+        build, extra = ShiftOperator.from_edges, {}
+    ops = [build(edge_index, edge_weight, num_nodes, gcn_norm=undirected,
+                 set_diag=add_self_loops, remove_diag=remove_self_loops,
+                 undirected=undirected, **extra)]
     if bidirectional:
-        ops.append(ShiftOperator.from_edges(edge_index, edge_weight, num_nodes, gcn_norm=False,
-                                            set_diag=add_self_loops,
-                                            remove_diag=remove_self_loops, transpose=True))
+        ops.append(build(edge_index, edge_weight, num_nodes, gcn_norm=False,
+                         set_diag=add_self_loops,
+                         remove_diag=remove_self_loops, transpose=True, **extra))
     return ops
 
 
