@@ -1293,6 +1293,51 @@ int sgp_shift_operator_f32(const void* src, const void* dst, int32_t idx64, cons
                            int64_t n_nodes, int32_t flags, int32_t* rowptr, int32_t* col, float* val, int64_t capacity,
                            int32_t* nnz, int32_t* err, void* ws, int64_t ws_bytes, sgp_stream_t stream);
 
+/* ------------------------------------- product and row subset of CSR operators ---
+ * The explicit supports of SGP's on-the-fly path for operators that live on the device (spgemm.hip).  An operand is
+ * CSR as sgp_shift_operator_f32 leaves it: rowptr int32 [rows + 1], col int32 / val fp32 of `capacity` >= 1 entries of
+ * which the first rowptr[rows] count, columns ascending and unique within a row.
+ *
+ * sgp_spgemm_f32: C = A B for A [n_rows, n_mid] and B [n_mid, n_cols] (A and B may be the same arrays), bit for bit
+ *   scipy's fp32 product with sorted indices: C[i, j] = +0.0f + a[i, k1] b[k1, j] + a[i, k2] b[k2, j] + ... in
+ *   ascending k, one fp32 multiply and one fp32 add per term (no fused multiply-add); columns ascending within a row;
+ *   an entry whose sum compares equal to zero (either sign) is absent, NaN stays.  One wave per output row keeps a
+ *   band of sgp_spgemm_form's width of columns as fp32 sums and touched flags in LDS, walks row i of A in order with
+ *   the lanes striding over the rows of B, and scans the flags; columns beyond the band follow in further bands (only
+ *   bands that hold an entry are walked).  A hub row is slow and correct.
+ *   phase: SGP_SPGEMM_COUNT counts the entries of every row into ws, SGP_SPGEMM_EMIT scans the counts (one workgroup,
+ *   64-bit sums) into rowptr and writes col / val; both bits: one call.  COUNT alone also scans (against a capacity of
+ *   2^31 - 1) and so leaves the exact size in *nnz for a caller that allocates between the two phases; EMIT alone
+ *   needs the ws of a COUNT call on the same operands.
+ *     replaces the scipy SpGEMM of sgp_spatial_support (lib/sgp_preprocessing.py:143-145)
+ * sgp_csr_take_rows_f32: row t of the result is row index[t] of A (index int32 / int64 by idx64, unsorted, repeats
+ *   allowed), n_index rows, A's columns: row lengths, the same scan, a copy by one wave per row.  Same phases.
+ *     replaces adj.index_select(0, node_index) (lib/datasets/iid_dataset.py:111-114; the product at
+ *     lib/sgp_preprocessing.py:143-145 is applied to these rows)
+ * Outputs of both: rowptr [rows + 1], the first rowptr[rows] entries of col / val, *nnz = rowptr[rows], and *err (the
+ * caller cleared it; bits are OR-ed in).  SGP_SPGEMM_ERR_CAPACITY: the result has more than `capacity` (or 2^31 - 1)
+ * entries; rowptr is then clamped to the capacity -- monotone, the rows that fit are complete, the rest cut short.
+ * SGP_SPGEMM_ERR_INDEX: a rowptr entry of an operand outside [0, capacity] or decreasing, a column of A outside
+ * [0, n_mid), a column of B outside [0, n_cols), an index outside [0, n_rows): compared unsigned before it indexes
+ * anything, then skipped (an empty row).  Nothing is written outside the buffers.  ws: sgp_spgemm_workspace_bytes(rows
+ * of the result) bytes.  No host read, no workgroup waits for another.
+ * sgp_spgemm_form (host only): out[0] = the band width, out[1] = the bands that cover n_cols, out[2] = the regime:
+ *   0 nothing to do, 1 one band, 2 banded; out[3] = workgroups (one wave each). */
+#define SGP_SPGEMM_COUNT 1
+#define SGP_SPGEMM_EMIT  2
+#define SGP_SPGEMM_ERR_CAPACITY 1
+#define SGP_SPGEMM_ERR_INDEX    2
+int64_t sgp_spgemm_workspace_bytes(int64_t n_rows);
+int sgp_spgemm_form(int64_t n_rows, int64_t n_cols, int64_t* out);
+int sgp_spgemm_f32(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val, int64_t a_capacity, int64_t n_rows,
+                   int64_t n_mid, const int32_t* b_rowptr, const int32_t* b_col, const float* b_val, int64_t b_capacity,
+                   int64_t n_cols, int32_t phase, int32_t* rowptr, int32_t* col, float* val, int64_t capacity,
+                   int32_t* nnz, int32_t* err, void* ws, int64_t ws_bytes, sgp_stream_t stream);
+int sgp_csr_take_rows_f32(const int32_t* a_rowptr, const int32_t* a_col, const float* a_val, int64_t a_capacity,
+                          int64_t n_rows, const void* index, int32_t idx64, int64_t n_index, int32_t phase,
+                          int32_t* rowptr, int32_t* col, float* val, int64_t capacity, int32_t* nnz, int32_t* err, void* ws,
+                          int64_t ws_bytes, sgp_stream_t stream);
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

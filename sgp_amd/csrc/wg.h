@@ -34,6 +34,27 @@ __device__ __forceinline__ V wave_sum(V v) {
     return v;
 }
 
+// xor butterflies over the 64 lanes: EVERY lane holds the minimum / maximum
+template <class V>
+__device__ __forceinline__ V wave_min(V v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const V o = __shfl_xor(v, off, 64); v = o < v ? o : v; }
+    return v;
+}
+template <class V>
+__device__ __forceinline__ V wave_max(V v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const V o = __shfl_xor(v, off, 64); v = o > v ? o : v; }
+    return v;
+}
+
+// the flag scan of one wave: the number of lanes below this one whose flag is set; total = all of them (every lane)
+__device__ __forceinline__ int wave_rank(bool flag, int& total) {
+    const unsigned long long m = __ballot(flag);
+    total = __popcll(m);
+    return __popcll(m & ((1ull << (threadIdx.x & 63)) - 1ull));
+}
+
 // ---------------------------------------------------------------------------------------------------- reductions
 // Halving tree over T slots of LDS that the caller has filled (slot = thread): fold(a, b) folds slot b into slot a,
 // for as many quantities and element-wise operations (sum, min, max, or) as the caller keeps per slot.  Slot 0 holds

@@ -19,16 +19,20 @@ The DataLoader / Batch plumbing around these lines is tsl's and is not rebuilt h
 import torch
 
 from .. import hip
+from ..devgraph import DeviceShiftOperator
 from ..graph import ShiftOperator
 
 
 def _rect_dense(a, x3, dst):
-    """Rows of a dense support selected by ``node_index``: CSR of the [rows, N] block."""
+    """Rows of a dense support selected by ``node_index``: CSR of the [rows, N] block, built where ``a`` lives."""
     r, c = a.nonzero(as_tuple=True)
     counts = torch.bincount(r, minlength=a.shape[0])
-    rowptr = torch.zeros(a.shape[0] + 1, dtype=torch.long)
+    rowptr = torch.zeros(a.shape[0] + 1, dtype=torch.long, device=a.device)
     rowptr[1:] = torch.cumsum(counts, 0)
-    ShiftOperator(rowptr, c, a[r, c], a.shape[0], num_cols=a.shape[1]).propagate_rect(x3, dst)
+    if a.is_cuda and a.device == x3.device:
+        hip.spmm_csr(rowptr.to(torch.int32), c.to(torch.int32), a[r, c].contiguous(), x3, dst)
+    else:
+        ShiftOperator(rowptr.cpu(), c.cpu(), a[r, c].cpu(), a.shape[0], num_cols=a.shape[1]).propagate_rect(x3, dst)
 
 
 _CONSTANT_CACHE = {}          # id(adj) -> (weakref to adj, adj._version, value); a handful of entries at most
@@ -45,12 +49,13 @@ def _constant_value(adj):
     hit = _CONSTANT_CACHE.get(key)
     if hit is not None and hit[0]() is adj and hit[1] == version:
         return hit[2]
-    a = torch.as_tensor(adj)
+    a = torch.as_tensor(adj)                             # compared where it lives: a device matrix is not copied down
     value = None
     if a.numel():
         c = a.flatten()[0]
-        if bool((a == c).all()):
-            value = float(c)
+        ok = torch.stack([(a == c).all().to(c.dtype), c]).tolist()      # ONE host read: (all equal, the value)
+        if ok[0]:
+            value = float(ok[1])
     for k in [k for k, v in _CONSTANT_CACHE.items() if v[0]() is None]:      # entries whose tensor is gone
         del _CONSTANT_CACHE[k]
     if len(_CONSTANT_CACHE) >= 8:
@@ -62,19 +67,24 @@ def _constant_value(adj):
     return value
 
 
-def apply_supports(x, support, node_index=None):
-    """x[..., N, F] -> [..., N (or len(node_index)), (1 + len(support)) * F]."""
+def apply_supports(x, support, node_index=None, check=True):
+    """x[..., N, F] -> [..., N (or len(node_index)), (1 + len(support)) * F].  The supports are ``ShiftOperator``s,
+    dense matrices, or the :class:`~sgp_amd.devgraph.DeviceShiftOperator`s of a device-resident list:
+    those run on their own device (an ``x`` already there is not copied) and take their ``node_index`` rows with
+    ``take_rows(node_index, check=check)``."""
     hip.require_gpu()
     dev_in = x.device
     xg = x.float()
     if not xg.is_cuda:
-        xg = xg.cuda()
+        on = next((a.rowptr.device for a in support if isinstance(a, DeviceShiftOperator)), None)
+        xg = xg.cuda() if on is None else xg.to(on)
     lead = xg.shape[:-2]
     n, f = xg.shape[-2:]
     x3 = xg.reshape(-1, n, f)
     if x3.stride(2) != 1:
         x3 = x3.contiguous()
-    idx = None if node_index is None else torch.as_tensor(node_index, dtype=torch.long)
+    idx = None if node_index is None else (node_index.long() if torch.is_tensor(node_index)
+                                           else torch.as_tensor(node_index, dtype=torch.long))
     rows = n if idx is None else idx.numel()
     out = torch.empty(x3.shape[0], rows, (1 + len(support)) * f, dtype=torch.float32, device=xg.device)
     if idx is None:
@@ -83,7 +93,9 @@ def apply_supports(x, support, node_index=None):
         hip.gather_nodes(x3, idx.to(xg.device, torch.int32), out[:, :, :f])
     for s, adj in enumerate(support, start=1):
         dst = out[:, :, s * f:(s + 1) * f]
-        if isinstance(adj, ShiftOperator):
+        if isinstance(adj, DeviceShiftOperator):
+            (adj if idx is None else adj.take_rows(idx, check=check)).propagate(x3, dst)
+        elif isinstance(adj, ShiftOperator):
             op = adj if idx is None else adj.index_select(0, idx)
             op.propagate_rect(x3, dst)
         else:
@@ -95,7 +107,7 @@ def apply_supports(x, support, node_index=None):
             if const is not None:
                 hip.bcast_rows(hip.node_sums(x3), const, dst)
             else:
-                a = torch.as_tensor(adj, dtype=torch.float32).cpu()
-                _rect_dense(a if idx is None else a[idx.cpu()], x3, dst)
+                a = torch.as_tensor(adj, dtype=torch.float32)
+                _rect_dense(a if idx is None else a[idx.to(a.device)], x3, dst)
     out = out.reshape(*lead, rows, out.shape[-1])
     return out if dev_in == out.device else out.to(dev_in)

@@ -10,6 +10,10 @@ The operator keeps its arrays on the device and runs every hop with the exact-fp
 (``hip.spmm_csr``): the planned hop kernels need host-side plans, which pay for a graph that stays, not for one that
 lives for a single step.  ``to_host()`` hands out a ``ShiftOperator`` for callers that want them.  There is no CPU
 fallback.
+
+Operators from operators (kernels in ``csrc/spgemm.hip``): ``matmul`` is the CSR-times-CSR product of
+``sgp_spatial_support`` (``A_hat @ A_hat``), bit for bit scipy's, and ``take_rows`` the rectangular row subset that the
+on-the-fly loaders apply to a node sample.
 """
 import torch
 
@@ -76,10 +80,11 @@ class DeviceShiftOperator:
 
     next_bound = None           # (the split-fp16 hop's bound bookkeeping: this operator's hops are exact fp32)
 
-    def __init__(self, rowptr, col, val, nnz, err, num_nodes):
+    def __init__(self, rowptr, col, val, nnz, err, num_nodes, num_cols=None):
         self.rowptr, self.col, self.val = rowptr, col, val
         self._nnz, self._err = nnz, err
-        self.num_nodes = self.num_cols = int(num_nodes)
+        self.num_nodes = int(num_nodes)
+        self.num_cols = self.num_nodes if num_cols is None else int(num_cols)      # (take_rows: a rectangular operator)
 
     # ---- construction -----------------------------------------------------
     @classmethod
@@ -113,6 +118,84 @@ class DeviceShiftOperator:
             raise ValueError("edge_index out of range for num_nodes")
         return cls(rowptr, col, val, words[:1], words[1:], n)
 
+    # ---- operators from operators (kernels in csrc/spgemm.hip) ----
+    def _derived(self, rows, cols, capacity, check, workspace, run, overflow, bad_index):
+        """The two-phase build shared by ``matmul`` and ``take_rows``: ``run(phase, rowptr, col, val, nnz, err, ws)``."""
+        if capacity is not None and (int(capacity) != capacity or capacity < 0 or capacity > MAX_ITEMS):
+            raise ValueError(f"capacity={capacity} outside [0, 2^31 - 1]")
+        hip.require_gpu()
+        dev = self.rowptr.device
+        ws = (workspace or _default).buffer(dev, hip.spgemm_workspace_bytes(rows))
+        rowptr = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+        words = torch.zeros(2, dtype=torch.int32, device=dev)         # nnz, error bits
+        phase = None
+        if capacity is None:
+            run(hip.SPGEMM_COUNT, rowptr, None, None, words[:1], words[1:], ws, None)
+            capacity, phase = int(words[0].item()), hip.SPGEMM_EMIT   # the one host read of the exact build
+        col = torch.empty(max(int(capacity), 1), dtype=torch.int32, device=dev)
+        val = torch.empty(max(int(capacity), 1), dtype=torch.float32, device=dev)
+        run(phase, rowptr, col, val, words[:1], words[1:], ws, int(capacity))
+        if check:
+            bits = int(words[1].item())                               # the one host read of the check
+            if bits & hip.SPGEMM_ERR_INDEX:
+                raise bad_index
+            if bits & hip.SPGEMM_ERR_CAPACITY:
+                raise overflow
+        return DeviceShiftOperator(rowptr, col, val, words[:1], words[1:], rows, cols)
+
+    def matmul(self, other, capacity=None, check=True, workspace=None):
+        """``self @ other`` for another :class:`DeviceShiftOperator` on the same device, built there on the current
+        stream: scipy's fp32 product of the two CSR operators with sorted indices, bit for bit, exact zeros dropped
+        (``A_hat @ A_hat`` of ``sgp_spatial_support``).  ``other`` may be ``self``.
+
+        ``capacity=None`` allocates exactly: ONE host read of the count (a synchronisation) between the counting and
+        the emitting pass.  With an integer ``capacity`` nothing is read back for the build; a product that does not
+        fit sets the error word, and the rows that fit are complete.  ``check=True`` reads the error word (one more
+        host read) and raises ``ValueError`` for the overflow or for an operand whose positions are out of range;
+        ``check=False`` reads nothing."""
+        if not isinstance(other, DeviceShiftOperator):
+            raise TypeError("matmul expects a DeviceShiftOperator (a dense tensor: op @ x)")
+        if self.num_cols != other.num_nodes:
+            raise ValueError(f"operands do not chain: {self.num_nodes} x {self.num_cols} times "
+                             f"{other.num_nodes} x {other.num_cols}")
+        if self.rowptr.device != other.rowptr.device:
+            raise ValueError(f"operands on different devices: {self.rowptr.device} and {other.rowptr.device}")
+        a, b = (self.rowptr, self.col, self.val), (other.rowptr, other.col, other.val)
+        shapes = (self.num_nodes, self.num_cols), (other.num_nodes, other.num_cols)
+
+        def run(phase, rowptr, col, val, nnz, err, ws, cap):
+            hip.spgemm(a, shapes[0], b, shapes[1], rowptr, col, val, nnz, err, ws, phase=phase, capacity=cap)
+        return self._derived(self.num_nodes, other.num_cols, capacity, check, workspace, run,
+                             ValueError(f"the product has more entries than its capacity ({capacity}): overflow"),
+                             ValueError("an operand of the product holds a position out of range"))
+
+    def take_rows(self, index, check=True, capacity=None, workspace=None):
+        """The rows ``index`` of the operator (int32 / int64 tensor on any device, or a list; unsorted, repeats
+        allowed) as a rectangular device operator: ``num_nodes = len(index)``, ``num_cols`` unchanged -- the
+        ``adj.index_select(0, node_index)`` of the reference's IID dataset.  Its ``propagate`` runs the generic CSR
+        kernel.  An index outside ``[0, num_nodes)`` selects an empty row and sets the error word; ``check=True``
+        reads that word (one host read) and raises ``IndexError``.  ``capacity`` as in :meth:`matmul`: ``None`` costs
+        ONE host read of the count; an integer and ``check=False`` read nothing back (the operator's own capacity is
+        enough for any index without repeats)."""
+        dev = self.rowptr.device
+        idx = index if torch.is_tensor(index) else torch.as_tensor(index)
+        if not torch.is_tensor(index) and idx.numel() == 0:           # (an empty list has no dtype of its own)
+            idx = idx.to(torch.int64)
+        if idx.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"take_rows: expected an int32 or int64 index, got {idx.dtype}")
+        if idx.dim() != 1:
+            raise ValueError(f"take_rows: expected a 1-D index, got {tuple(idx.shape)}")
+        if idx.numel() >= MAX_ITEMS:
+            raise ValueError("take_rows: index too long")
+        idx = idx.to(dev).contiguous()
+        a = (self.rowptr, self.col, self.val)
+
+        def run(phase, rowptr, col, val, nnz, err, ws, cap):
+            hip.csr_take_rows(a, self.num_nodes, idx, rowptr, col, val, nnz, err, ws, phase=phase, capacity=cap)
+        return self._derived(idx.numel(), self.num_cols, capacity, check, workspace, run,
+                             ValueError(f"the selected rows hold more entries than the capacity ({capacity}): overflow"),
+                             IndexError(f"take_rows: index out of range for {self.num_nodes} rows"))
+
     # ---- duck-typed accessors (graph.ShiftOperator-like) --------------------
     def size(self, dim):
         return self.num_nodes if dim == 0 else self.num_cols
@@ -141,7 +224,7 @@ class DeviceShiftOperator:
         rowptr = flat[:n + 1]
         nnz = min(max(int(rowptr[n]), 0), cap)
         return ShiftOperator(rowptr.clone(), flat[n + 1:n + 1 + nnz].clone(),
-                             flat[n + 1 + cap:n + 1 + cap + nnz].view(torch.float32).clone(), n)
+                             flat[n + 1 + cap:n + 1 + cap + nnz].view(torch.float32).clone(), n, num_cols=self.num_cols)
 
     # ---- hops ----------------------------------------------------------------
     def propagate(self, x, y, x_bound=None, force=None, halo=None, **kw):
@@ -175,6 +258,8 @@ class DeviceShiftOperator:
         raise NotImplementedError("a DeviceShiftOperator is square: use propagate(x, y), or to_host().propagate_rect(x, y)")
 
     def __matmul__(self, x):
+        if isinstance(x, DeviceShiftOperator):
+            return self.matmul(x)
         if not torch.is_tensor(x) or x.dim() < 2:
             raise TypeError("DeviceShiftOperator @ expects a dense tensor [..., N, F]")
         lead = x.shape[:-2]

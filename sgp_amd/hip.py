@@ -1127,6 +1127,86 @@ def shift_operator(src, dst, weight, n, flags, rowptr, col, val, nnz, err, ws):
     return rowptr, col, val
 
 
+# ---------------------------------------------------------------- operator product and row subset (spgemm.hip)
+SPGEMM_COUNT, SPGEMM_EMIT = _DEFINES["SGP_SPGEMM_COUNT"], _DEFINES["SGP_SPGEMM_EMIT"]
+SPGEMM_ERR_CAPACITY, SPGEMM_ERR_INDEX = _DEFINES["SGP_SPGEMM_ERR_CAPACITY"], _DEFINES["SGP_SPGEMM_ERR_INDEX"]
+_SPGEMM_REGIMES = ("empty", "one_band", "banded")
+
+
+def spgemm_workspace_bytes(n_rows):
+    """Workspace of :func:`spgemm` / :func:`csr_take_rows` for a result of ``n_rows`` rows."""
+    need = load().sgp_spgemm_workspace_bytes(int(n_rows))
+    if need < 0:
+        raise ValueError(f"spgemm: n_rows={n_rows} outside [0, 2^31 - 1)")
+    return need
+
+
+def spgemm_form(n_rows, n_cols=None):
+    """The launch of :func:`spgemm` for a result ``[n_rows, n_cols]`` (``n_cols`` None: square), as a dict (host only:
+    ``sgp_spgemm_form``): ``band`` (columns a wave keeps in LDS at a time), ``bands`` (that cover ``n_cols``),
+    ``regime`` ("empty", "one_band", "banded") and ``grid`` (workgroups of one wave)."""
+    out = (c_i64 * 4)()
+    rc = load().sgp_spgemm_form(int(n_rows), int(n_rows if n_cols is None else n_cols), ctypes.addressof(out))
+    if rc == SGP_EINVAL:
+        raise ValueError(f"spgemm_form: {load().sgp_last_error().decode()}")
+    _check(rc, "sgp_spgemm_form")
+    return dict(band=int(out[0]), bands=int(out[1]), regime=_SPGEMM_REGIMES[int(out[2])], grid=int(out[3]))
+
+
+def _csr_out(phase, n_rows, rowptr, col, val, capacity, nnz, err, ws):
+    emit = bool(phase & SPGEMM_EMIT)
+    if emit:
+        capacity = col.numel() if capacity is None else int(capacity)
+        if capacity < 0:
+            raise ValueError(f"capacity={capacity} is negative")
+    need = spgemm_workspace_bytes(n_rows)
+    return (_flat(rowptr, "rowptr", torch.int32, n_rows + 1), _flat(col, "col", torch.int32, max(capacity, 1)) if emit else None,
+            _flat(val, "val", torch.float32, max(capacity, 1)) if emit else None, capacity if emit else 0,
+            _flat(nnz, "nnz", torch.int32, 1), _flat(err, "err", torch.int32, 1), _flat(ws, "ws", torch.uint8, need),
+            ws.numel())
+
+
+def _csr_in(rowptr, col, val, n_rows, name):
+    if col.numel() != val.numel():
+        raise ValueError(f"{name}: col and val differ in size")
+    return (_flat(rowptr, f"{name}.rowptr", torch.int32, n_rows + 1), _flat(col, f"{name}.col", torch.int32, 1),
+            _flat(val, f"{name}.val", torch.float32, 1), col.numel())
+
+
+@_on_device
+def spgemm(a, a_shape, b, b_shape, rowptr, col, val, nnz, err, ws, phase=None, capacity=None):
+    """``C = A @ B`` for CSR operands ``(rowptr, col, val)`` of shapes ``a_shape = (n, m)`` and ``b_shape = (m, p)`` as
+    :func:`shift_operator` leaves them, bit for bit scipy's fp32 product with sorted indices and the exact zeros
+    dropped.  Writes ``rowptr`` (int32 [n + 1]), the first ``rowptr[n]`` entries of ``col`` / ``val`` (``capacity``, or
+    their size: never empty tensors), ``nnz`` and ``err`` (1-element int32 views; the caller cleared ``err``; ``SPGEMM_ERR_*`` bits).
+    ``phase``: ``SPGEMM_COUNT`` (``col`` / ``val`` may be None; leaves the exact size in ``nnz``), ``SPGEMM_EMIT``
+    (after a count on the same operands and ``ws``), or None: both.  Reads nothing back."""
+    lib = require_gpu()
+    phase = SPGEMM_COUNT | SPGEMM_EMIT if phase is None else int(phase)
+    (n, m), (m2, p) = (int(v) for v in a_shape), (int(v) for v in b_shape)
+    if m != m2:
+        raise ValueError(f"spgemm: A has {m} columns, B {m2} rows")
+    _check(lib.sgp_spgemm_f32(*_csr_in(*a, n, "A"), n, m, *_csr_in(*b, m, "B"), p, phase,
+                              *_csr_out(phase, n, rowptr, col, val, capacity, nnz, err, ws), _stream(rowptr)),
+           "sgp_spgemm_f32")
+    return rowptr, col, val
+
+
+@_on_device
+def csr_take_rows(a, n_rows, index, rowptr, col, val, nnz, err, ws, phase=None, capacity=None):
+    """Row ``t`` of the result = row ``index[t]`` of the CSR operand ``a`` (int32 / int64 CUDA ``index``, unsorted,
+    repeats allowed); outputs, ``phase`` and error bits as :func:`spgemm` (an index outside ``[0, n_rows)`` gives an
+    empty row and ``SPGEMM_ERR_INDEX``)."""
+    lib = require_gpu()
+    phase = SPGEMM_COUNT | SPGEMM_EMIT if phase is None else int(phase)
+    k = index.numel()
+    ip, i64 = (None, 0) if k == 0 else _ids(index, "index")
+    _check(lib.sgp_csr_take_rows_f32(*_csr_in(*a, int(n_rows), "A"), int(n_rows), ip, i64, k, phase,
+                                     *_csr_out(phase, k, rowptr, col, val, capacity, nnz, err, ws), _stream(rowptr)),
+           "sgp_csr_take_rows_f32")
+    return rowptr, col, val
+
+
 GL_ACT_CODES = {None: 0, "linear": 0, "identity": 0, "relu": 1, "silu": 2}
 
 

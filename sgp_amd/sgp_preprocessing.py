@@ -183,16 +183,43 @@ def _operator_from_scipy(m):
                          torch.from_numpy(m.data.astype(np.float32)), m.shape[0])
 
 
+def _device_spatial_support(edge_index, edge_weight, num_nodes, k, undirected, add_self_loops, remove_self_loops,
+                            bidirectional, global_attr, check):
+    """``sgp_spatial_support`` for a device-resident list: the operators are built and squared on the
+    list's device.  ``A_hat @ A_hat`` is ONE product and the same object k - 1 times; the ``bidirectional`` supports
+    are the row-normalised forward operator again, which without ``undirected`` is the first operator itself."""
+    def supports(gcn_norm):
+        a0 = DeviceShiftOperator.from_edges(edge_index, edge_weight, num_nodes, gcn_norm=gcn_norm, undirected=undirected,
+                                            set_diag=add_self_loops, remove_diag=remove_self_loops, check=check)
+        return [a0] + ([a0.matmul(a0, check=check)] * (k - 1) if k > 1 else [])
+    support = supports(undirected)
+    if bidirectional:
+        support += supports(False) if undirected else list(support)
+    if global_attr:
+        n = int(num_nodes)
+        support.append(torch.full((n, n), 1.0 / n, device=edge_index.device))
+    return support
+
+
 def sgp_spatial_support(edge_index, edge_weight=None, num_nodes=None, k=2, undirected=False,
                         add_self_loops=False, remove_self_loops=False, bidirectional=False,
-                        global_attr=False):
+                        global_attr=False, check=True):
     """lib/sgp_preprocessing.py:108-160: explicit sparse supports for on-the-fly propagation
-    (``sgp_preprocessing: True``).  One-off graph preparation, done on the host with scipy
-    (SpSpGEMM); every support is a :class:`ShiftOperator` whose ``@`` runs on the GPU.  The
+    (``sgp_preprocessing: True``).  For CPU, numpy, scipy and sparse-like inputs this is one-off
+    graph preparation, done on the host with scipy (SpSpGEMM); every support is a
+    :class:`ShiftOperator` whose ``@`` runs on the GPU.  A CUDA ``edge_index`` (a sampler's batch;
+    ``num_nodes`` is then required) gets :class:`~sgp_amd.devgraph.DeviceShiftOperator`s built and
+    multiplied on its device, the same entries bit for bit where the host's operator is
+    (``check``: passed to the builds and the product; ``False`` reads no error word).  The
     reference's quirks are kept so that a decoder trained against them sees the same inputs:
     every support after the first is ``A_hat @ A_hat`` (:143-145), and the ``bidirectional``
     recursion is handed the un-transposed adjacency (:147-154), i.e. its supports are the
     row-normalised forward operator again.  ``global_attr`` appends a dense 1/N matrix."""
+    if _is_device_list(edge_index):
+        if num_nodes is None:
+            raise ValueError("num_nodes is required: inferring it from a device-resident edge_index needs a host read")
+        return _device_spatial_support(edge_index, edge_weight, num_nodes, k, undirected, add_self_loops,
+                                       remove_self_loops, bidirectional, global_attr, check)
     import scipy.sparse as sp
     if _is_sparse_like(edge_index):
         row, col, val = edge_index.coo()
