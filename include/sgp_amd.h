@@ -20,6 +20,8 @@
  *       output slot; the fused path writes slots in place and never concatenates.
  *   sgp_gather_rows_f32
  *       lib/datasets/iid_dataset.py:57-99 (IID (t, n) row gather of the embedding; "next" row f1)
+ *   sgp_pack_rows_16, sgp_gather_rows_16
+ *       the same embedding kept in bf16 / fp16 (no counterpart in the reference: lib/utils.py:24-35 holds float32)
  *   sgp_grouped_linear_f32
  *       lib/nn/models/sgp_model.py:41-52 (decoder input encoder: grouped Conv1d + activation; f4)
  *
@@ -630,6 +632,32 @@ int sgp_gather_rows_f32(const float* X, int64_t x_row_stride, int64_t x_batch_st
                         const int32_t* step, const int32_t* node, int32_t n_index,
                         float* out, int64_t out_row_stride, int64_t out_batch_stride,
                         int32_t batch, int32_t feat, sgp_stream_t stream);
+
+/* ------------------------------------------------- 16-bit embedding store ---
+ * embed_store.hip.  The encoders' product can be kept in 16 bits: packed after the hops have written
+ * their fp32 slots, widened again by the samplers' gather.  Strides of a 16-bit view are in 16-bit ELEMENTS.
+ *
+ * sgp_pack_rows_16: Y[b, i, 0:feat] = X[b, i, 0:feat] rounded to nearest-even in format `fmt`, bit-equal to the IEEE
+ * conversion (fp16: subnormals, underflow to signed zero, overflow to infinity; NaN stays NaN -- bf16 writes the quiet
+ * NaN 0x7FC0).  overflow_count (optional, fp16 only, device int64, 8-byte aligned) is INCREMENTED by the number of
+ * finite inputs that became infinite: summed per workgroup, at most one atomic per workgroup, exact.  It is ignored for
+ * bf16, whose exponent range is fp32's.  feat % 8 == 0 with strides that are multiples of 8 and 16-byte aligned bases
+ * takes two 16-byte loads and one 16-byte store per thread; everything else (any feat and stride, X on 4 and Y on 2
+ * bytes) the element-wise kernel.  An empty shape returns 0 without a launch.
+ *
+ * sgp_gather_rows_16: sgp_gather_rows_f32 over a 16-bit source -- out[k, 0:feat] = X[step[k], node[k], 0:feat], or with
+ * step = NULL out[b, k, :] = X[b, node[k], :]; out is fp32 and may be a slot of a wider buffer.  Widening is exact.
+ * The same two paths as the pack entry. */
+#define SGP_STORE_BF16 1
+#define SGP_STORE_F16  2
+int sgp_pack_rows_16(const float* X, int64_t x_row_stride, int64_t x_batch_stride,
+                     int32_t batch, int32_t n_rows, int32_t feat, int32_t fmt,
+                     void* Y, int64_t y_row_stride, int64_t y_batch_stride,
+                     int64_t* overflow_count, sgp_stream_t stream);
+int sgp_gather_rows_16(const void* X, int64_t x_row_stride, int64_t x_batch_stride,
+                       const int32_t* step, const int32_t* node, int32_t n_index, int32_t fmt,
+                       float* out, int64_t out_row_stride, int64_t out_batch_stride,
+                       int32_t batch, int32_t feat, sgp_stream_t stream);
 
 /* ------------------------------------------------- Decoder first layer ("next" row f4) ---
  * Grouped 1x1 convolution of lib/nn/models/sgp_model.py:41-52 (nn.Conv1d(input_size, out_channels,

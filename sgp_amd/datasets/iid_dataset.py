@@ -46,7 +46,10 @@ class IIDSampler:
             raise ValueError(f"pattern {pattern!r} needs a {want}-D tensor, got {tuple(tensor.shape)}")
         if tensor.shape[0] != self.n_steps or ("n" in dims and tensor.shape[1] != self.n_nodes):
             raise ValueError("tensor does not match n_steps / n_nodes")
-        t = tensor.to(self.device, torch.float32)
+        # a bfloat16 / float16 tensor (the 16-bit embedding store) stays in its dtype: half the resident bytes and half
+        # the gather's; ``_rows`` widens it to float32 in the gather kernel (``sgp_gather_rows_16``), exactly
+        keep = tensor.dtype if tensor.dtype in hip.STORE_CODES else torch.float32
+        t = tensor.to(self.device, keep)
         return t if t.stride(-1) == 1 else t.contiguous()
 
     def add_input(self, key, tensor, pattern="t n f", scaler=None, preprocess=True):

@@ -25,27 +25,30 @@ from .iid_dataset import IIDSampler, _Entry
 
 
 class ShardedEmbedding:
-    def __init__(self, paths: Sequence[str], n_steps: int, n_nodes: int, d_out: int):
+    def __init__(self, paths: Sequence[str], n_steps: int, n_nodes: int, d_out: int, dtype=torch.float32):
         self.paths = list(paths)
         self.shape = (int(n_steps), int(n_nodes), int(d_out))
+        self.dtype = dtype                          # what the shards hold: float32, or the 16-bit store's format
         self._index = None
 
     @classmethod
     def from_dir(cls, shard_dir):
         meta = torch.load(os.path.join(shard_dir, "index.pt"))
         paths = [os.path.join(shard_dir, os.path.basename(p)) for p in meta["paths"]]
-        return cls(paths, *meta["shape"])
+        return cls(paths, *meta["shape"], dtype=getattr(torch, meta.get("dtype", "float32")))   # (no entry: float32)
 
     @staticmethod
     def write_shard(path, t0, steps, rows, embedding, **extra):
         """One shard file: ``dict(t0, steps, **extra, rows, embedding)``.  ``embedding`` is saved as a copy of its
-        own (the writers hand over a pinned slot that their pipeline refills)."""
+        own (the writers hand over a pinned slot that their pipeline refills), in its own dtype."""
         torch.save(dict(t0=t0, steps=steps, **extra, rows=rows, embedding=embedding.clone()), path)
 
     @staticmethod
-    def write_index(shard_dir, paths, shape):
-        torch.save(dict(paths=[os.path.basename(p) for p in paths], shape=tuple(int(v) for v in shape)),
-                   os.path.join(shard_dir, "index.pt"))
+    def write_index(shard_dir, paths, shape, dtype=torch.float32):
+        meta = dict(paths=[os.path.basename(p) for p in paths], shape=tuple(int(v) for v in shape))
+        if dtype != torch.float32:
+            meta["dtype"] = str(dtype)[6:]          # "bfloat16" / "float16"
+        torch.save(meta, os.path.join(shard_dir, "index.pt"))
 
     def index(self):
         """[(t0, steps, path)] -- read from the file names' shard headers once."""
@@ -57,11 +60,12 @@ class ShardedEmbedding:
             self._index = sorted(out)
         return self._index
 
-    def load_steps(self, t0, t1):
-        """Host tensor [t1 - t0, N, D] in the original node order."""
+    def load_steps(self, t0, t1, dtype=None):
+        """Host tensor [t1 - t0, N, D] in the original node order, in the stored dtype or in ``dtype`` (float32 of a
+        16-bit store: exact)."""
         T, N, D = self.shape
         t0, t1 = max(0, int(t0)), min(T, int(t1))
-        out = torch.empty(t1 - t0, N, D, dtype=torch.float32)
+        out = torch.empty(t1 - t0, N, D, dtype=self.dtype if dtype is None else dtype)
         for s0, steps, path in self.index():
             lo, hi = max(t0, s0), min(t1, s0 + steps)
             if lo >= hi:
@@ -72,7 +76,7 @@ class ShardedEmbedding:
             if rows is None:
                 out[lo - t0:hi - t0] = piece
             else:
-                out[lo - t0:hi - t0].index_copy_(1, rows.long(), piece)
+                out[lo - t0:hi - t0].index_copy_(1, rows.long(), piece.to(out.dtype))
         return out
 
     def __len__(self):
@@ -105,7 +109,8 @@ class ShardedIIDSampler(IIDSampler):
                 raise ValueError("a node belongs to two shards")
             owner[ids] = k
             local[ids] = torch.arange(ids.numel())
-            t = t.to(torch.float32) if t.is_cuda else t.to(self.device, torch.float32)
+            keep = t.dtype if t.dtype in hip.STORE_CODES else torch.float32     # (a 16-bit store stays 16-bit)
+            t = t.to(keep) if t.is_cuda else t.to(self.device, keep)
             tensors.append(t if t.stride(-1) == 1 else t.contiguous())
         if self.group is None and (owner < 0).any():
             raise ValueError("the shards do not cover every node")

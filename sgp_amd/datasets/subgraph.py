@@ -224,6 +224,9 @@ class SubgraphSampler:
             raise ValueError(f"pattern {pattern!r} needs a {len(dims)}-D tensor, got {tuple(tensor.shape)}")
         if tensor.shape[0] != self.n_steps or ("n" in dims and tensor.shape[1] != self.n_nodes):
             raise ValueError("tensor does not match n_steps / n_nodes")
+        if tensor.dtype in hip.STORE_CODES:
+            raise TypeError(f"SubgraphSampler has no {tensor.dtype} window gather: the 16-bit embedding store serves "
+                            f"IIDSampler / ShardedIIDSampler; pass a float32 tensor (DESIGN.md 9n)")
         hip.require_gpu()
         return tensor.to(self.device, torch.float32).contiguous()
 

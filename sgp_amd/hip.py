@@ -63,6 +63,8 @@ with open(_HEADER) as _f:
 SGP_EINVAL, SGP_EUNSUP, SGP_ENOMEM = (_DEFINES[k] for k in ("SGP_EINVAL", "SGP_EUNSUP", "SGP_ENOMEM"))
 # "tanh_rel": tanh with relative accuracy near zero (layers whose bias is tiny: ReservoirLayer.kernel_activation)
 ACT_CODES = {k[len("SGP_ACT_"):].lower(): v for k, v in _DEFINES.items() if k.startswith("SGP_ACT_")}
+# the two formats of the 16-bit embedding store (embed_store.hip)
+STORE_CODES = {torch.bfloat16: _DEFINES["SGP_STORE_BF16"], torch.float16: _DEFINES["SGP_STORE_F16"]}
 
 _lib = None
 
@@ -190,10 +192,10 @@ def _stream(t):
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
-def _view3(t, name):
-    """[B, N, D] float32 CUDA view with unit feature stride -> (ptr, row_stride, batch_stride)."""
-    if t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda:
-        raise ValueError(f"{name}: expected a 3-D float32 CUDA tensor, got "
+def _view3(t, name, dtype=torch.float32):
+    """[B, N, D] float32 (or ``dtype``) CUDA view with unit feature stride -> (ptr, row_stride, batch_stride)."""
+    if t.dim() != 3 or t.dtype != dtype or not t.is_cuda:
+        raise ValueError(f"{name}: expected a 3-D {str(dtype)[6:]} CUDA tensor, got "
                          f"{tuple(t.shape)} {t.dtype} {t.device}")
     if t.shape[2] > 1 and t.stride(2) != 1:
         raise ValueError(f"{name}: feature stride must be 1")
@@ -846,15 +848,82 @@ def gather_nodes(x, node_index, out=None):
     return out
 
 
+def _gather_rows_16(lib, x, step_index, node_index, out):
+    """``gather_rows`` over a bf16 / fp16 source (``sgp_gather_rows_16``): fp32 out, widened exactly."""
+    xp, xrs, xbs = _view3(x, "x", x.dtype)
+    B, D, K = x.shape[0], x.shape[2], node_index.numel()
+    if node_index.dtype != torch.int32 or (step_index is not None and step_index.dtype != torch.int32):
+        raise ValueError("gather_rows: indices must be int32")
+    if step_index is not None:
+        if out is None:
+            out = torch.empty(K, D, dtype=torch.float32, device=x.device)
+        if out.dim() != 2 or tuple(out.shape) != (K, D) or out.dtype != torch.float32 or (D > 1 and out.stride(1) != 1):
+            raise ValueError(f"gather_rows: out must be a float32 [{K}, {D}] view with unit feature stride")
+        _check(lib.sgp_gather_rows_16(xp, xrs, xbs, step_index.data_ptr(), node_index.data_ptr(), K, STORE_CODES[x.dtype],
+                                      out.data_ptr(), out.stride(0), 0, 1, D, _stream(x)), "sgp_gather_rows_16")
+        return out
+    if out is None:
+        out = torch.empty(B, K, D, dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (B, K, D):
+        raise ValueError(f"gather_rows: out must be [{B}, {K}, {D}]")
+    op, ors, obs = _view3(out, "out")
+
+    def run(b0, nb):
+        _check(lib.sgp_gather_rows_16(xp + 2 * b0 * xbs, xrs, xbs, None, node_index.data_ptr(), K, STORE_CODES[x.dtype],
+                                      op + 4 * b0 * obs, ors, obs, nb, D, _stream(x)), "sgp_gather_rows_16")
+    _batched(run, B)
+    return out
+
+
 @_on_device
-def gather_rows(x, step_index, node_index):
-    """out[k, :] = x[step_index[k], node_index[k], :] (IID sampling of the embedding)."""
+def gather_rows(x, step_index, node_index, out=None):
+    """out[k, :] = x[step_index[k], node_index[k], :] (IID sampling of the embedding), fp32.  A bfloat16 / float16
+    ``x`` (the 16-bit embedding store) is widened by its own kernel; it also takes ``step_index=None`` --
+    out[b, k, :] = x[b, node_index[k], :] -- and ``out``, an fp32 view that may be a slot of a wider buffer."""
     lib = require_gpu()
+    if x.dtype in STORE_CODES:
+        return _gather_rows_16(lib, x, step_index, node_index, out)
+    if out is not None or step_index is None:
+        raise ValueError("gather_rows: out= and step_index=None are for bfloat16 / float16 sources")
     xp, xrs, xbs = _view3(x, "x")
     K, D = node_index.numel(), x.shape[2]
     out = torch.empty(K, D, dtype=torch.float32, device=x.device)
     _check(lib.sgp_gather_rows_f32(xp, xrs, xbs, step_index.data_ptr(), node_index.data_ptr(), K,
                                    out.data_ptr(), D, 0, 1, D, _stream(x)), "sgp_gather_rows_f32")
+    return out
+
+
+def store_code(dtype):
+    """The ``SGP_STORE_*`` code of a store dtype; anything but bfloat16 / float16 is a ``ValueError``."""
+    if dtype not in STORE_CODES:
+        raise ValueError(f"store_dtype must be torch.bfloat16 or torch.float16, got {dtype}")
+    return STORE_CODES[dtype]
+
+
+@_on_device
+def pack_rows(x, out=None, dtype=torch.bfloat16, overflow=None):
+    """fp32 ``x[B, N, D]`` -> ``out[B, N, D]`` in bfloat16 / float16, rounded to nearest-even: bit-equal to
+    ``x.to(dtype)`` (``sgp_pack_rows_16``).  Both may be strided views with unit feature stride.  ``out`` given: its
+    dtype is the format.  ``overflow``: a one-element int64 CUDA tensor that float16 packing INCREMENTS by the number
+    of finite values that became infinite (bfloat16 leaves it alone)."""
+    lib = require_gpu()
+    if out is None:
+        store_code(dtype)
+        out = torch.empty(x.shape, dtype=dtype, device=x.device)
+    fmt = store_code(out.dtype)
+    xp, xrs, xbs = _view3(x, "x")
+    yp, yrs, ybs = _view3(out, "out", out.dtype)
+    if tuple(out.shape) != tuple(x.shape) or out.device != x.device:
+        raise ValueError(f"pack_rows: out {tuple(out.shape)} on {out.device} does not match x {tuple(x.shape)} on {x.device}")
+    if overflow is not None and (overflow.dtype != torch.int64 or overflow.numel() != 1 or overflow.device != x.device):
+        raise ValueError("pack_rows: overflow must be a one-element int64 tensor on x's device")
+    B, N, D = x.shape
+    cnt = overflow.data_ptr() if overflow is not None else None
+
+    def run(b0, nb):
+        _check(lib.sgp_pack_rows_16(xp + 4 * b0 * xbs, xrs, xbs, nb, N, D, fmt, yp + 2 * b0 * ybs, yrs, ybs, cnt,
+                                    _stream(x)), "sgp_pack_rows_16")
+    _batched(run, B)
     return out
 
 

@@ -81,7 +81,8 @@ class RegisteredSink:
         self.blocks = []
 
 
-def run_chunks(x, T, tc, encode, dev, n_rows, d_out, *, rows=None, out=None, register=True, sink=None, events=None):
+def run_chunks(x, T, tc, encode, dev, n_rows, d_out, *, rows=None, out=None, register=True, sink=None, events=None,
+               store_dtype=None, overflow=None):
     """Host ``x[T, ...]`` -> ``encode(xs, oc)`` per time chunk of ``tc`` steps -> ``out`` or ``sink``.
 
     ``encode`` only enqueues on the current stream: it reads ``xs[n, n_rows, F]`` and writes ``oc[n, n_rows, d_out]``
@@ -94,20 +95,35 @@ def run_chunks(x, T, tc, encode, dev, n_rows, d_out, *, rows=None, out=None, reg
     H2D into a slot waits for the compute that last read it, the compute for its slot's H2D and for the D2H that last
     emptied its output slot, the host for the previous H2D of a pinned input slot before it refills it -- nothing on
     the compute stream waits for the host.  On return every chunk has reached ``out`` / ``sink``.  ``events``: a list
-    that receives per chunk ``(compute start, compute end, d2h end)`` timing events."""
+    that receives per chunk ``(compute start, compute end, d2h end)`` timing events.
+
+    ``store_dtype`` (bfloat16 / float16): the chunk is still encoded into its fp32 device slot, then packed on the
+    compute stream into a 16-bit device slot (``hip.pack_rows``; float16 counts its overflows into ``overflow``, a
+    one-element int64 device tensor), and that slot is what leaves the device: ``out``, the pinned output slots and
+    what ``sink`` receives are all in the store dtype -- half the D2H bytes."""
     if T == 0:
         return
+    if store_dtype is not None:
+        from . import hip
+        hip.store_code(store_dtype)
+        if out is not None and out.dtype != store_dtype:
+            raise ValueError(f"out is {out.dtype}, store_dtype is {store_dtype}")
+    out_dtype = torch.float32 if store_dtype is None else store_dtype
+    esize = 4 if store_dtype is None else 2
     starts = list(range(0, T, tc))
     nbuf = 2 if len(starts) > 1 else 1
     timing = events is not None
     direct_in = rows is None and x.is_pinned() and x.dtype == torch.float32
     xin = [torch.empty(tc, n_rows, x.shape[2], dtype=torch.float32, device=dev) for _ in range(nbuf)]
     buf = [torch.empty(tc, n_rows, d_out, dtype=torch.float32, device=dev) for _ in range(nbuf)]
+    # what the D2H reads: the fp32 slot itself, or its packed 16-bit copy
+    wire = buf if store_dtype is None else [torch.empty(tc, n_rows, d_out, dtype=store_dtype, device=dev)
+                                            for _ in range(nbuf)]
     pin_in = None if direct_in else [torch.empty(tc, n_rows, x.shape[2], dtype=torch.float32, pin_memory=True)
                                      for _ in range(nbuf)]
     # pinned output slots: every chunk passes one on its way to ``sink``; into ``out`` only a bounced chunk (allocated
     # when that first happens)
-    pin_out = [torch.empty(tc, n_rows, d_out, dtype=torch.float32, pin_memory=True) if out is None else None
+    pin_out = [torch.empty(tc, n_rows, d_out, dtype=out_dtype, pin_memory=True) if out is None else None
                for _ in range(nbuf)]
     out_pinned = out is not None and out.is_pinned()
     reg = RegisteredSink(out) if out is not None and register and not out_pinned else None
@@ -118,9 +134,9 @@ def run_chunks(x, T, tc, encode, dev, n_rows, d_out, *, rows=None, out=None, reg
     h2d, d2h = torch.cuda.Stream(dev, priority=-1), torch.cuda.Stream(dev, priority=-1)
     ev_h2d = [None] * nbuf            # the input slot holds its chunk
     ev_done = [None] * nbuf           # compute of the slot's chunk finished
-    ev_d2h = [None] * nbuf            # the chunk has left buf[slot]
+    ev_d2h = [None] * nbuf            # the chunk has left buf[slot] (wire[slot])
     bounced = [False] * nbuf          # the chunk sits in pin_out[slot], not in out
-    row_bytes = n_rows * d_out * 4
+    row_bytes = n_rows * d_out * esize
 
     def stage_in(i):
         s, t0 = i % nbuf, starts[i]
@@ -148,19 +164,19 @@ def run_chunks(x, T, tc, encode, dev, n_rows, d_out, *, rows=None, out=None, reg
         n = min(tc, T - t0)
         direct = out_pinned or (reg is not None and reg.wait((t0 + n) * row_bytes))
         if not direct and pin_out[s] is None:
-            pin_out[s] = torch.empty(tc, n_rows, d_out, dtype=torch.float32, pin_memory=True)
+            pin_out[s] = torch.empty(tc, n_rows, d_out, dtype=out_dtype, pin_memory=True)
         bounced[s] = not direct
         with torch.cuda.stream(d2h):
             d2h.wait_event(ev_done[s])
             if direct:
-                src, out_flat = buf[s][:n].reshape(-1), out.view(-1)
-                e0 = t0 * (row_bytes // 4)
+                src, out_flat = wire[s][:n].reshape(-1), out.view(-1)
+                e0 = t0 * (row_bytes // esize)
                 cuts = [(t0 * row_bytes, (t0 + n) * row_bytes)] if out_pinned else \
                     reg.pieces(t0 * row_bytes, (t0 + n) * row_bytes)
                 for a, b in cuts:
-                    out_flat[a // 4:b // 4].copy_(src[a // 4 - e0:b // 4 - e0], non_blocking=True)
+                    out_flat[a // esize:b // esize].copy_(src[a // esize - e0:b // esize - e0], non_blocking=True)
             else:
-                pin_out[s][:n].copy_(buf[s][:n], non_blocking=True)
+                pin_out[s][:n].copy_(wire[s][:n], non_blocking=True)
             ev_d2h[s] = torch.cuda.Event(enable_timing=timing)
             ev_d2h[s].record(d2h)
 
@@ -190,6 +206,8 @@ def run_chunks(x, T, tc, encode, dev, n_rows, d_out, *, rows=None, out=None, reg
                 c0 = torch.cuda.Event(enable_timing=True)
                 c0.record(main)
             encode(xin[s][:n], buf[s][:n])
+            if store_dtype is not None:
+                hip.pack_rows(buf[s][:n], wire[s][:n], overflow=overflow)
             ev_done[s] = torch.cuda.Event(enable_timing=timing)
             ev_done[s].record(main)
             send_out(i)

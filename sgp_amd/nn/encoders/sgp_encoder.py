@@ -175,7 +175,61 @@ class SGPEncoder(nn.Module):
     stream_threshold_bytes = 256 << 20
     stream_chunk_bytes = 1 << 30          # embedding bytes per time chunk of the pipelined path
 
-    def encode_streamed(self, x, ops, t_chunk, out=None):
+    # ---- the 16-bit embedding store ----------------------------------------------------------------
+    # The format the last encode of this encoder stored its product in (None: float32); describe() records it.
+    store_dtype = None
+
+    def _overflow_counter(self, store_dtype, dev):
+        """The one device counter of an encode's float16 overflows (finite states that became infinite); bfloat16 has
+        float32's exponent range and needs none."""
+        return torch.zeros(1, dtype=torch.int64, device=dev) if store_dtype == torch.float16 else None
+
+    @staticmethod
+    def _raise_on_overflow(counter):
+        """Read once, after the pipeline has drained."""
+        lost = 0 if counter is None else int(counter.item())
+        if lost:
+            raise OverflowError(f"store_dtype=torch.float16: {lost} finite embedding values exceed float16's range "
+                                f"(65504) and became infinite; store in torch.bfloat16, which has float32's range")
+
+    def encode_device_packed(self, x, ops, out=None, store_dtype=torch.bfloat16, t_chunk=None, state=None):
+        """x[T, N, F] CUDA float32 -> the embedding [T, N, D_out] in ``store_dtype`` (bfloat16 / float16) on the same
+        device: ``t_chunk`` steps at a time are encoded into ONE float32 scratch (``encode_device``) and packed into the
+        resident 16-bit tensor (``hip.pack_rows``, round-to-nearest-even: bit-equal to ``.to(store_dtype)`` of the
+        float32 embedding).  HBM holds the 16-bit embedding plus one scratch chunk.  The reservoir state is carried
+        across the chunks as ``encode_streamed`` carries it.  ``t_chunk`` defaults to ``stream_chunk_bytes`` of
+        float32 embedding, at least 32 steps.  float16 raises ``OverflowError`` if a finite value became infinite."""
+        hip.store_code(store_dtype)
+        hip.require_gpu()
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
+            raise ValueError("encode_device_packed takes a CUDA float32 tensor [T, N, F]")
+        T, N, _ = x.shape
+        D = self.output_size
+        if out is None:
+            out = torch.empty(T, N, D, dtype=store_dtype, device=x.device)
+        elif (out.device != x.device or out.dtype != store_dtype or tuple(out.shape) != (T, N, D)
+              or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous {store_dtype} tensor of shape {(T, N, D)} on {x.device}")
+        self.store_dtype = store_dtype
+        if T == 0:
+            return out
+        if t_chunk is None:
+            t_chunk = max(32, self.stream_chunk_bytes // max(1, N * D * 4))
+        tc = max(1, min(int(t_chunk), T))
+        if state is None:
+            state = self.zero_state(N, x.device)
+        if x.stride(2) != 1:
+            x = x.contiguous()
+        scratch = torch.empty(tc, N, D, dtype=torch.float32, device=x.device)
+        lost = self._overflow_counter(store_dtype, x.device)
+        for t0 in range(0, T, tc):
+            n = min(tc, T - t0)
+            self.encode_device(x[t0:t0 + n], ops, out=scratch[:n], state=state)
+            hip.pack_rows(scratch[:n], out[t0:t0 + n], overflow=lost)
+        self._raise_on_overflow(lost)
+        return out
+
+    def encode_streamed(self, x, ops, t_chunk, out=None, store_dtype=None):
         """Host tensor x[T, N, F] -> host tensor [T, N, D_out], ``t_chunk`` steps at a time,
         transfers overlapped with the compute (the drivers hand over host tensors,
         lib/utils.py:24-31): two device buffers per direction, H2D of chunk i+1 (through a pinned
@@ -193,39 +247,59 @@ class SGPEncoder(nn.Module):
         of a fresh one.  A FRESH result tensor costs this host a page fault + zeroing per page
         (11-13 GB/s) -- more than the PCIe transfer; a tensor that is re-used between
         calls (or was touched before) skips that, and a pinned one (``.pin_memory()``) is written
-        by the D2H copies directly, without the registration thread."""
+        by the D2H copies directly, without the registration thread.
+
+        ``store_dtype`` (bfloat16 / float16; or an ``out`` of that dtype): every chunk is packed on the device after
+        its hops and leaves it in 16 bits -- half the D2H bytes and half the host tensor; the result is bit-equal to
+        ``.to(store_dtype)`` of the float32 result.  float16 raises ``OverflowError`` if a finite value became
+        infinite."""
+        if store_dtype is None and out is not None and out.dtype in hip.STORE_CODES:
+            store_dtype = out.dtype
+        if store_dtype is not None:
+            hip.store_code(store_dtype)
+            if out is not None and out.dtype != store_dtype:
+                raise ValueError(f"out is {out.dtype}, store_dtype is {store_dtype}")
         hip.require_gpu()
         T, N, _ = x.shape
         dev = torch.device("cuda", torch.cuda.current_device())
         D = self.output_size
+        dtype = torch.float32 if store_dtype is None else store_dtype
         if out is None:
-            out = torch.empty(T, N, D, dtype=torch.float32)
-        elif (out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (T, N, D)
+            out = torch.empty(T, N, D, dtype=dtype)
+        elif (out.is_cuda or out.dtype != dtype or tuple(out.shape) != (T, N, D)
               or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous float32 host tensor of shape {(T, N, D)}")
+            raise ValueError(f"out must be a contiguous {str(dtype)[6:]} host tensor of shape {(T, N, D)}")
         state = self.zero_state(N, dev)
+        self.store_dtype = store_dtype
+        lost = self._overflow_counter(store_dtype, dev)
         hostpipe.run_chunks(x, T, max(1, min(int(t_chunk), T)),
                             lambda xs, oc: self.encode_device(xs, ops, out=oc, state=state),
-                            dev, N, D, out=out, register=self.register_output)
+                            dev, N, D, out=out, register=self.register_output, store_dtype=store_dtype, overflow=lost)
+        self._raise_on_overflow(lost)
         return out
 
-    def encode_to_shards(self, x, ops, shard_dir, shard_steps):
+    def encode_to_shards(self, x, ops, shard_dir, shard_steps, store_dtype=None):
         """Host tensor x[T, N, F] -> time shards on disk, ``shard_steps`` steps each, through the pipeline of
         ``encode_streamed``: embeddings larger than host RAM (configuration C5 is 629 GB,
         ``experiments/run_largescale_sgp.py:208-212``).  The host holds at most two pinned shard-sized slots (the
         pipeline's double buffer) plus the copy of the shard being written.  The reservoir state is carried on the
         device, the propagation is independent per step: the shards are bit-identical to slices of one pass.
-        Returns a ``sgp_amd.datasets.ShardedEmbedding`` (``load_steps(t0, t1)`` reads any time range back)."""
+        Returns a ``sgp_amd.datasets.ShardedEmbedding`` (``load_steps(t0, t1)`` reads any time range back).
+        ``store_dtype`` (bfloat16 / float16): the shards hold the embedding in 16 bits, packed on the device."""
         import os
         from ...datasets.sharded import ShardedEmbedding
+        if store_dtype is not None:
+            hip.store_code(store_dtype)
         hip.require_gpu()
         T, N, F = x.shape
         os.makedirs(shard_dir, exist_ok=True)
         dev = torch.device("cuda", torch.cuda.current_device())
         D = self.output_size
-        per_step = N * (F + D) * 4
+        per_step = N * (F + D) * 4 + (0 if store_dtype is None else N * D * 2)     # (+ the 16-bit slot beside the fp32 one)
         ts = max(1, min(int(shard_steps), T, self._budget() // max(1, 2 * per_step)))    # two slots each way
         state = self.zero_state(N, dev)
+        self.store_dtype = store_dtype
+        lost = self._overflow_counter(store_dtype, dev)
         paths = []
 
         def sink(t0, n, emb):
@@ -233,9 +307,11 @@ class SGPEncoder(nn.Module):
             ShardedEmbedding.write_shard(paths[-1], t0, n, None, emb)
 
         hostpipe.run_chunks(x, T, ts, lambda xs, oc: self.encode_device(xs, ops, out=oc, state=state),
-                            dev, N, D, sink=sink)
-        ShardedEmbedding.write_index(shard_dir, paths, (T, N, D))
-        return ShardedEmbedding(paths, T, N, D)
+                            dev, N, D, sink=sink, store_dtype=store_dtype, overflow=lost)
+        self._raise_on_overflow(lost)
+        dtype = torch.float32 if store_dtype is None else store_dtype
+        ShardedEmbedding.write_index(shard_dir, paths, (T, N, D), dtype=dtype)
+        return ShardedEmbedding(paths, T, N, D, dtype=dtype)
 
     def zero_state(self, n_nodes, device):
         """Reservoir state ``[L, n_nodes, R]`` carried across time chunks: zero, hence marked unit-bounded
@@ -249,7 +325,7 @@ class SGPEncoder(nn.Module):
     register_output = True
 
     def forward(self, x, edge_index, edge_weight, return_device=False, out=None, gpus=None, shard_dir=None,
-                shard_steps=None):
+                shard_steps=None, store_dtype=None, t_chunk=None):
         # x : [t n f]; ``return_device=True`` keeps the embedding of a host input on the GPU
         # (the next row f1 consumes it there: sgp_amd.datasets.IIDDataset); ``out``: host tensor
         # [t, n, d_out] to fill (host inputs only; see encode_streamed); ``gpus``: number of GPUs the
@@ -259,8 +335,20 @@ class SGPEncoder(nn.Module):
         # ``shard_dir``: write the embedding as shard files instead of returning one host tensor (embeddings
         # larger than host RAM) -- time shards of ``shard_steps`` steps on one GPU, time x node-block shards of
         # the ranks with ``gpus`` > 1; the call then returns a ``sgp_amd.datasets.ShardedEmbedding``
+        # ``store_dtype`` (torch.bfloat16 / torch.float16, or an ``out`` of that dtype): the embedding is stored in 16
+        # bits -- host tensor, shards or, with ``return_device`` / a device input, the resident tensor
+        # (encode_device_packed, ``t_chunk`` steps per scratch chunk); one GPU only
         from ... import multigpu
         n_gpus = multigpu.resolve_gpus(gpus)
+        if store_dtype is None and out is not None and out.dtype in hip.STORE_CODES:
+            store_dtype = out.dtype
+        if store_dtype is not None:
+            hip.store_code(store_dtype)
+            if n_gpus > 1:
+                raise ValueError("store_dtype is a single-GPU path: the ranks of gpus > 1 exchange and write float32")
+            return self._forward_stored(x, edge_index, edge_weight, return_device, out, shard_dir, shard_steps,
+                                        store_dtype, t_chunk)
+        self.store_dtype = None
         if n_gpus > 1:
             if x.is_cuda or return_device:
                 raise ValueError("gpus > 1 takes a host tensor and returns a host tensor in the original node "
@@ -304,6 +392,40 @@ class SGPEncoder(nn.Module):
             xg = xg.contiguous()
         return self.encode_device(xg, ops).to(dev)
 
+    def _forward_stored(self, x, edge_index, edge_weight, return_device, out, shard_dir, shard_steps, store_dtype,
+                        t_chunk):
+        """``forward`` with ``store_dtype``: the same routes, every one through the pack kernel."""
+        ops = self.sgp_encoder.operators(x.size(-2), edge_index, edge_weight)
+        if shard_dir is not None:
+            if x.is_cuda or return_device or out is not None:
+                raise ValueError("shard_dir takes a host tensor and writes shard files")
+            return self.encode_to_shards(x, ops, shard_dir, shard_steps or 256, store_dtype=store_dtype)
+        xg = x.float()
+        T, N, F = xg.shape
+        D = self.output_size
+        if xg.is_cuda or return_device:
+            if out is not None:
+                raise ValueError("out= is for host inputs (a device input returns a device tensor)")
+            if t_chunk is None:
+                t_chunk = max(32, self.stream_chunk_bytes // max(1, N * D * 4))
+            t_chunk = max(1, min(int(t_chunk), max(1, T)))
+            if not xg.is_cuda:
+                hip.require_gpu()
+                # the input, the 16-bit embedding and the one float32 scratch chunk
+                if T * N * (F * 4 + D * 2) + t_chunk * N * D * 4 > self._budget():
+                    raise RuntimeError("return_device=True: the embedding does not fit the device")
+                xg = xg.cuda()
+            return self.encode_device_packed(xg, ops, store_dtype=store_dtype, t_chunk=t_chunk)
+        hip.require_gpu()
+        # two input, two float32 and two 16-bit output slots on the device
+        per_step = N * (F + D) * 4 + N * D * 2
+        if t_chunk is None:
+            t_chunk = T
+            if T * per_step > min(self._budget(), self.stream_threshold_bytes) and T > 1:
+                t_chunk = max(32, self.stream_chunk_bytes // max(1, N * D * 4))
+        t_chunk = max(1, min(int(t_chunk), self._budget() // max(1, 2 * per_step)))
+        return self.encode_streamed(xg, ops, t_chunk, out=out, store_dtype=store_dtype)
+
     def describe(self):
         """What makes an embedding re-derivable: constructor arguments, the
         per-layer leaking rates and every weight tensor."""
@@ -319,6 +441,8 @@ class SGPEncoder(nn.Module):
                         global_attr=sp.global_attr, add_self_loops=sp.add_self_loops,
                         undirected=sp.undirected, reservoir_activation=res.mode),
             alphas=[float(l.alpha) for l in res.reservoir_layers],
+            # the format the last encode stored the embedding in ("bfloat16" / "float16"; None: float32)
+            store_dtype=None if self.store_dtype is None else str(self.store_dtype)[6:],
             state_dict={k: v.detach().cpu().clone() for k, v in self.state_dict().items()})
 
     @staticmethod

@@ -79,6 +79,9 @@ def gram_to_coef(gram, n_rows, shift, n_features, alpha, fit_intercept=True):
 # ---------------------------------------------------------------------------------------------- segments
 def _feature_segment(t, name):
     """[T, N, w] (per node) or [T, w] (global: broadcast over the nodes) -> (tensor, ss, ns, w, 0, 1)."""
+    if torch.is_tensor(t) and t.dtype in hip.STORE_CODES:
+        raise TypeError(f"{name}: the ridge readout's Gram kernels read float32; a {t.dtype} embedding (the 16-bit "
+                        f"store) is not cast silently -- pass .float() of it (DESIGN.md 9n)")
     if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() not in (2, 3):
         raise ValueError(f"{name}: expected a 2-D or 3-D float32 tensor, got "
                          f"{getattr(t, 'shape', type(t))} {getattr(t, 'dtype', '')}")

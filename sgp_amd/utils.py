@@ -13,7 +13,8 @@ logger = logging.getLogger("sgp_amd")
 
 
 def encode_dataset(dataset, encoder_class, encoder_kwargs, encode_exogenous=True,
-                   keep_raw=False, save_path=None, return_device=False, gpus=None, shard_steps=None):
+                   keep_raw=False, save_path=None, return_device=False, gpus=None, shard_steps=None,
+                   store_dtype=None):
     """lib/utils.py:10-47.  ``dataset`` is any object with the slice of the
     ``tsl.data.SpatioTemporalDataset`` interface the harness touches: ``exogenous``,
     ``get_tensors``, ``edge_index``, ``edge_weight``, ``add_exogenous``, ``set_input_map``.
@@ -33,7 +34,9 @@ def encode_dataset(dataset, encoder_class, encoder_kwargs, encode_exogenous=True
     time shards of S steps (the host holds at most two pinned shard-sized slots and the copy being
     written: embeddings larger than host RAM, the 629 GB of ``run_largescale_sgp.py:208-212``)
     instead of the reference's single ``torch.save`` (lib/utils.py:34-35); ``encoded_x`` is then a
-    ``sgp_amd.datasets.ShardedEmbedding``."""
+    ``sgp_amd.datasets.ShardedEmbedding``; ``store_dtype=torch.bfloat16`` (or ``torch.float16``) keeps the
+    embedding in 16 bits wherever it goes -- host tensor, shards or, with ``return_device``, HBM (half
+    the D2H, resident and gather bytes; ``IIDSampler`` widens its batches back to float32; one GPU only)."""
     exo_keys = _exogenous_to_encode(dataset, encode_exogenous)
     x, _ = dataset.get_tensors(['data'] + exo_keys, preprocess=True, cat_dim=-1)
     encoder = encoder_class(**encoder_kwargs)
@@ -45,15 +48,16 @@ def encode_dataset(dataset, encoder_class, encoder_kwargs, encode_exogenous=True
         from . import hip
         x, _ = hip.to_gpu(x)
     from .multigpu import resolve_gpus
+    stored = {} if store_dtype is None else dict(store_dtype=store_dtype)
     if shard_steps is not None:
         embedding = encoder(x, edge_index=dataset.edge_index, edge_weight=dataset.edge_weight, gpus=gpus,
-                            shard_dir=str(save_path), shard_steps=int(shard_steps))
+                            shard_dir=str(save_path), shard_steps=int(shard_steps), **stored)
     elif resolve_gpus(gpus) > 1:
         if return_device:
             raise ValueError("return_device=True keeps ONE device tensor: use gpus=1")
-        embedding = encoder(x, edge_index=dataset.edge_index, edge_weight=dataset.edge_weight, gpus=gpus)
+        embedding = encoder(x, edge_index=dataset.edge_index, edge_weight=dataset.edge_weight, gpus=gpus, **stored)
     else:
-        embedding = encoder(x, edge_index=dataset.edge_index, edge_weight=dataset.edge_weight)
+        embedding = encoder(x, edge_index=dataset.edge_index, edge_weight=dataset.edge_weight, **stored)
     seconds = int(time() - started)
     logger.info(f"Dataset encoded in {seconds // 60}:{seconds % 60:02d} minutes.")
 
