@@ -24,6 +24,8 @@
  *       the same embedding kept in bf16 / fp16 (no counterpart in the reference: lib/utils.py:24-35 holds float32)
  *   sgp_grouped_linear_f32
  *       lib/nn/models/sgp_model.py:41-52 (decoder input encoder: grouped Conv1d + activation; f4)
+ *   sgp_grouped_linear_fwd_16, sgp_grouped_linear_wgrad_16
+ *       the same layer, forward and weight gradient, reading the bf16 / fp16 embedding in place
  *
  * Conventions
  *   - All pointers are DEVICE pointers owned by the caller (e.g. the PyTorch
@@ -721,6 +723,34 @@ int sgp_grouped_linear_form(int32_t ic, int32_t oc, int64_t x_row_stride, int64_
                             int32_t* jtc, int32_t* xvec);
 int sgp_grouped_linear_wgrad_form(int32_t n_rows, int32_t groups, int32_t ic, int32_t oc,
                                   int32_t* rows_per_slice, int32_t* slices);
+/* The same layer fed from the 16-bit embedding store: X holds bfloat16 / float16 elements (`fmt` =
+ * SGP_STORE_BF16 / SGP_STORE_F16, anything else SGP_EINVAL), 2-byte aligned, strides in 16-bit ELEMENTS; every other
+ * argument, the row sources (step / node, or step = NULL: plain rows X[row]), pre, dropout, activation and
+ * out_row_stride are sgp_grouped_linear_fwd_f32's and sgp_grouped_linear_wgrad_f32's.  The kernels are the fp32 ones
+ * instantiated for the source type: an element is widened to fp32 in registers (bf16: shift left by 16; fp16: the
+ * hardware convert -- both exact) and enters the same v_mfma_f32_16x16x4_f32 chain in the same order, so
+ *   sgp_grouped_linear_fwd_16(X16) is BIT-EQUAL to sgp_grouped_linear_fwd_f32(widened X16), out and pre, and
+ *   sgp_grouped_linear_wgrad_16 is bit-equal to sgp_grouped_linear_wgrad_f32 wherever that one is deterministic (one
+ *   row slice); with several slices both meet in dW through float atomics in no fixed order.
+ * Weights, bias, dz, out, pre and dW stay fp32; no gradient exists for X.  n_rows == 0: success without a launch (the
+ * wgrad entry still zeroes dW).
+ * sgp_grouped_linear_form_16: jtc as sgp_grouped_linear_form; xvec = 1 when a lane reads the 4 elements of a k-block
+ * with one 8-byte load: ic % 4 == 0, both strides multiples of 4 elements and x_aligned8 (X on an 8-byte boundary);
+ * 0 = one element at a time (any ic, any stride, 2-byte alignment). */
+int sgp_grouped_linear_fwd_16(const void* X, int32_t fmt, int64_t x_row_stride, int64_t x_batch_stride,
+                              const int32_t* step, const int32_t* node,
+                              const float* w_packed, const float* bias, int32_t act,
+                              float* out, int64_t out_row_stride, float* pre,
+                              double dropout_p, uint64_t seed,
+                              int32_t n_rows, int32_t groups, int32_t ic, int32_t oc,
+                              sgp_stream_t stream);
+int sgp_grouped_linear_wgrad_16(const void* X, int32_t fmt, int64_t x_row_stride, int64_t x_batch_stride,
+                                const int32_t* step, const int32_t* node,
+                                const float* dz, float* dw,
+                                int32_t n_rows, int32_t groups, int32_t ic, int32_t oc,
+                                sgp_stream_t stream);
+int sgp_grouped_linear_form_16(int32_t ic, int32_t oc, int64_t x_row_stride, int64_t x_batch_stride, int32_t x_aligned8,
+                               int32_t* jtc, int32_t* xvec);
 
 /* ---------------------------------------------------------- Ridge readout ---
  * The closed-form baseline's readout (experiments/run_closed_form.py:169-247): sklearn Ridge(alpha) fitted once per

@@ -39,14 +39,28 @@ __global__ void pack_grouped(const float* __restrict__ w, float* __restrict__ ou
     }
 }
 
+// The source of the rows: FMT 0 = fp32, SGP_STORE_BF16 / SGP_STORE_F16 = the 16-bit embedding store.
+// A 16-bit element is widened to fp32 in registers -- exactly, in both formats: bf16 is the upper half of the fp32
+// pattern, every fp16 value (subnormals included) is an fp32 value -- and feeds the same MFMA chain in the same order,
+// so a 16-bit launch is bit-equal to the fp32 launch on the widened source.
+template <int FMT> struct Src { using T = unsigned short; };
+template <> struct Src<0> { using T = float; };
+
+template <int FMT>
+__device__ __forceinline__ float widen(unsigned h) {
+    if constexpr (FMT == SGP_STORE_BF16) return __uint_as_float(h << 16);
+    else return (float)__builtin_bit_cast(_Float16, (unsigned short)h);     // v_cvt_f32_f16
+}
+
+template <int FMT>
 struct GlArgs {
-    const float* x; long long xrs, xbs;
+    const typename Src<FMT>::T* x; long long xrs, xbs;   // strides in elements of the source
     const int* step; const int* node;
     const float* wp; const float* bias;
     float* out; long long ors;
     float* pre;                       // [n_rows, groups*oc] pre-activation values for the backward pass, or null
     int n_rows, groups, ic, oc, act;
-    bool xvec;
+    bool xvec;                        // a lane's 4 elements of a k-block in one load (16 bytes of fp32, 8 of a 16-bit source)
     unsigned drop_thresh;             // Dropout(p) after the activation (sgp_model.py:50): element kept when its
     unsigned seed_lo, seed_hi;        // Philox word >= drop_thresh = p * 2^32, scaled by keep_scale = 1 / (1 - p);
     float keep_scale;                 // drop_thresh == 0: no dropout (eval mode / p = 0)
@@ -55,15 +69,15 @@ struct GlArgs {
 // One wave = 16 rows x one group (blockIdx.y).  JTC output tiles (16 channels each) are accumulated
 // together so that every row piece is loaded once; the row pieces of 8 k-blocks are requested
 // before the first MFMA consumes one (a wave's chain is one memory latency, not one per k-block).
-template <int JTC>
-__global__ __launch_bounds__(64) void grouped_linear(GlArgs a) {
+template <int JTC, int FMT>
+__global__ __launch_bounds__(64) void grouped_linear(GlArgs<FMT> a) {
     constexpr int KC = 8;
     const int lane = threadIdx.x & 63;
     const int b = lane & 15, q = lane >> 4;
     const int row = blockIdx.x * 16 + b;
     const int g = blockIdx.y;
     const bool ok = row < a.n_rows;
-    const float* xp = a.x;
+    const typename Src<FMT>::T* xp = a.x;
     if (ok) {
         if (a.step) xp += (long long)a.step[row] * a.xbs + (long long)a.node[row] * a.xrs;
         else xp += (long long)row * a.xrs;
@@ -87,13 +101,25 @@ __global__ __launch_bounds__(64) void grouped_linear(GlArgs a) {
                 const int k = 16 * (kb0 + u) + 4 * q;
                 xv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (ok && kb0 + u < KB) {
-                    const float* p = xp + k;
-                    if (a.xvec) {
-                        if (k < a.ic) xv[u] = *reinterpret_cast<const f32x4*>(p);
+                    const typename Src<FMT>::T* p = xp + k;
+                    if constexpr (FMT == 0) {
+                        if (a.xvec) {
+                            if (k < a.ic) xv[u] = *reinterpret_cast<const f32x4*>(p);
+                        } else {
+#pragma unroll
+                            for (int s = 0; s < 4; ++s)
+                                if (k + s < a.ic) xv[u][s] = p[s];
+                        }
+                    } else if (a.xvec) {
+                        if (k < a.ic) {
+                            const uint2 h = *reinterpret_cast<const uint2*>(p);
+                            xv[u] = f32x4{widen<FMT>(h.x & 0xFFFFu), widen<FMT>(h.x >> 16),
+                                          widen<FMT>(h.y & 0xFFFFu), widen<FMT>(h.y >> 16)};
+                        }
                     } else {
 #pragma unroll
                         for (int s = 0; s < 4; ++s)
-                            if (k + s < a.ic) xv[u][s] = p[s];
+                            if (k + s < a.ic) xv[u][s] = widen<FMT>(p[s]);
                     }
                 }
             }
@@ -171,15 +197,17 @@ __global__ void transpose_grouped(const float* __restrict__ w, float* __restrict
 // v_mfma_f32_16x16x4_f32 with the ROWS as the contraction index: D[o, i] += dz[row, o] * x[row, i],
 // A operand lane (k, o) = dz[row0 + k][o], B operand lane (k, i) = x[row0 + k][i] (64-byte row pieces,
 // 4 rows per instruction); slices meet in dW through float atomics (dW is zeroed first).
+template <int FMT>
 struct WgArgs {
-    const float* x; long long xrs, xbs;
+    const typename Src<FMT>::T* x; long long xrs, xbs;
     const int* step; const int* node;
     const float* dz;                  // [n_rows, groups*oc]
     float* dw;                        // [groups*oc, ic]
     int n_rows, groups, ic, oc, rows_per_slice;
 };
 
-__global__ __launch_bounds__(64) void wgrad_kernel(WgArgs a) {
+template <int FMT>
+__global__ __launch_bounds__(64) void wgrad_kernel(WgArgs<FMT> a) {
     const int lane = threadIdx.x & 63;
     const int c = lane & 15, k = lane >> 4;
     const int KB = (a.ic + 15) / 16, JT = (a.oc + 15) / 16;
@@ -198,9 +226,11 @@ __global__ __launch_bounds__(64) void wgrad_kernel(WgArgs a) {
             av[u] = (ok && o < a.oc) ? a.dz[(long long)row * a.groups * a.oc + g * a.oc + o] : 0.f;
             float xv = 0.f;
             if (ok && i < a.ic) {
-                const float* xp = a.step ? a.x + (long long)a.step[row] * a.xbs + (long long)a.node[row] * a.xrs
-                                         : a.x + (long long)row * a.xrs;
-                xv = xp[g * a.ic + i];
+                const typename Src<FMT>::T* xp =
+                    a.step ? a.x + (long long)a.step[row] * a.xbs + (long long)a.node[row] * a.xrs
+                           : a.x + (long long)row * a.xrs;
+                if constexpr (FMT == 0) xv = xp[g * a.ic + i];
+                else xv = widen<FMT>(xp[g * a.ic + i]);
             }
             bv[u] = xv;
         }
@@ -213,6 +243,72 @@ __global__ __launch_bounds__(64) void wgrad_kernel(WgArgs a) {
         const int oo = 16 * jt + 4 * k + r;
         if (oo < a.oc && i < a.ic) atomicAdd(a.dw + ((long long)g * a.oc + oo) * a.ic + i, acc[r]);
     }
+}
+
+// the checks, the form and the launch shared by the fp32 and the 16-bit entries
+template <int FMT>
+int launch_grouped_linear(const void* X, int64_t x_row_stride, int64_t x_batch_stride,
+                                 const int32_t* step, const int32_t* node,
+                                 const float* w_packed, const float* bias, int32_t act,
+                                 float* out, int64_t out_row_stride, float* pre,
+                                 double dropout_p, uint64_t seed,
+                                 int32_t n_rows, int32_t groups, int32_t ic, int32_t oc,
+                                 sgp_stream_t stream) {
+    SGP_REQUIRE(X && w_packed && bias && out, "sgp_grouped_linear_f32: null pointer");
+    SGP_REQUIRE(dropout_p >= 0.0 && dropout_p < 1.0, "sgp_grouped_linear_fwd_f32: dropout_p must lie in [0, 1)");
+    SGP_REQUIRE((step == nullptr) == (node == nullptr), "sgp_grouped_linear_f32: step and node go together");
+    SGP_REQUIRE(n_rows >= 0 && groups > 0 && ic > 0 && oc > 0, "sgp_grouped_linear_f32: bad size");
+    SGP_REQUIRE(act >= 0 && act <= 2, "sgp_grouped_linear_f32: unknown activation %d", act);
+    SGP_REQUIRE(sgp::aligned16(w_packed), "sgp_grouped_linear_f32: packed weights must be 16-byte aligned");
+    if (FMT != 0)
+        SGP_REQUIRE((reinterpret_cast<uintptr_t>(X) & 1u) == 0, "sgp_grouped_linear_fwd_16: X must be 2-byte aligned");
+    if (n_rows == 0) return 0;
+    GlArgs<FMT> a;
+    a.x = static_cast<const typename Src<FMT>::T*>(X); a.xrs = x_row_stride; a.xbs = x_batch_stride;
+    a.step = step; a.node = node;
+    a.wp = w_packed; a.bias = bias;
+    a.out = out; a.ors = out_row_stride; a.pre = pre;
+    set_dropout(a.drop_thresh, a.seed_lo, a.seed_hi, a.keep_scale, dropout_p, seed);
+    a.n_rows = n_rows; a.groups = groups; a.ic = ic; a.oc = oc; a.act = act;
+    int32_t jtc, xvec;                                                                        // sizes checked above
+    if (FMT == 0) sgp_grouped_linear_form(ic, oc, x_row_stride, x_batch_stride, sgp::aligned16(X) ? 1 : 0, &jtc, &xvec);
+    else sgp_grouped_linear_form_16(ic, oc, x_row_stride, x_batch_stride,
+                                    (reinterpret_cast<uintptr_t>(X) & 7u) == 0 ? 1 : 0, &jtc, &xvec);
+    a.xvec = xvec != 0;
+    const int grid = (n_rows + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+    SGP_REQUIRE(groups <= 65535, "sgp_grouped_linear_f32: more than 65535 groups");
+    if (jtc == 1) hipLaunchKernelGGL((grouped_linear<1, FMT>), dim3(grid, groups), dim3(64), 0, s, a);
+    else if (jtc == 2) hipLaunchKernelGGL((grouped_linear<2, FMT>), dim3(grid, groups), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((grouped_linear<4, FMT>), dim3(grid, groups), dim3(64), 0, s, a);
+    return sgp::check_launch("grouped_linear");
+}
+
+template <int FMT>
+int launch_wgrad(const void* X, int64_t x_row_stride, int64_t x_batch_stride,
+                        const int32_t* step, const int32_t* node, const float* dz, float* dw,
+                        int32_t n_rows, int32_t groups, int32_t ic, int32_t oc, sgp_stream_t stream) {
+    SGP_REQUIRE(X && dz && dw, "sgp_grouped_linear_wgrad_f32: null pointer");
+    SGP_REQUIRE((step == nullptr) == (node == nullptr), "sgp_grouped_linear_wgrad_f32: step and node go together");
+    SGP_REQUIRE(n_rows >= 0 && groups > 0 && ic > 0 && oc > 0, "sgp_grouped_linear_wgrad_f32: bad size");
+    if (FMT != 0)
+        SGP_REQUIRE((reinterpret_cast<uintptr_t>(X) & 1u) == 0, "sgp_grouped_linear_wgrad_16: X must be 2-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(dw, 0, (size_t)groups * oc * ic * sizeof(float), s);
+    if (e != hipSuccess) return sgp::fail((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (n_rows == 0) return 0;
+    WgArgs<FMT> a;
+    a.x = static_cast<const typename Src<FMT>::T*>(X); a.xrs = x_row_stride; a.xbs = x_batch_stride;
+    a.step = step; a.node = node;
+    a.dz = dz; a.dw = dw; a.n_rows = n_rows; a.groups = groups; a.ic = ic; a.oc = oc;
+    const long long tiles = (long long)groups * ((ic + 15) / 16) * ((oc + 15) / 16);
+    SGP_REQUIRE(tiles < (1ll << 31), "sgp_grouped_linear_wgrad_f32: too many tiles");
+    int32_t rps, ny;
+    sgp_grouped_linear_wgrad_form(n_rows, groups, ic, oc, &rps, &ny);    // sizes checked above
+    a.rows_per_slice = rps;
+    SGP_REQUIRE(ny <= 65535, "sgp_grouped_linear_wgrad_f32: too many row slices");
+    hipLaunchKernelGGL(wgrad_kernel<FMT>, dim3((unsigned)tiles, (unsigned)ny), dim3(64), 0, s, a);
+    return sgp::check_launch("grouped_linear_wgrad");
 }
 
 }  // namespace
@@ -252,30 +348,24 @@ int sgp_grouped_linear_fwd_f32(const float* X, int64_t x_row_stride, int64_t x_b
                                double dropout_p, uint64_t seed,
                                int32_t n_rows, int32_t groups, int32_t ic, int32_t oc,
                                sgp_stream_t stream) {
-    SGP_REQUIRE(X && w_packed && bias && out, "sgp_grouped_linear_f32: null pointer");
-    SGP_REQUIRE(dropout_p >= 0.0 && dropout_p < 1.0, "sgp_grouped_linear_fwd_f32: dropout_p must lie in [0, 1)");
-    SGP_REQUIRE((step == nullptr) == (node == nullptr), "sgp_grouped_linear_f32: step and node go together");
-    SGP_REQUIRE(n_rows >= 0 && groups > 0 && ic > 0 && oc > 0, "sgp_grouped_linear_f32: bad size");
-    SGP_REQUIRE(act >= 0 && act <= 2, "sgp_grouped_linear_f32: unknown activation %d", act);
-    SGP_REQUIRE(sgp::aligned16(w_packed), "sgp_grouped_linear_f32: packed weights must be 16-byte aligned");
-    if (n_rows == 0) return 0;
-    GlArgs a;
-    a.x = X; a.xrs = x_row_stride; a.xbs = x_batch_stride;
-    a.step = step; a.node = node;
-    a.wp = w_packed; a.bias = bias;
-    a.out = out; a.ors = out_row_stride; a.pre = pre;
-    set_dropout(a.drop_thresh, a.seed_lo, a.seed_hi, a.keep_scale, dropout_p, seed);
-    a.n_rows = n_rows; a.groups = groups; a.ic = ic; a.oc = oc; a.act = act;
-    int32_t jtc, xvec;
-    sgp_grouped_linear_form(ic, oc, x_row_stride, x_batch_stride, sgp::aligned16(X) ? 1 : 0, &jtc, &xvec);   // sizes checked above
-    a.xvec = xvec != 0;
-    const int grid = (n_rows + 15) / 16;
-    hipStream_t s = (hipStream_t)stream;
-    SGP_REQUIRE(groups <= 65535, "sgp_grouped_linear_f32: more than 65535 groups");
-    if (jtc == 1) hipLaunchKernelGGL(grouped_linear<1>, dim3(grid, groups), dim3(64), 0, s, a);
-    else if (jtc == 2) hipLaunchKernelGGL(grouped_linear<2>, dim3(grid, groups), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL(grouped_linear<4>, dim3(grid, groups), dim3(64), 0, s, a);
-    return sgp::check_launch("grouped_linear");
+    return launch_grouped_linear<0>(X, x_row_stride, x_batch_stride, step, node, w_packed, bias, act, out, out_row_stride,
+                                    pre, dropout_p, seed, n_rows, groups, ic, oc, stream);
+}
+
+int sgp_grouped_linear_fwd_16(const void* X, int32_t fmt, int64_t x_row_stride, int64_t x_batch_stride,
+                              const int32_t* step, const int32_t* node,
+                              const float* w_packed, const float* bias, int32_t act,
+                              float* out, int64_t out_row_stride, float* pre,
+                              double dropout_p, uint64_t seed,
+                              int32_t n_rows, int32_t groups, int32_t ic, int32_t oc,
+                              sgp_stream_t stream) {
+    SGP_REQUIRE(fmt == SGP_STORE_BF16 || fmt == SGP_STORE_F16,
+                "sgp_grouped_linear_fwd_16: fmt must be SGP_STORE_BF16 or SGP_STORE_F16");
+    if (fmt == SGP_STORE_BF16)
+        return launch_grouped_linear<SGP_STORE_BF16>(X, x_row_stride, x_batch_stride, step, node, w_packed, bias, act, out,
+                                                     out_row_stride, pre, dropout_p, seed, n_rows, groups, ic, oc, stream);
+    return launch_grouped_linear<SGP_STORE_F16>(X, x_row_stride, x_batch_stride, step, node, w_packed, bias, act, out,
+                                                out_row_stride, pre, dropout_p, seed, n_rows, groups, ic, oc, stream);
 }
 
 int sgp_grouped_linear_form(int32_t ic, int32_t oc, int64_t x_row_stride, int64_t x_batch_stride, int32_t x_aligned16,
@@ -284,6 +374,15 @@ int sgp_grouped_linear_form(int32_t ic, int32_t oc, int64_t x_row_stride, int64_
     const int JT = (oc + 15) / 16;
     if (jtc) *jtc = JT == 1 ? 1 : (JT == 2 ? 2 : 4);
     if (xvec) *xvec = (ic % 4 == 0 && x_row_stride % 4 == 0 && x_batch_stride % 4 == 0 && x_aligned16) ? 1 : 0;
+    return 0;
+}
+
+int sgp_grouped_linear_form_16(int32_t ic, int32_t oc, int64_t x_row_stride, int64_t x_batch_stride, int32_t x_aligned8,
+                               int32_t* jtc, int32_t* xvec) {
+    SGP_REQUIRE(ic > 0 && oc > 0, "sgp_grouped_linear_form_16: bad size");
+    const int JT = (oc + 15) / 16;
+    if (jtc) *jtc = JT == 1 ? 1 : (JT == 2 ? 2 : 4);
+    if (xvec) *xvec = (ic % 4 == 0 && x_row_stride % 4 == 0 && x_batch_stride % 4 == 0 && x_aligned8) ? 1 : 0;
     return 0;
 }
 
@@ -333,24 +432,19 @@ int sgp_grouped_linear_wgrad_f32(const float* X, int64_t x_row_stride, int64_t x
                                  const float* dz, float* dw,
                                  int32_t n_rows, int32_t groups, int32_t ic, int32_t oc,
                                  sgp_stream_t stream) {
-    SGP_REQUIRE(X && dz && dw, "sgp_grouped_linear_wgrad_f32: null pointer");
-    SGP_REQUIRE((step == nullptr) == (node == nullptr), "sgp_grouped_linear_wgrad_f32: step and node go together");
-    SGP_REQUIRE(n_rows >= 0 && groups > 0 && ic > 0 && oc > 0, "sgp_grouped_linear_wgrad_f32: bad size");
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(dw, 0, (size_t)groups * oc * ic * sizeof(float), s);
-    if (e != hipSuccess) return sgp::fail((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
-    if (n_rows == 0) return 0;
-    WgArgs a;
-    a.x = X; a.xrs = x_row_stride; a.xbs = x_batch_stride; a.step = step; a.node = node;
-    a.dz = dz; a.dw = dw; a.n_rows = n_rows; a.groups = groups; a.ic = ic; a.oc = oc;
-    const long long tiles = (long long)groups * ((ic + 15) / 16) * ((oc + 15) / 16);
-    SGP_REQUIRE(tiles < (1ll << 31), "sgp_grouped_linear_wgrad_f32: too many tiles");
-    int32_t rps, ny;
-    sgp_grouped_linear_wgrad_form(n_rows, groups, ic, oc, &rps, &ny);    // sizes checked above
-    a.rows_per_slice = rps;
-    SGP_REQUIRE(ny <= 65535, "sgp_grouped_linear_wgrad_f32: too many row slices");
-    hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)tiles, (unsigned)ny), dim3(64), 0, s, a);
-    return sgp::check_launch("grouped_linear_wgrad");
+    return launch_wgrad<0>(X, x_row_stride, x_batch_stride, step, node, dz, dw, n_rows, groups, ic, oc, stream);
+}
+
+int sgp_grouped_linear_wgrad_16(const void* X, int32_t fmt, int64_t x_row_stride, int64_t x_batch_stride,
+                                const int32_t* step, const int32_t* node,
+                                const float* dz, float* dw,
+                                int32_t n_rows, int32_t groups, int32_t ic, int32_t oc,
+                                sgp_stream_t stream) {
+    SGP_REQUIRE(fmt == SGP_STORE_BF16 || fmt == SGP_STORE_F16,
+                "sgp_grouped_linear_wgrad_16: fmt must be SGP_STORE_BF16 or SGP_STORE_F16");
+    if (fmt == SGP_STORE_BF16)
+        return launch_wgrad<SGP_STORE_BF16>(X, x_row_stride, x_batch_stride, step, node, dz, dw, n_rows, groups, ic, oc, stream);
+    return launch_wgrad<SGP_STORE_F16>(X, x_row_stride, x_batch_stride, step, node, dz, dw, n_rows, groups, ic, oc, stream);
 }
 
 }  // extern "C"

@@ -1293,12 +1293,18 @@ def grouped_linear_pack(weight, groups):
 
 
 def _gl_rows(x2, step_index, node_index, source):
+    """Row operands of the grouped layer and ``fmt``: None for a float32 source (the ``_f32`` entries), the
+    ``SGP_STORE_*`` code of a bfloat16 / float16 one (the ``_16`` entries, strides in 16-bit elements)."""
+    rows = source if source is not None else x2
+    if rows.dtype != torch.float32 and rows.dtype not in STORE_CODES:
+        raise ValueError(f"grouped_linear: rows must be float32, bfloat16 or float16, got {rows.dtype}")
+    fmt = STORE_CODES.get(rows.dtype)
     if source is not None:
-        xp, xrs, xbs = _view3(source, "source")
-        return xp, xrs, xbs, node_index.numel(), step_index.data_ptr(), node_index.data_ptr(), source.device
+        xp, xrs, xbs = _view3(source, "source", source.dtype)
+        return xp, xrs, xbs, node_index.numel(), step_index.data_ptr(), node_index.data_ptr(), source.device, fmt
     if x2.dim() != 2 or x2.stride(1) != 1:
         raise ValueError("grouped_linear: rows must be a 2-D view with unit feature stride")
-    return x2.data_ptr(), x2.stride(0), 0, x2.shape[0], None, None, x2.device
+    return x2.data_ptr(), x2.stride(0), 0, x2.shape[0], None, None, x2.device, fmt
 
 
 @_on_device
@@ -1306,15 +1312,19 @@ def grouped_linear(x2, packed, bias, groups, ic, oc, activation, step_index=None
                    source=None, want_pre=False, dropout_p=0., seed=0):
     """rows [K, groups*ic] -> [K, groups*oc]; with (step_index, node_index) the rows are gathered
     from ``source[T, N, groups*ic]`` instead of being read from ``x2``.  ``want_pre``: also return the
-    pre-activation values (for the backward pass); ``dropout_p`` / ``seed``: Philox dropout mask."""
+    pre-activation values (for the backward pass); ``dropout_p`` / ``seed``: Philox dropout mask.  Rows (``x2`` or
+    ``source``) may be bfloat16 / float16 -- the 16-bit embedding store: ``sgp_grouped_linear_fwd_16`` widens them in
+    registers, bit-equal to this call on ``rows.float()``; the result is float32 either way."""
     lib = require_gpu()
-    xp, xrs, xbs, K, sp, np_, dev = _gl_rows(x2, step_index, node_index, source)
+    xp, xrs, xbs, K, sp, np_, dev, fmt = _gl_rows(x2, step_index, node_index, source)
     out = torch.empty(K, groups * oc, dtype=torch.float32, device=dev)
     pre = torch.empty(K, groups * oc, dtype=torch.float32, device=dev) if want_pre else None
-    _check(lib.sgp_grouped_linear_fwd_f32(xp, xrs, xbs, sp, np_, packed.data_ptr(), bias.data_ptr(),
-                                          GL_ACT_CODES[activation], out.data_ptr(), out.stride(0),
-                                          pre.data_ptr() if want_pre else None, float(dropout_p), int(seed),
-                                          K, groups, ic, oc, _stream(out)), "sgp_grouped_linear_fwd_f32")
+    rest = (sp, np_, packed.data_ptr(), bias.data_ptr(), GL_ACT_CODES[activation], out.data_ptr(), out.stride(0),
+            pre.data_ptr() if want_pre else None, float(dropout_p), int(seed), K, groups, ic, oc, _stream(out))
+    if fmt is None:
+        _check(lib.sgp_grouped_linear_fwd_f32(xp, xrs, xbs, *rest), "sgp_grouped_linear_fwd_f32")
+    else:
+        _check(lib.sgp_grouped_linear_fwd_16(xp, fmt, xrs, xbs, *rest), "sgp_grouped_linear_fwd_16")
     return (out, pre) if want_pre else out
 
 
@@ -1348,9 +1358,10 @@ def grouped_linear_transpose(weight, groups):
 
 @_on_device
 def grouped_linear_wgrad(x2, dz, groups, ic, oc, step_index=None, node_index=None, source=None):
-    """dW[groups*oc, ic] = sum over rows of dz[row, g*oc + o] * x[row, g*ic + i]."""
+    """dW[groups*oc, ic] = sum over rows of dz[row, g*oc + o] * x[row, g*ic + i]; bfloat16 / float16 rows go to
+    ``sgp_grouped_linear_wgrad_16`` (widened in registers, dW float32)."""
     lib = require_gpu()
-    xp, xrs, xbs, K, sp, np_, dev = _gl_rows(x2, step_index, node_index, source)
+    xp, xrs, xbs, K, sp, np_, dev, fmt = _gl_rows(x2, step_index, node_index, source)
     if dz.dim() != 2 or dz.dtype != torch.float32 or not dz.is_cuda or not dz.is_contiguous() \
             or tuple(dz.shape) != (K, groups * oc):
         raise ValueError(f"dz: expected a contiguous float32 CUDA tensor [{K}, {groups * oc}], got "
@@ -1358,8 +1369,11 @@ def grouped_linear_wgrad(x2, dz, groups, ic, oc, step_index=None, node_index=Non
     if K == 0:                                                          # (tensors without elements have no address to hand over)
         return torch.zeros(groups * oc, ic, dtype=torch.float32, device=dev)
     dw = torch.empty(groups * oc, ic, dtype=torch.float32, device=dev)
-    _check(lib.sgp_grouped_linear_wgrad_f32(xp, xrs, xbs, sp, np_, dz.data_ptr(), dw.data_ptr(),
-                                            K, groups, ic, oc, _stream(dw)), "sgp_grouped_linear_wgrad_f32")
+    rest = (sp, np_, dz.data_ptr(), dw.data_ptr(), K, groups, ic, oc, _stream(dw))
+    if fmt is None:
+        _check(lib.sgp_grouped_linear_wgrad_f32(xp, xrs, xbs, *rest), "sgp_grouped_linear_wgrad_f32")
+    else:
+        _check(lib.sgp_grouped_linear_wgrad_16(xp, fmt, xrs, xbs, *rest), "sgp_grouped_linear_wgrad_16")
     return dw
 
 
@@ -1369,6 +1383,16 @@ def grouped_linear_form(ic, oc, x_row_stride, x_batch_stride=0, aligned=True):
     jtc, xvec = c_i32(0), c_i32(0)
     _check(load().sgp_grouped_linear_form(int(ic), int(oc), int(x_row_stride), int(x_batch_stride), int(bool(aligned)),
                                           ctypes.addressof(jtc), ctypes.addressof(xvec)), "sgp_grouped_linear_form")
+    return jtc.value, xvec.value
+
+
+def grouped_linear_form_16(ic, oc, x_row_stride, x_batch_stride=0, aligned=True):
+    """``grouped_linear_form`` for a bfloat16 / float16 source (``sgp_grouped_linear_form_16``, host only): strides in
+    16-bit elements, ``aligned`` = the base lies on an 8-byte boundary; 1 = one 8-byte load per k-block, 0 = one element
+    at a time."""
+    jtc, xvec = c_i32(0), c_i32(0)
+    _check(load().sgp_grouped_linear_form_16(int(ic), int(oc), int(x_row_stride), int(x_batch_stride), int(bool(aligned)),
+                                             ctypes.addressof(jtc), ctypes.addressof(xvec)), "sgp_grouped_linear_form_16")
     return jtc.value, xvec.value
 
 

@@ -34,7 +34,8 @@ from ..encoders._args import opt_list, str_to_bool
 class _GroupedLinearFn(torch.autograd.Function):
     """y = dropout(act(grouped_linear(rows))) with rows either ``x2[K, groups*ic]`` or gathered from
     ``source[step, node]``; gradients for x2 (not for a gathered source: the embedding is data),
-    weight and bias."""
+    weight and bias.  A bfloat16 / float16 source is saved as it is and read again by the 16-bit weight-gradient
+    kernel."""
 
     @staticmethod
     def forward(ctx, x2, weight, bias, source, step, node, groups, activation, p, seed, cached):
@@ -112,7 +113,8 @@ class SGPInputEncoder(nn.Module):
         if x.dim() != 3 or x.shape[-1] != self.input_size:
             raise ValueError(f"expected [b, n, {self.input_size}], got {tuple(x.shape)}")
         x, on_cpu = hip.to_gpu(x)
-        x = x.float()
+        if x.dtype not in hip.STORE_CODES or x.requires_grad:                # (a 16-bit batch goes to the kernel as it is)
+            x = x.float()
         rows = x.reshape(-1, self.input_size)
         if rows.stride(1) != 1:
             rows = rows.contiguous()
@@ -141,10 +143,14 @@ class SGPInputEncoder(nn.Module):
 
     def forward_sampled(self, embedding, step_index, node_index):
         """Rows ``embedding[step_index[k], node_index[k], :]`` -> [K, 1, out_channels] without
-        materialising the gathered batch (f1 + f4 in one launch)."""
+        materialising the gathered batch (f1 + f4 in one launch).  The embedding is float32, or the 16-bit store
+        (bfloat16 / float16): widened in registers, the result equals that of ``embedding.float()``
+        bit for bit and no float32 copy of it is made, forward or backward."""
         hip.require_gpu()
         if embedding.dim() != 3 or embedding.shape[-1] != self.input_size or not embedding.is_cuda:
             raise ValueError("embedding must be a CUDA tensor [T, N, input_size]")
+        if embedding.dtype != torch.float32 and embedding.dtype not in hip.STORE_CODES:
+            raise ValueError(f"embedding must be float32, bfloat16 or float16, got {embedding.dtype}")
         st = step_index.to(embedding.device, torch.int32)
         nd = node_index.to(embedding.device, torch.int32)
         if self._needs_graph():
@@ -261,7 +267,9 @@ class SGPModel(nn.Module):
     def forward_sampled(self, embedding, step_index, node_index, u=None):
         """IID training (``sgp_amd.datasets.IIDSampler``): rows ``embedding[step_index[k], node_index[k]]`` go through
         the fused gather of the input layer, and the same ``node_index`` feeds the positional encoding -> the output of
-        ``forward(embedding[step_index, node_index][:, None, None], u, node_index[:, None])``: [K, horizon, 1, out]."""
+        ``forward(embedding[step_index, node_index][:, None, None], u, node_index[:, None])``: [K, horizon, 1, out].
+        ``embedding`` may be the 16-bit store (bfloat16 / float16): the grouped input layer reads it in place; the fully
+        connected one gathers its K rows into a float32 batch.  Neither makes a float32 copy of the table."""
         hip.require_gpu()
         if embedding.dim() != 3 or not embedding.is_cuda or embedding.shape[-1] != self.input_size:
             raise ValueError(f"embedding must be a CUDA tensor [T, N, {self.input_size}]")
@@ -271,7 +279,11 @@ class SGPModel(nn.Module):
         K = node_index.numel()
         if step_index.numel() != K:
             raise ValueError("step_index and node_index must have the same number of elements")
-        if self.fully_connected:
+        if self.fully_connected and embedding.dtype in hip.STORE_CODES:
+            # a 16-bit embedding is never widened as a whole: its K rows are gathered (and widened) into a float32 batch
+            rows = hip.gather_rows(embedding.detach(), step_index.to(torch.int32), node_index.to(torch.int32))
+            h = self._fc_input(rows, None, K)
+        elif self.fully_connected:
             F = embedding.shape[2]
             src = (step_index.to(torch.int64) * N + node_index.to(torch.int64)).to(torch.int32)
             table = embedding.detach().float().reshape(T * N, F)
