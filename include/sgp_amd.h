@@ -931,6 +931,50 @@ int sgp_masked_loss_bwd_f32(const float* y_hat, const float* y, const uint8_t* m
                             int64_t row, int32_t kind, int32_t at, int32_t mask_nans, const float* grad_out,
                             const double* count, float* grad, sgp_stream_t stream);
 
+/* The loss and the metrics on the ROOT NODES of a sampled batch.  y_hat is contiguous [batch, horizon, nodes_all,
+ * channels] (the model's output on every node of the subgraph); y and mask are [batch, horizon, roots, channels] and
+ * root j is node target_nodes[j] of y_hat (int32 or int64, index_bytes = 4 or 8, device).  The forward entries walk the
+ * units of sgp_masked_loss_f32 / sgp_masked_metrics_f32 over the sliced index space and add the same partials in the
+ * same order: loss, count and state are bit-equal to those entries on y_hat[..., target_nodes, :].contiguous().
+ * err (int32, device, persistent: the caller zeroes it, the kernels only OR into it): bit 0 an id outside
+ * [0, nodes_all) -- compared (unsigned) before it indexes anything; such an element contributes nothing -- bit 1 a
+ * node named twice.
+ *
+ * sgp_target_nodes_table: inv[nodes_all] (int32) with inv[target_nodes[j]] = j and -1 elsewhere (a memset and one
+ * launch; a repeated node is seen by the integer atomicMax that writes the table and keeps its larger j).
+ * sgp_masked_loss_nodes_bwd_f32: the FULL gradient [batch, horizon, nodes_all, channels] in one launch -- row n with
+ * inv[n] = j >= 0 gets what sgp_masked_loss_bwd_f32 writes for sliced row j, every other row +0; every element is
+ * written exactly once (no memset before it, no atomics), 16 bytes per lane when grad is 16-byte aligned.
+ * sgp_masked_metrics_nodes_f32: scale / bias are addressed by the ROOT position j (element (j, c) at
+ * j * sc_node_stride + c): the sampler slices the target's scaler with the roots.
+ *   replaces y_hat[..., batch.target_nodes, :] and the loss_fn / metrics.update calls on it, and the zero fill +
+ *   index_put of its backward (lib/predictors/subgraph_predictor.py:14-15,25,28; 42-43,53,56; 66-67,70,73) */
+int sgp_target_nodes_table(const void* target_nodes, int32_t index_bytes, int64_t roots, int64_t nodes_all,
+                           int32_t* inv, int32_t* err, sgp_stream_t stream);
+int sgp_masked_loss_nodes_f32(const float* y_hat, const float* y, const uint8_t* mask, const void* target_nodes,
+                              int32_t index_bytes, int64_t batch, int32_t horizon, int64_t nodes_all, int64_t roots,
+                              int32_t channels, int32_t kind, int32_t at, int32_t mask_nans, int32_t* err, double* work,
+                              int64_t work_doubles, float* loss, double* count, sgp_stream_t stream);
+int sgp_masked_loss_nodes_bwd_f32(const float* y_hat, const float* y, const uint8_t* mask, const int32_t* inv,
+                                  int64_t batch, int32_t horizon, int64_t nodes_all, int64_t roots, int32_t channels,
+                                  int32_t kind, int32_t at, int32_t mask_nans, const float* grad_out,
+                                  const double* count, float* grad, sgp_stream_t stream);
+int sgp_masked_metrics_nodes_f32(const float* y_hat, const float* y, const uint8_t* mask, const void* target_nodes,
+                                 int32_t index_bytes, int64_t batch, int32_t horizon, int64_t nodes_all, int64_t roots,
+                                 int32_t channels, const float* scale, const float* bias, int64_t sc_node_stride,
+                                 int32_t mask_nans, int32_t mask_inf, int32_t* err, double* work, int64_t work_doubles,
+                                 double* state, sgp_stream_t stream);
+/* The launch regime of the four entries above -- a host-only query computed by the functions the entries launch with.
+ * The workspaces are those of sgp_masked_loss_workspace_doubles(batch, horizon, roots * channels, at) and
+ * sgp_masked_metrics_workspace_doubles(batch, horizon, roots, channels).  out[7] (int64):
+ *   0: units (2048 sliced elements each) of the loss -- over the whole sliced tensor, or over step `at`
+ *   1: units per horizon step of the metrics
+ *   2: workgroups of the backward (at most 2048)   3: its grid-stride trips (the most any thread makes)
+ *   4: elements per lane of the backward: 4 (grad_aligned16 and at least 4 elements), else 1
+ *   5: 1 = the int64 index kernels, 0 = int32   6: workgroups of the table launch */
+int sgp_masked_nodes_form(int64_t batch, int32_t horizon, int64_t nodes_all, int64_t roots, int32_t channels,
+                          int32_t at, int32_t index_bytes, int32_t grad_aligned16, int64_t* out);
+
 
 /* ------------------------------------------------ Gated graph network: edges -----
  * The per-edge MLP, gate and sum of a GatedGraphNetwork layer (gated_gn.hip), forward and backward, for the same

@@ -15,7 +15,7 @@ from .scalers import MinMaxScaler, RobustScaler, Scaler, StandardScaler
 from .metrics import (MaskedMAE, MaskedMAPE, MaskedMRE, MaskedMSE, MetricSet, masked_loss, masked_mae, masked_mape,
                       masked_mse)
 from .optim import FusedAdam
-from .predictors import Predictor
+from .predictors import Predictor, SubgraphPredictor
 from .sgp_preprocessing import (preprocess_adj, preprocess_dataset, reservoir_preprocessing_,
                                 sgp_spatial_embedding, sgp_spatial_support)
 from .utils import encode_dataset, self_normalizing_activation

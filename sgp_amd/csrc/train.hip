@@ -251,8 +251,151 @@ __global__ void masked_loss_bwd_kernel(const float* __restrict__ yh, const float
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the same, on root nodes
+// y_hat is contiguous [B, H, nodes_all, C]; y and mask are [B, H, roots, C] and root j sits at node tn[j] of y_hat.
+// The unit walk is the one above over the SLICED index space (R = roots * C), so thread, order and partials are those
+// of the kernels above on y_hat[..., tn, :].contiguous(); only the address of the prediction differs.
+enum { TN_ERR_RANGE = 1, TN_ERR_REPEAT = 2 };
+
+struct Nodes { long long nodes_all; int channels; };
+
+// address in y_hat of sliced element `a` = (bh * roots + j) * C + c; false (and bit 0 of err) when tn[j] is no node
+template <class I>
+__device__ __forceinline__ bool node_addr(long long a, long long R, const I* __restrict__ tn, const Nodes& nd,
+                                          int* __restrict__ err, long long& ah) {
+    long long bh, r;
+    if (((unsigned long long)a | (unsigned long long)R) >> 32) { bh = a / R; r = a - bh * R; }
+    else { const unsigned q = (unsigned)a / (unsigned)R; bh = q; r = (unsigned)a - q * (unsigned)R; }
+    const long long j = r / nd.channels, c = r - j * nd.channels;
+    const I id = tn[j];
+    if (!sgp::in_range(id, nd.nodes_all)) { atomicOr(err, TN_ERR_RANGE); return false; }
+    ah = (bh * nd.nodes_all + (long long)id) * nd.channels + c;
+    return true;
+}
+
+// inv[tn[j]] = j over a table the entry has filled with -1; atomicMax keeps the larger j of a node named twice
+template <class I>
+__global__ __launch_bounds__(TR_THREADS) void target_nodes_table_kernel(const I* __restrict__ tn, long long roots,
+                                                                        long long nodes_all, int* __restrict__ inv,
+                                                                        int* __restrict__ err) {
+    for (long long j = blockIdx.x * (long long)TR_THREADS + threadIdx.x; j < roots; j += (long long)gridDim.x * TR_THREADS) {
+        const I id = tn[j];
+        if (!sgp::in_range(id, nodes_all)) { atomicOr(err, TN_ERR_RANGE); continue; }
+        if (atomicMax(inv + (long long)id, (int)j) != -1) atomicOr(err, TN_ERR_REPEAT);
+    }
+}
+
+template <class I>
+__global__ __launch_bounds__(TR_THREADS) void masked_metrics_nodes_kernel(const float* __restrict__ yh, const float* __restrict__ y,
+                                                                          const unsigned char* __restrict__ mask,
+                                                                          const I* __restrict__ tn, Nodes nd, long long J,
+                                                                          long long H, long long R, long long nseg, Transform tr,
+                                                                          int mask_nans, int mask_inf, int* __restrict__ err,
+                                                                          double* __restrict__ partial) {
+    __shared__ double lds[MET_COLS * TR_WAVES];
+    const long long u = blockIdx.x, h = u / nseg, seg = u - h * nseg;
+    const long long j1 = (seg + 1) * MET_SEG < J ? (seg + 1) * MET_SEG : J;
+    double s[MET_COLS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long long j = seg * MET_SEG + threadIdx.x; j < j1; j += TR_THREADS) {
+        long long r, ah;
+        const long long a = addr_of(j, R, H, h, r);
+        if (!node_addr(a, R, tn, nd, err, ah)) continue;
+        const float t = y[a], d = inverse_transform(yh[ah], tr, r) - t;        // r / channels is the ROOT position
+        const bool m = mask ? mask[a] != 0 : true;
+        const float ad = fabsf(d);
+        if (counts(m, ad, mask_nans, mask_inf)) { s[0] += (double)ad; s[1] += 1.0; s[2] += (double)(d * d); s[5] += (double)t; }
+        const float q = fabsf(d / t);
+        if (counts(m, q, mask_nans, 1)) { s[3] += (double)q; s[4] += 1.0; }
+    }
+    wg_sum_waves<TR_THREADS>(s, lds);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int k = 0; k < MET_COLS; ++k) partial[u * MET_COLS + k] = s[k];
+}
+
+template <class I>
+__global__ __launch_bounds__(TR_THREADS) void masked_loss_nodes_kernel(const float* __restrict__ yh, const float* __restrict__ y,
+                                                                       const unsigned char* __restrict__ mask,
+                                                                       const I* __restrict__ tn, Nodes nd, long long J,
+                                                                       long long H, long long R, long long h, long long Rn,
+                                                                       int kind, int mask_nans, int* __restrict__ err,
+                                                                       double* __restrict__ partial) {
+    __shared__ double lds[2 * TR_WAVES];
+    const long long seg = blockIdx.x;
+    const long long j1 = (seg + 1) * MET_SEG < J ? (seg + 1) * MET_SEG : J;
+    double s[2] = {0.0, 0.0};
+    for (long long j = seg * MET_SEG + threadIdx.x; j < j1; j += TR_THREADS) {
+        long long r, ah;
+        const long long a = addr_of(j, R, H, h, r);                             // (H, R, h) as in sgp_masked_loss_f32
+        if (!node_addr(a, Rn, tn, nd, err, ah)) continue;                       // Rn = roots * C whatever `at` is
+        const float t = y[a], val = loss_value(kind, yh[ah] - t, t);
+        if (counts(mask ? mask[a] != 0 : true, val, mask_nans, kind == LOSS_MAPE)) { s[0] += (double)val; s[1] += 1.0; }
+    }
+    wg_sum_waves<TR_THREADS>(s, lds);
+    if (threadIdx.x == 0) { partial[2 * seg] = s[0]; partial[2 * seg + 1] = s[1]; }
+}
+
+// One element of the full gradient: row `n` of block bh = b * H + h, channel c, at flat address e of y_hat.
+__device__ __forceinline__ float loss_nodes_grad(const float* __restrict__ yh, const float* __restrict__ y,
+                                                 const unsigned char* __restrict__ mask, const int* __restrict__ inv,
+                                                 long long e, long long bh, long long n, long long c, long long roots,
+                                                 int channels, long long H, long long at, int kind, int mask_nans,
+                                                 float scale) {
+    const int j = inv[n];
+    if (!sgp::in_range(j, roots) || !(at < 0 || bh % H == at)) return 0.f;
+    const long long a = (bh * roots + j) * channels + c;
+    const float t = y[a], d = yh[e] - t;
+    if (!counts(mask ? mask[a] != 0 : true, loss_value(kind, d, t), mask_nans, kind == LOSS_MAPE)) return 0.f;
+    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f * d);
+    return kind == LOSS_MAE ? scale * sgn : (kind == LOSS_MSE ? scale * 2.f * d : scale * sgn / fabsf(t));
+}
+
+// The whole gradient [B, H, nodes_all, C] in one pass: thread -> V consecutive elements (V = 4: one 16-byte store),
+// every element written once, rows outside tn as +0.
+template <int V>
+__global__ __launch_bounds__(TR_THREADS) void masked_loss_nodes_bwd_kernel(const float* __restrict__ yh, const float* __restrict__ y,
+                                                                           const unsigned char* __restrict__ mask,
+                                                                           const int* __restrict__ inv, long long n_all,
+                                                                           long long nodes_all, long long roots, int channels,
+                                                                           long long H, long long at, int kind, int mask_nans,
+                                                                           const float* __restrict__ gout,
+                                                                           const double* __restrict__ count,
+                                                                           float* __restrict__ grad) {
+    const float scale = gout[0] / (float)count[0];
+    const long long stride = (long long)gridDim.x * TR_THREADS * V;
+    for (long long e0 = (blockIdx.x * (long long)TR_THREADS + threadIdx.x) * V; e0 < n_all; e0 += stride) {
+        const long long row = e0 / channels;
+        long long c = e0 - row * channels, bh = row / nodes_all, n = row - bh * nodes_all;
+        float g[V];
+#pragma unroll
+        for (int q = 0; q < V; ++q) {
+            g[q] = e0 + q < n_all ? loss_nodes_grad(yh, y, mask, inv, e0 + q, bh, n, c, roots, channels, H, at, kind,
+                                                    mask_nans, scale) : 0.f;
+            if (++c == channels) { c = 0; if (++n == nodes_all) { n = 0; ++bh; } }
+        }
+        if (V == 4 && e0 + 4 <= n_all) { sgp::st4(grad + e0, f32x4{g[0], g[1], g[2], g[3]}); continue; }
+#pragma unroll
+        for (int q = 0; q < V; ++q)
+            if (e0 + q < n_all) grad[e0 + q] = g[q];
+    }
+}
+
 long long units_of(long long J) { return J > 0 ? (J + MET_SEG - 1) / MET_SEG : 0; }
 constexpr long long MAX_GRID = 2147483647LL;
+
+// ---- launch arithmetic of the root-node entries: the entries and sgp_masked_nodes_form both go through these
+constexpr long long NODES_BWD_CAP = 2048;       // workgroups of the backward: 8 of 256 threads on each of 256 CUs
+long long nodes_loss_J(long long batch, long long horizon, long long roots, long long channels, int at) {
+    return at < 0 ? batch * horizon * roots * channels : batch * roots * channels;
+}
+int nodes_bwd_vec(long long n_all, bool aligned16) { return aligned16 && n_all >= 4 ? 4 : 1; }
+unsigned nodes_bwd_grid(long long n_all, int vec) { return sgp::grid_for(n_all, (long long)TR_THREADS * vec, NODES_BWD_CAP); }
+long long nodes_bwd_trips(long long n_all, int vec) {
+    const long long per = (long long)nodes_bwd_grid(n_all, vec) * TR_THREADS * vec;
+    return n_all > 0 ? (n_all + per - 1) / per : 0;
+}
+unsigned nodes_table_grid(long long roots) { return sgp::grid_for(roots, TR_THREADS, 1024); }
+bool index_ok(int index_bytes) { return index_bytes == 4 || index_bytes == 8; }
 
 }  // namespace
 
@@ -371,6 +514,132 @@ int sgp_masked_loss_bwd_f32(const float* y_hat, const float* y, const uint8_t* m
                        y_hat, y, mask, n, (long long)horizon, (long long)row, (long long)at, kind, mask_nans, grad_out,
                        count, grad);
     return sgp::check_launch("masked_loss_bwd");
+}
+
+int sgp_masked_nodes_form(int64_t batch, int32_t horizon, int64_t nodes_all, int64_t roots, int32_t channels,
+                          int32_t at, int32_t index_bytes, int32_t grad_aligned16, int64_t* out) {
+    SGP_REQUIRE(out, "sgp_masked_nodes_form: null pointer");
+    SGP_REQUIRE(batch >= 0 && horizon >= 0 && nodes_all >= 0 && roots >= 0 && channels >= 0,
+                "sgp_masked_nodes_form: bad size");
+    SGP_REQUIRE(at >= -1 && (at < 0 || at < horizon), "sgp_masked_nodes_form: at outside the horizon");
+    SGP_REQUIRE(index_ok(index_bytes), "sgp_masked_nodes_form: index_bytes is 4 (int32) or 8 (int64)");
+    const long long n_all = batch * horizon * nodes_all * channels;
+    const int vec = nodes_bwd_vec(n_all, grad_aligned16 != 0);
+    out[0] = units_of(nodes_loss_J(batch, horizon, roots, channels, at));
+    out[1] = units_of(batch * roots * channels);
+    out[2] = n_all > 0 ? (long long)nodes_bwd_grid(n_all, vec) : 0;
+    out[3] = nodes_bwd_trips(n_all, vec);
+    out[4] = vec;
+    out[5] = index_bytes == 8;
+    out[6] = roots > 0 ? (long long)nodes_table_grid(roots) : 0;
+    return 0;
+}
+
+int sgp_target_nodes_table(const void* target_nodes, int32_t index_bytes, int64_t roots, int64_t nodes_all,
+                           int32_t* inv, int32_t* err, sgp_stream_t stream) {
+    SGP_REQUIRE(inv && err && (target_nodes || roots == 0), "sgp_target_nodes_table: null pointer");
+    SGP_REQUIRE(roots >= 0 && nodes_all > 0 && roots <= 2147483647LL && nodes_all <= 2147483647LL,
+                "sgp_target_nodes_table: bad size");
+    SGP_REQUIRE(index_ok(index_bytes), "sgp_target_nodes_table: index_bytes is 4 (int32) or 8 (int64)");
+    hipError_t e = hipMemsetAsync(inv, 0xFF, (size_t)nodes_all * sizeof(int32_t), (hipStream_t)stream);   // every entry -1
+    if (e != hipSuccess) return sgp::fail((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (roots == 0) return 0;
+    const dim3 grid(nodes_table_grid(roots)), block(TR_THREADS);
+    if (index_bytes == 8)
+        hipLaunchKernelGGL(target_nodes_table_kernel<long long>, grid, block, 0, (hipStream_t)stream,
+                           (const long long*)target_nodes, (long long)roots, (long long)nodes_all, inv, err);
+    else
+        hipLaunchKernelGGL(target_nodes_table_kernel<int>, grid, block, 0, (hipStream_t)stream,
+                           (const int*)target_nodes, (long long)roots, (long long)nodes_all, inv, err);
+    return sgp::check_launch("target_nodes_table");
+}
+
+int sgp_masked_metrics_nodes_f32(const float* y_hat, const float* y, const uint8_t* mask, const void* target_nodes,
+                                 int32_t index_bytes, int64_t batch, int32_t horizon, int64_t nodes_all, int64_t roots,
+                                 int32_t channels, const float* scale, const float* bias, int64_t sc_node_stride,
+                                 int32_t mask_nans, int32_t mask_inf, int32_t* err, double* work, int64_t work_doubles,
+                                 double* state, sgp_stream_t stream) {
+    SGP_REQUIRE(y_hat && y && target_nodes && err && work && state, "sgp_masked_metrics_nodes_f32: null pointer");
+    SGP_REQUIRE(batch >= 0 && horizon >= 0 && nodes_all >= 0 && roots >= 0 && channels >= 0 && sc_node_stride >= 0,
+                "sgp_masked_metrics_nodes_f32: bad size");
+    SGP_REQUIRE(index_ok(index_bytes), "sgp_masked_metrics_nodes_f32: index_bytes is 4 (int32) or 8 (int64)");
+    SGP_REQUIRE((scale == nullptr) == (bias == nullptr), "sgp_masked_metrics_nodes_f32: scale and bias come together");
+    SGP_REQUIRE((mask_nans == 0 || mask_nans == 1) && (mask_inf == 0 || mask_inf == 1),
+                "sgp_masked_metrics_nodes_f32: mask_nans / mask_inf are 0 or 1");
+    const long long R = roots * channels, J = batch * R, nseg = units_of(J);
+    if (nseg == 0 || horizon == 0) return 0;
+    SGP_REQUIRE(nseg * horizon <= MAX_GRID, "sgp_masked_metrics_nodes_f32: too many units");
+    SGP_REQUIRE(work_doubles >= nseg * horizon * MET_COLS, "sgp_masked_metrics_nodes_f32: workspace too small");
+    Transform tr = {scale, bias, sc_node_stride, channels};
+    const Nodes nd = {nodes_all, channels};
+    const dim3 grid((unsigned)(nseg * horizon)), block(TR_THREADS);
+    if (index_bytes == 8)
+        hipLaunchKernelGGL(masked_metrics_nodes_kernel<long long>, grid, block, 0, (hipStream_t)stream, y_hat, y, mask,
+                           (const long long*)target_nodes, nd, J, (long long)horizon, R, nseg, tr, mask_nans, mask_inf, err,
+                           work);
+    else
+        hipLaunchKernelGGL(masked_metrics_nodes_kernel<int>, grid, block, 0, (hipStream_t)stream, y_hat, y, mask,
+                           (const int*)target_nodes, nd, J, (long long)horizon, R, nseg, tr, mask_nans, mask_inf, err, work);
+    if (int rc = sgp::check_launch("masked_metrics_nodes")) return rc;
+    hipLaunchKernelGGL(masked_metrics_final_kernel, dim3((unsigned)horizon), dim3(TR_THREADS), 0, (hipStream_t)stream,
+                       (const double*)work, nseg, state);
+    return sgp::check_launch("masked_metrics_final");
+}
+
+int sgp_masked_loss_nodes_f32(const float* y_hat, const float* y, const uint8_t* mask, const void* target_nodes,
+                              int32_t index_bytes, int64_t batch, int32_t horizon, int64_t nodes_all, int64_t roots,
+                              int32_t channels, int32_t kind, int32_t at, int32_t mask_nans, int32_t* err, double* work,
+                              int64_t work_doubles, float* loss, double* count, sgp_stream_t stream) {
+    SGP_REQUIRE(y_hat && y && target_nodes && err && work && loss && count, "sgp_masked_loss_nodes_f32: null pointer");
+    SGP_REQUIRE(batch >= 0 && horizon >= 0 && nodes_all >= 0 && roots >= 0 && channels >= 0,
+                "sgp_masked_loss_nodes_f32: bad size");
+    SGP_REQUIRE(index_ok(index_bytes), "sgp_masked_loss_nodes_f32: index_bytes is 4 (int32) or 8 (int64)");
+    SGP_REQUIRE(kind >= LOSS_MAE && kind <= LOSS_MAPE, "sgp_masked_loss_nodes_f32: kind is 0 (mae), 1 (mse) or 2 (mape)");
+    SGP_REQUIRE(at >= -1 && (at < 0 || at < horizon), "sgp_masked_loss_nodes_f32: at outside the horizon");
+    SGP_REQUIRE(mask_nans == 0 || mask_nans == 1, "sgp_masked_loss_nodes_f32: mask_nans is 0 or 1");
+    const long long Rn = roots * channels, J = nodes_loss_J(batch, horizon, roots, channels, at), nseg = units_of(J);
+    SGP_REQUIRE(nseg <= MAX_GRID, "sgp_masked_loss_nodes_f32: too many units");
+    SGP_REQUIRE(work_doubles >= 2 * nseg, "sgp_masked_loss_nodes_f32: workspace too small");
+    if (nseg > 0) {
+        const Nodes nd = {nodes_all, channels};
+        const dim3 grid((unsigned)nseg), block(TR_THREADS);
+        const long long H = at < 0 ? 1LL : (long long)horizon, R = at < 0 ? J : Rn, h = at < 0 ? 0LL : (long long)at;
+        if (index_bytes == 8)
+            hipLaunchKernelGGL(masked_loss_nodes_kernel<long long>, grid, block, 0, (hipStream_t)stream, y_hat, y, mask,
+                               (const long long*)target_nodes, nd, J, H, R, h, Rn, kind, mask_nans, err, work);
+        else
+            hipLaunchKernelGGL(masked_loss_nodes_kernel<int>, grid, block, 0, (hipStream_t)stream, y_hat, y, mask,
+                               (const int*)target_nodes, nd, J, H, R, h, Rn, kind, mask_nans, err, work);
+        if (int rc = sgp::check_launch("masked_loss_nodes")) return rc;
+    }
+    hipLaunchKernelGGL(masked_loss_final_kernel, dim3(1), dim3(TR_THREADS), 0, (hipStream_t)stream,
+                       (const double*)work, nseg, loss, count);
+    return sgp::check_launch("masked_loss_final");
+}
+
+int sgp_masked_loss_nodes_bwd_f32(const float* y_hat, const float* y, const uint8_t* mask, const int32_t* inv,
+                                  int64_t batch, int32_t horizon, int64_t nodes_all, int64_t roots, int32_t channels,
+                                  int32_t kind, int32_t at, int32_t mask_nans, const float* grad_out,
+                                  const double* count, float* grad, sgp_stream_t stream) {
+    SGP_REQUIRE(y_hat && inv && grad_out && count && grad && (y || roots == 0), "sgp_masked_loss_nodes_bwd_f32: null pointer");
+    SGP_REQUIRE(batch >= 0 && horizon >= 0 && nodes_all >= 0 && roots >= 0 && channels >= 0 && roots <= 2147483647LL,
+                "sgp_masked_loss_nodes_bwd_f32: bad size");
+    SGP_REQUIRE(kind >= LOSS_MAE && kind <= LOSS_MAPE, "sgp_masked_loss_nodes_bwd_f32: kind is 0 (mae), 1 (mse) or 2 (mape)");
+    SGP_REQUIRE(at >= -1 && (at < 0 || at < horizon), "sgp_masked_loss_nodes_bwd_f32: at outside the horizon");
+    SGP_REQUIRE(mask_nans == 0 || mask_nans == 1, "sgp_masked_loss_nodes_bwd_f32: mask_nans is 0 or 1");
+    const long long n_all = batch * horizon * nodes_all * channels;
+    if (n_all == 0) return 0;
+    const int vec = nodes_bwd_vec(n_all, sgp::aligned16(grad));
+    const dim3 grid(nodes_bwd_grid(n_all, vec)), block(TR_THREADS);
+    if (vec == 4)
+        hipLaunchKernelGGL(masked_loss_nodes_bwd_kernel<4>, grid, block, 0, (hipStream_t)stream, y_hat, y, mask, inv, n_all,
+                           (long long)nodes_all, (long long)roots, channels, (long long)horizon, (long long)at, kind,
+                           mask_nans, grad_out, count, grad);
+    else
+        hipLaunchKernelGGL(masked_loss_nodes_bwd_kernel<1>, grid, block, 0, (hipStream_t)stream, y_hat, y, mask, inv, n_all,
+                           (long long)nodes_all, (long long)roots, channels, (long long)horizon, (long long)at, kind,
+                           mask_nans, grad_out, count, grad);
+    return sgp::check_launch("masked_loss_nodes_bwd");
 }
 
 }  // extern "C"

@@ -1615,6 +1615,139 @@ def masked_loss_bwd(y_hat, y, mask, kind, at, mask_nans, grad_out, count):
     return grad
 
 
+# ---- the same on the root nodes of a sampled batch: y_hat [B, H, nodes_all, C], y / mask [B, H, roots, C]
+TN_ERR_RANGE, TN_ERR_REPEAT = 1, 2          # bits of the error word the root-node kernels OR into
+_NODES_FORM_KEYS = ("loss_units", "metric_units_per_step", "bwd_grid", "bwd_trips", "bwd_vec", "index64", "table_grid")
+
+
+def masked_nodes_form(batch, horizon, nodes_all, roots, channels, at=None, index_dtype=torch.int64, grad_aligned=True):
+    """The launch regime of ``masked_loss_nodes`` / ``masked_loss_nodes_bwd`` / ``masked_metrics_nodes`` /
+    ``target_nodes_table`` for these sizes, as a dict (host only: ``sgp_masked_nodes_form``)."""
+    out = (c_i64 * len(_NODES_FORM_KEYS))()
+    rc = load().sgp_masked_nodes_form(int(batch), int(horizon), int(nodes_all), int(roots), int(channels),
+                                      -1 if at is None else int(at), _index_bytes(index_dtype), int(bool(grad_aligned)),
+                                      ctypes.addressof(out))
+    if rc == SGP_EINVAL:
+        raise ValueError(f"masked_nodes_form: {load().sgp_last_error().decode()}")
+    _check(rc, "sgp_masked_nodes_form")
+    return {k: int(out[i]) for i, k in enumerate(_NODES_FORM_KEYS)}
+
+
+def _index_bytes(dtype):
+    if dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"target_nodes: int32 or int64 indices, got {dtype}")
+    return 4 if dtype == torch.int32 else 8
+
+
+def target_nodes_error(word, what="target_nodes"):
+    """Raise what a non-zero error word of the root-node kernels says: ``IndexError`` for an id outside the nodes of
+    the prediction, ``ValueError`` for a node named twice.  ``word``: the int (or the tensor: a host sync)."""
+    word = int(word)
+    if word & TN_ERR_RANGE:
+        raise IndexError(f"{what}: an index is outside the nodes of the prediction")
+    if word & TN_ERR_REPEAT:
+        raise ValueError(f"{what}: a node is named more than once")
+
+
+def _nodes_operands(y_hat, y, mask, tn, err, what):
+    """Checks of the root-node bindings -> (B, H, nodes_all, roots, C)."""
+    for name, t in (("y_hat", y_hat), ("y", y)):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 4:
+            raise ValueError(f"{what}: {name} must be a contiguous float32 CUDA tensor [B, H, nodes, C]")
+    if y_hat.shape[:2] != y.shape[:2] or y_hat.shape[3] != y.shape[3]:
+        raise ValueError(f"{what}: y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} differ outside the node axis")
+    if mask is not None and (mask.shape != y.shape or mask.dtype != torch.uint8 or not mask.is_cuda
+                             or not mask.is_contiguous()):
+        raise ValueError(f"{what}: mask must be a contiguous uint8 CUDA tensor of the shape of y")
+    if tn is not None:
+        _index_bytes(tn.dtype)
+        if tn.dim() != 1 or not tn.is_cuda or not tn.is_contiguous() or tn.numel() != y.shape[2]:
+            raise ValueError(f"{what}: target_nodes must be a contiguous CUDA vector of the {y.shape[2]} roots of y, "
+                             f"got {tuple(tn.shape)} on {tn.device}")
+    if err is not None and (err.dtype != torch.int32 or not err.is_cuda or err.numel() != 1):
+        raise ValueError(f"{what}: the error word is one int32 on the device")
+    B, H, nodes_all, C = y_hat.shape
+    return B, H, nodes_all, y.shape[2], C
+
+
+@_on_device
+def target_nodes_table(tn, nodes_all, err):
+    """int32 CUDA ``[nodes_all]``: the position of every node among ``tn``, -1 for the others; a bad ``tn`` sets
+    ``err`` (``TN_ERR_RANGE`` / ``TN_ERR_REPEAT``) and is never used as an address."""
+    lib = require_gpu()
+    if tn.dim() != 1 or not tn.is_cuda or not tn.is_contiguous():
+        raise ValueError("target_nodes_table: target_nodes must be a contiguous CUDA vector")
+    if err.dtype != torch.int32 or not err.is_cuda or err.numel() != 1:
+        raise ValueError("target_nodes_table: the error word is one int32 on the device")
+    inv = torch.empty(int(nodes_all), dtype=torch.int32, device=tn.device)
+    if int(nodes_all) > 0:
+        _check(lib.sgp_target_nodes_table(_ptr(tn) if tn.numel() else None, _index_bytes(tn.dtype), tn.numel(),
+                                          int(nodes_all), inv.data_ptr(), err.data_ptr(), _stream(tn)),
+               "sgp_target_nodes_table")
+    return inv
+
+
+@_on_device
+def masked_loss_nodes(y_hat, y, mask, tn, err, kind="mae", at=None, mask_nans=False):
+    """``masked_loss`` of ``y_hat[..., tn, :]`` against ``y`` without the slice: (loss, count), bit-equal to it."""
+    lib = require_gpu()
+    B, H, nodes_all, roots, C = _nodes_operands(y_hat, y, mask, tn, err, "masked_loss_nodes")
+    _, _, R, at = _loss_dims(y, at)
+    if not y.numel() or not nodes_all:
+        return torch.zeros((), dtype=torch.float32, device=y.device), torch.zeros(1, dtype=torch.float64, device=y.device)
+    loss = torch.empty((), dtype=torch.float32, device=y.device)
+    count = torch.empty(1, dtype=torch.float64, device=y.device)
+    work = torch.empty(max(1, lib.sgp_masked_loss_workspace_doubles(B, H, R, at)), dtype=torch.float64, device=y.device)
+    _check(lib.sgp_masked_loss_nodes_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), tn.data_ptr(), _index_bytes(tn.dtype),
+                                         B, H, nodes_all, roots, C, LOSS_KINDS[kind], at, int(bool(mask_nans)),
+                                         err.data_ptr(), work.data_ptr(), work.numel(), loss.data_ptr(), count.data_ptr(),
+                                         _stream(y)), "sgp_masked_loss_nodes_f32")
+    return loss, count
+
+
+@_on_device
+def masked_loss_nodes_bwd(y_hat, y, mask, inv, kind, at, mask_nans, grad_out, count, out=None):
+    """The full gradient ``[B, H, nodes_all, C]`` of ``masked_loss_nodes`` in one launch (``inv``: the table of
+    ``target_nodes_table``); ``out``: a float32 CUDA buffer of that shape to write into (every element is written)."""
+    lib = require_gpu()
+    B, H, nodes_all, roots, C = _nodes_operands(y_hat, y, mask, None, None, "masked_loss_nodes_bwd")
+    _, _, _, at = _loss_dims(y, at)
+    if inv.dtype != torch.int32 or not inv.is_cuda or not inv.is_contiguous() or inv.numel() != nodes_all:
+        raise ValueError(f"masked_loss_nodes_bwd: the table must be contiguous int32 CUDA [{nodes_all}]")
+    grad = torch.empty_like(y_hat) if out is None else out
+    if grad.shape != y_hat.shape or grad.dtype != torch.float32 or not grad.is_cuda or not grad.is_contiguous():
+        raise ValueError("masked_loss_nodes_bwd: out must be a contiguous float32 CUDA tensor of the shape of y_hat")
+    if not y_hat.numel():
+        return grad
+    _check(lib.sgp_masked_loss_nodes_bwd_f32(y_hat.data_ptr(), _ptr(y) if y.numel() else None, _ptr(mask), inv.data_ptr(),
+                                             B, H, nodes_all, roots, C, LOSS_KINDS[kind], at, int(bool(mask_nans)),
+                                             grad_out.data_ptr(), count.data_ptr(), grad.data_ptr(), _stream(grad)),
+           "sgp_masked_loss_nodes_bwd_f32")
+    return grad
+
+
+@_on_device
+def masked_metrics_nodes(y_hat, y, mask, tn, err, state, scale=None, bias=None, sc_node_stride=0, mask_nans=False,
+                         mask_inf=False):
+    """``masked_metrics`` of ``y_hat[..., tn, :]`` against ``y`` without the slice; ``scale`` / ``bias`` are addressed
+    by the root position (element (j, c) at ``j * sc_node_stride + c``)."""
+    lib = require_gpu()
+    B, H, nodes_all, roots, C = _nodes_operands(y_hat, y, mask, tn, err, "masked_metrics_nodes")
+    if tuple(state.shape) != (H, METRIC_COLS) or state.dtype != torch.float64 or not state.is_cuda \
+            or not state.is_contiguous():
+        raise ValueError(f"masked_metrics_nodes: state must be contiguous float64 CUDA [{H}, {METRIC_COLS}]")
+    if not y.numel() or not nodes_all:
+        return state
+    work = torch.empty(max(1, lib.sgp_masked_metrics_workspace_doubles(B, H, roots, C)), dtype=torch.float64,
+                       device=y.device)
+    _check(lib.sgp_masked_metrics_nodes_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), tn.data_ptr(),
+                                            _index_bytes(tn.dtype), B, H, nodes_all, roots, C, _ptr(scale), _ptr(bias),
+                                            int(sc_node_stride), int(bool(mask_nans)), int(bool(mask_inf)), err.data_ptr(),
+                                            work.data_ptr(), work.numel(), state.data_ptr(), _stream(y)),
+           "sgp_masked_metrics_nodes_f32")
+    return state
+
+
 # ---------------------------------------------------------------- gated graph network edges (gated_gn.hip)
 def gated_gn_supported(H, activation):
     """Whether the edge kernels cover a layer of output width ``H`` with this activation (no GPU needed)."""

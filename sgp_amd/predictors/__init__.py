@@ -1,3 +1,4 @@
 from .predictor import Predictor
+from .subgraph_predictor import SubgraphPredictor
 
-__all__ = ["Predictor"]
+__all__ = ["Predictor", "SubgraphPredictor"]
