@@ -22,6 +22,9 @@
  *       lib/datasets/iid_dataset.py:57-99 (IID (t, n) row gather of the embedding; "next" row f1)
  *   sgp_pack_rows_16, sgp_gather_rows_16
  *       the same embedding kept in bf16 / fp16 (no counterpart in the reference: lib/utils.py:24-35 holds float32)
+ *   sgp_window_gather
+ *       tsl/data/spatiotemporal_dataset.py (window / horizon indexing of a sample) and
+ *       lib/dataloader/subgraph_dataloader.py:31-34 (node slices of a batch), one launch per tensor and batch
  *   sgp_grouped_linear_f32
  *       lib/nn/models/sgp_model.py:41-52 (decoder input encoder: grouped Conv1d + activation; f4)
  *   sgp_grouped_linear_fwd_16, sgp_grouped_linear_wgrad_16
@@ -660,6 +663,44 @@ int sgp_gather_rows_16(const void* X, int64_t x_row_stride, int64_t x_batch_stri
                        const int32_t* step, const int32_t* node, int32_t n_index, int32_t fmt,
                        float* out, int64_t out_row_stride, int64_t out_batch_stride,
                        int32_t batch, int32_t feat, sgp_stream_t stream);
+
+/* ------------------------------------------------- Window gather of the data module ---
+ * window_gather.hip.  Replaces tsl/data/spatiotemporal_dataset.py's window / horizon indexing of a
+ * sample (one fancy index per item and tensor, then a collate) and lib/dataloader/subgraph_dataloader.py:31-34 (the
+ * node slice of inputs, targets and mask): ONE launch builds one registered tensor of a whole batch,
+ *
+ *   out[b, j, k, 0:feat] = T( X[start[b] + offset + lag * j, node(b, k), 0:feat] ),   b < batch, j < count, k < n_out.
+ *
+ * X: a resident [n_steps, n_nodes, feat] series, fp32 (src_fmt 0) or SGP_STORE_BF16 / SGP_STORE_F16 (widened
+ * exactly), unit feature stride, step and node strides in ELEMENTS (a slot of a wider buffer is a legal source).  A
+ * "t f" tensor is n_nodes = 1, node = NULL.  start: DEVICE int32 [batch].  (offset, count, lag) is (0, window, 1) for
+ * inputs and (window + delay, len(range(0, horizon, horizon_lag)), horizon_lag) for targets and the mask.
+ * node: NULL (all nodes, n_out = n_nodes), int32 [n_out] shared by the batch (node_batch_stride 0) or int32
+ * [batch, n_out] (node_batch_stride n_out).  out: contiguous [batch, count, n_out, feat], fp32, or bool bytes under
+ * SGP_WINDOW_MASK.
+ *
+ * T (mode): SGP_WINDOW_IDENTITY; SGP_WINDOW_SCALE, (x - bias) / scale + 5e-8 in the operations and order of
+ * sgp_scaler_apply_f32 (bit-equal to gather-then-transform), bias / scale device fp32 [param_nodes, param_feat] with
+ * param_nodes in {1, n_nodes}, param_feat in {1, feat}, indexed by the GLOBAL node id; SGP_WINDOW_MASK, x != 0.
+ *
+ * Bounds are judged in the kernel before any access: a start whose first or last row
+ * (start + offset + lag * (count - 1)) lies outside [0, n_steps) sets SGP_WINDOW_ERR_START in the caller's device word
+ * *err (an atomic or; the caller zeroes and reads it), a node id outside [0, n_nodes) sets SGP_WINDOW_ERR_NODE; the
+ * rows concerned are written as zeros and nothing is read out of range.
+ * feat % 4 == 0 (fp32) or feat % 8 == 0 (16-bit) with 16-byte aligned X and out and strides that are such multiples
+ * moves 16 source bytes per lane; everything else runs element-wise with the lanes along the nodes.  An empty shape
+ * returns 0 without a launch; a null pointer or a negative size is SGP_EINVAL. */
+#define SGP_WINDOW_IDENTITY 0
+#define SGP_WINDOW_SCALE    1
+#define SGP_WINDOW_MASK     2
+#define SGP_WINDOW_ERR_START 1
+#define SGP_WINDOW_ERR_NODE  2
+int sgp_window_gather(const void* X, int32_t src_fmt, int64_t x_step_stride, int64_t x_node_stride,
+                      int32_t n_steps, int32_t n_nodes, int32_t feat,
+                      const int32_t* start, int32_t batch, int32_t offset, int32_t count, int32_t lag,
+                      const int32_t* node, int32_t n_out, int64_t node_batch_stride,
+                      int32_t mode, const float* bias, const float* scale, int32_t param_nodes, int32_t param_feat,
+                      void* out, int32_t* err, sgp_stream_t stream);
 
 /* ------------------------------------------------- Decoder first layer ("next" row f4) ---
  * Grouped 1x1 convolution of lib/nn/models/sgp_model.py:41-52 (nn.Conv1d(input_size, out_channels,

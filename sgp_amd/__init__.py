@@ -5,6 +5,8 @@ is no CPU fallback."""
 from . import dataloader, datasets, hip
 from .connectivity import (correntropy_connectivity, correntropy_similarity, dense_connectivity,
                            geographic_connectivity)
+from .datamodule import AtStepSplitter, FixedIndicesSplitter, TemporalSplitter, WindowDataModule
+from .datasets import WindowSampler
 from .devgraph import DeviceShiftOperator
 from .edgetables import EdgeTables, csr_tables, sort_plan, stable_sort_by_key
 from .graph import ShiftOperator

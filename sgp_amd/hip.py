@@ -927,6 +927,100 @@ def pack_rows(x, out=None, dtype=torch.bfloat16, overflow=None):
     return out
 
 
+# ---------------------------------------------------------------- window gather of the data module (window_gather.hip)
+WINDOW_ERR_START, WINDOW_ERR_NODE = _DEFINES["SGP_WINDOW_ERR_START"], _DEFINES["SGP_WINDOW_ERR_NODE"]
+
+
+def _window_index(t, name, shapes, device):
+    if not torch.is_tensor(t) or t.dtype != torch.int32:
+        raise TypeError(f"window_gather: {name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if t.device != device:
+        raise ValueError(f"window_gather: {name} is on {t.device}, x on {device}")
+    if not t.is_contiguous():
+        raise ValueError(f"window_gather: {name} must be contiguous")
+    if shapes is not None and tuple(t.shape) not in shapes:
+        raise ValueError(f"window_gather: {name} must have shape {' or '.join(str(s) for s in shapes)}, "
+                         f"got {tuple(t.shape)}")
+    return t
+
+
+@_on_device
+def window_gather(x, start, offset, count, lag, err, node=None, bias=None, scale=None, mask=False, out=None):
+    """``out[b, j, k, :] = T(x[start[b] + offset + lag * j, node(b, k), :])`` in one launch (``sgp_window_gather``).
+
+    ``x``: CUDA ``[T, N, F]`` or ``[T, F]`` (a ``"t f"`` tensor: no node axis in ``out`` either), float32 / bfloat16 /
+    float16 with unit feature stride (any step and node stride); ``start``: CUDA int32 ``[B]``; ``node``: ``None``,
+    CUDA int32 ``[n]`` (shared) or ``[B, n]`` (per item); ``bias`` / ``scale``: CUDA float32 ``[1 | N, 1 | F]``, the
+    scaler's transform fused in; ``mask=True``: ``x != 0`` as a bool tensor; ``err``: the caller's one-element CUDA
+    int32 error word (``WINDOW_ERR_START`` / ``WINDOW_ERR_NODE`` bits are or-ed into it).  Returns float32 (bool)
+    ``[B, count, n, F]`` or ``[B, count, F]``."""
+    if not torch.is_tensor(x) or x.dim() not in (2, 3):
+        raise ValueError("window_gather: x must be a [T, N, F] or [T, F] tensor")
+    if x.dtype != torch.float32 and x.dtype not in STORE_CODES:
+        raise TypeError(f"window_gather: x must be float32, bfloat16 or float16, got {x.dtype}")
+    if x.shape[-1] > 1 and x.stride(-1) != 1:
+        raise ValueError("window_gather: the feature stride of x must be 1")
+    offset, count, lag = int(offset), int(count), int(lag)
+    if offset < 0 or count < 0 or lag < 1:
+        raise ValueError(f"window_gather: offset {offset} and count {count} must not be negative, lag {lag} at least 1")
+    T, F = x.shape[0], x.shape[-1]
+    N = x.shape[1] if x.dim() == 3 else 1
+    if max(T, N, F) > 2 ** 31 - 1:
+        raise ValueError("window_gather: more than 2^31 - 1 steps, nodes or features")
+    if x.dim() == 2 and node is not None:
+        raise ValueError("window_gather: a [T, F] tensor takes no node index")
+    start = _window_index(start, "start", None, x.device)
+    if start.dim() != 1:
+        raise ValueError(f"window_gather: start must be 1-D, got {tuple(start.shape)}")
+    B = start.shape[0]
+    n_out = N
+    if node is not None:
+        if node.dim() not in (1, 2):
+            raise ValueError(f"window_gather: node must be [n] or [{B}, n], got {tuple(node.shape)}")
+        n_out = node.shape[-1]
+        node = _window_index(node, "node", ((n_out,), (B, n_out)), x.device)
+    _window_index(err, "err", ((1,),), x.device)
+    if mask and (bias is not None or scale is not None):
+        raise ValueError("window_gather: a mask takes no scaler")
+    if (bias is None) != (scale is None):
+        raise ValueError("window_gather: bias and scale come together")
+    pn = pf = 1
+    if bias is not None:
+        for name, p in (("bias", bias), ("scale", scale)):
+            if not torch.is_tensor(p) or p.dtype != torch.float32 or p.device != x.device or not p.is_contiguous():
+                raise TypeError(f"window_gather: {name} must be a contiguous float32 tensor on {x.device}")
+            if p.dim() != 2 or p.shape[0] not in (1, N) or p.shape[1] not in (1, F):
+                raise ValueError(f"window_gather: {name} must be [1 | {N}, 1 | {F}], got {tuple(p.shape)}")
+        if bias.shape != scale.shape:
+            raise ValueError(f"window_gather: bias {tuple(bias.shape)} and scale {tuple(scale.shape)} differ")
+        pn, pf = bias.shape
+    shape = (B, count, n_out, F) if x.dim() == 3 else (B, count, F)
+    dtype = torch.bool if mask else torch.float32
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != dtype or out.device != x.device or not out.is_contiguous():
+        raise ValueError(f"window_gather: out must be a contiguous {dtype} {shape} tensor on {x.device}")
+    lib = require_gpu()
+    if not x.is_cuda:
+        raise ValueError("window_gather: x must be a CUDA tensor (the series is resident)")
+    mode = _DEFINES["SGP_WINDOW_MASK"] if mask else _DEFINES["SGP_WINDOW_SCALE" if bias is not None else "SGP_WINDOW_IDENTITY"]
+    _check(lib.sgp_window_gather(x.data_ptr(), STORE_CODES.get(x.dtype, 0), x.stride(0), x.stride(1) if x.dim() == 3 else 0,
+                                 T, N, F, start.data_ptr(), B, offset, count, lag,
+                                 None if node is None else node.data_ptr(), n_out,
+                                 n_out if node is not None and node.dim() == 2 else 0, mode,
+                                 None if bias is None else bias.data_ptr(), None if scale is None else scale.data_ptr(),
+                                 pn, pf, out.data_ptr(), err.data_ptr(), _stream(x)), "sgp_window_gather")
+    return out
+
+
+def window_error(word):
+    """The ``IndexError`` of a non-zero error word of :func:`window_gather`, naming the kind of index; else ``None``."""
+    kinds = [name for bit, name in ((WINDOW_ERR_START, "window start"), (WINDOW_ERR_NODE, "node index")) if word & bit]
+    if not kinds:
+        return None
+    return IndexError(f"window gather: {' and '.join(kinds)} out of range (the rows concerned were written as zeros)")
+
+
 # ---------------------------------------------------------------- k-hop subgraph sampling (subgraph.hip)
 def _flat(t, name, dtype, numel=None):
     """1-D contiguous CUDA tensor of ``dtype`` (and at least ``numel`` entries) -> its pointer."""
