@@ -25,6 +25,8 @@
  *   sgp_window_gather
  *       tsl/data/spatiotemporal_dataset.py (window / horizon indexing of a sample) and
  *       lib/dataloader/subgraph_dataloader.py:31-34 (node slices of a batch), one launch per tensor and batch
+ *   sgp_window_hop_f32
+ *       lib/nn/models/sgp_online.py:55-61 (rearrange 'b t n f -> b n (t f)', sgp_spatial_embedding, torch.cat)
  *   sgp_grouped_linear_f32
  *       lib/nn/models/sgp_model.py:41-52 (decoder input encoder: grouped Conv1d + activation; f4)
  *   sgp_grouped_linear_fwd_16, sgp_grouped_linear_wgrad_16
@@ -701,6 +703,37 @@ int sgp_window_gather(const void* X, int32_t src_fmt, int64_t x_step_stride, int
                       const int32_t* node, int32_t n_out, int64_t node_batch_stride,
                       int32_t mode, const float* bias, const float* scale, int32_t param_nodes, int32_t param_feat,
                       void* out, int32_t* err, sgp_stream_t stream);
+
+/* ------------------------------------------------- Window hops of SGPOnlineModel ---
+ * window_hops.hip.  Replaces lib/nn/models/sgp_online.py:55-61: rearrange(x, 'b t n f -> b n (t f)'),
+ * sgp_spatial_embedding (k hops forward, k hops backward) and torch.cat(x, -1).  ONE launch is one hop of one direction
+ * for the whole batch over a CSR operator (int32 rowptr / col, fp32 val; indices are trusted), into block dst_block of
+ *
+ *   out[b, i, n_blocks * W],  W = steps * feat,  block j = columns j W .. (j + 1) W - 1,  contiguous.
+ *
+ * Source: src_block < 0 reads the raw window where it lies, element (b, t, c, k) at
+ * x[b * x_batch_stride + t * x_step_stride + c * x_node_stride + k] (strides in floats, k stride 1), as column
+ * t * feat + k of node c; src_block >= 0 reads that block of `out` (x is not read).  write_block0 != 0 (window source
+ * only) also writes block 0, the flattened window, for the launch's own rows.  rowptr == NULL with write_block0 writes
+ * block 0 alone (k = 0).
+ *
+ * Every output element is accumulated in fp32 in the order the generic CSR kernel takes for a W-wide slot of an
+ * aligned buffer (sgp_spmm_csr_form(W, 1, 0) lanes per row chunk for W % 4 == 0, one chain in CSR order otherwise), so
+ * the result is bit-equal to sgp_copy_rows_f32 + sgp_spmm_csr_f32 on the flattened window.  Rows without entries are
+ * written as zeros.  For W % 4 == 0 `out` has to be 16-byte aligned.
+ *
+ * form: 0 = the one sgp_window_hop_form names; SGP_WINDOW_HOP_DIRECT gathers the source per element / per 16 bytes
+ * from memory; SGP_WINDOW_HOP_PLANES (window source, steps > 1, n * feat <= 16384) stages the [n, feat] planes of one
+ * step for up to 4 batch items in LDS and gathers there.  Asking for PLANES outside its domain is SGP_EUNSUP.  An empty
+ * shape returns 0 without a launch. */
+#define SGP_WINDOW_HOP_DIRECT 1
+#define SGP_WINDOW_HOP_PLANES 2
+int32_t sgp_window_hop_form(int32_t from_window, int32_t has_operator, int32_t steps, int32_t n, int32_t feat);
+int sgp_window_hop_f32(const int32_t* rowptr, const int32_t* col, const float* val,
+                       const float* x, int64_t x_batch_stride, int64_t x_step_stride, int64_t x_node_stride,
+                       float* out, int32_t src_block, int32_t dst_block, int32_t write_block0,
+                       int32_t batch, int32_t steps, int32_t n, int32_t feat, int32_t n_blocks,
+                       int32_t form, sgp_stream_t stream);
 
 /* ------------------------------------------------- Decoder first layer ("next" row f4) ---
  * Grouped 1x1 convolution of lib/nn/models/sgp_model.py:41-52 (nn.Conv1d(input_size, out_channels,

@@ -16,10 +16,11 @@ from .readout import RidgeReadout, closed_form_readout
 from .scalers import MinMaxScaler, RobustScaler, Scaler, StandardScaler
 from .metrics import (MaskedMAE, MaskedMAPE, MaskedMRE, MaskedMSE, MetricSet, masked_loss, masked_mae, masked_mape,
                       masked_mse)
+from .nn.models import SGPOnlineModel
 from .optim import FusedAdam
 from .predictors import Predictor, SubgraphPredictor
 from .sgp_preprocessing import (preprocess_adj, preprocess_dataset, reservoir_preprocessing_,
-                                sgp_spatial_embedding, sgp_spatial_support)
+                                sgp_spatial_embedding, sgp_spatial_support, window_spatial_embedding)
 from .utils import encode_dataset, self_normalizing_activation
 
 __version__ = "0.1.0"

@@ -1021,6 +1021,78 @@ def window_error(word):
     return IndexError(f"window gather: {' and '.join(kinds)} out of range (the rows concerned were written as zeros)")
 
 
+# ---------------------------------------------------------------- window hops of SGPOnlineModel (window_hops.hip)
+WINDOW_HOP_FORMS = {None: 0, "direct": _DEFINES["SGP_WINDOW_HOP_DIRECT"], "planes": _DEFINES["SGP_WINDOW_HOP_PLANES"]}
+
+
+def window_hop_operands(x, out, k, n_dirs, csr=None, src_block=None, dst_block=None, write_block0=False):
+    """The argument checks of :func:`window_hop`, none of which needs the GPU or reads a tensor's values:
+    ``(b, t, n, f, n_blocks)``.  ``x [b, t, n, f]`` float32 with unit ``f`` stride, ``out [b, n, (1 + k n_dirs) t f]``
+    float32 contiguous, both on one CUDA device; ``csr = (rowptr [n + 1], col, val)`` int32 / int32 / float32 there."""
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise ValueError(f"x: expected a window [b, t, n, f], got {tuple(x.shape) if torch.is_tensor(x) else type(x)}")
+    if x.dtype != torch.float32 or out.dtype != torch.float32:
+        raise ValueError(f"x and out must be float32, got {x.dtype} and {out.dtype}")
+    if not x.is_cuda or out.device != x.device:
+        raise ValueError(f"x and out must be on one CUDA device, got {x.device} and {out.device}")
+    b, t, n, f = x.shape
+    if f > 1 and x.stride(3) != 1:
+        raise ValueError("x: feature stride must be 1")
+    if int(k) != k or k < 0 or n_dirs not in (1, 2):
+        raise ValueError(f"k={k} hops in {n_dirs} directions: expected k >= 0 and 1 or 2 directions")
+    n_blocks = 1 + int(k) * n_dirs
+    W = t * f
+    if out.dim() != 3 or tuple(out.shape) != (b, n, n_blocks * W) or not out.is_contiguous():
+        raise ValueError(f"out: expected a contiguous [{b}, {n}, {n_blocks} * {W}] tensor (1 + k * directions blocks of "
+                         f"t * f columns), got {tuple(out.shape)} with strides {tuple(out.stride())}")
+    if W >= 1 << 24 or n_blocks * W >= 1 << 31:
+        raise ValueError(f"window of {W} columns in {n_blocks} blocks is too wide")
+    if csr is None:
+        if not write_block0 or src_block is not None:
+            raise ValueError("without an operator a launch can only write block 0 from the window")
+        return b, t, n, f, n_blocks
+    rowptr, col, val = csr
+    for name, a, dt in (("rowptr", rowptr, torch.int32), ("col", col, torch.int32), ("val", val, torch.float32)):
+        if not torch.is_tensor(a) or a.dtype != dt or a.dim() != 1 or not a.is_contiguous() or a.device != x.device:
+            raise ValueError(f"{name}: expected a contiguous 1-D {dt} tensor on {x.device}")
+    if rowptr.numel() != n + 1 or col.numel() != val.numel():
+        raise ValueError(f"operator of {rowptr.numel() - 1} rows ({col.numel()} / {val.numel()} entries) for {n} nodes")
+    if dst_block is None or not 1 <= dst_block < n_blocks:
+        raise ValueError(f"dst_block={dst_block} outside [1, {n_blocks})")
+    if src_block is not None and (not 0 <= src_block < n_blocks or src_block == dst_block):
+        raise ValueError(f"src_block={src_block}: expected a block of [0, {n_blocks}) other than the destination")
+    if write_block0 and src_block is not None:
+        raise ValueError("block 0 is written by the launch that reads the window")
+    return b, t, n, f, n_blocks
+
+
+@_on_device
+def window_hop(x, out, k, n_dirs, csr=None, src_block=None, dst_block=None, write_block0=False, form=None):
+    """One launch of csrc/window_hops.hip: ``out`` block ``dst_block`` = ``A`` times the source, per batch item.  The
+    source is the raw window ``x [b, t, n, f]`` read where it lies (``src_block=None``; any batch / step / node
+    strides) or block ``src_block`` of ``out``; ``write_block0`` also writes the flattened window (``'b t n f -> b n
+    (t f)'``) into block 0.  ``csr=None`` with ``write_block0`` writes block 0 alone.  ``form``: ``None``, ``"direct"``
+    or ``"planes"``.  Bit-equal to ``copy_rows`` + ``spmm_csr`` on the flattened window.  Returns ``out``."""
+    if form not in WINDOW_HOP_FORMS:
+        raise ValueError(f"form={form!r}: expected one of {sorted(map(str, WINDOW_HOP_FORMS))}")
+    b, t, n, f, n_blocks = window_hop_operands(x, out, k, n_dirs, csr, src_block, dst_block, write_block0)
+    lib = require_gpu()
+    if out.data_ptr() % 16 and (t * f) % 4 == 0:
+        raise ValueError("out must be 16-byte aligned")
+    rowptr, col, val = (None, None, None) if csr is None else (a.data_ptr() for a in csr)
+    _check(lib.sgp_window_hop_f32(rowptr, col, val, x.data_ptr(), x.stride(0), x.stride(1), x.stride(2),
+                                  out.data_ptr(), -1 if src_block is None else src_block,
+                                  0 if dst_block is None else dst_block, 1 if write_block0 else 0,
+                                  b, t, n, f, n_blocks, WINDOW_HOP_FORMS[form], _stream(x)), "sgp_window_hop_f32")
+    return out
+
+
+def window_hop_form(from_window, has_operator, steps, n, feat):
+    """``"direct"`` or ``"planes"``: the form a launch of that shape takes by itself (host only)."""
+    code = load().sgp_window_hop_form(int(bool(from_window)), int(bool(has_operator)), steps, n, feat)
+    return {v: k for k, v in WINDOW_HOP_FORMS.items() if k}[code]
+
+
 # ---------------------------------------------------------------- k-hop subgraph sampling (subgraph.hip)
 def _flat(t, name, dtype, numel=None):
     """1-D contiguous CUDA tensor of ``dtype`` (and at least ``numel`` entries) -> its pointer."""

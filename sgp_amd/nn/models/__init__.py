@@ -4,8 +4,9 @@ from .gated_gn_model import GatedGraphNetwork, GatedGraphNetworkMLPModel, GatedG
 from .rnn_model import FCRNNModel, RNNModel
 from .dcrnn_model import DCRNNModel
 from .gwnet_model import GraphWaveNetModel
+from .sgp_online import SGPOnlineModel
 from ...metrics import masked_mae        # the loss every model trains with lives with the other losses
 
 __all__ = ["SGPInputEncoder", "SGPModel", "OnlineSGPModel", "ESNModel", "masked_mae", "GatedGraphNetwork",
            "GatedGraphNetworkModel", "GatedGraphNetworkMLPModel", "RNNModel", "FCRNNModel", "DCRNNModel",
-           "GraphWaveNetModel"]
+           "GraphWaveNetModel", "SGPOnlineModel"]

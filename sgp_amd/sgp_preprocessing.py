@@ -162,6 +162,80 @@ def sgp_spatial_embedding(x,
     return res
 
 
+def window_hop_schedule(k, n_dirs):
+    """The launches of :func:`window_spatial_embedding` as ``(direction, src_block, dst_block, write_block0)``, in
+    order; ``src_block=None`` reads the raw window.  Blocks follow the reference's cat (sgp_preprocessing.py:198-217):
+    ``[X | A X .. A^k X | A_b X .. A_b^k X]``.  The first forward hop reads the window and writes block 0 with it;
+    the first backward hop reads block 0.  ``k = 0`` is the one launch that writes block 0."""
+    if int(k) != k or k < 0 or n_dirs not in (1, 2):
+        raise ValueError(f"k={k} hops in {n_dirs} directions: expected k >= 0 and 1 or 2 directions")
+    if k == 0:
+        return [(None, None, 0, True)]
+    steps = []
+    for d in range(n_dirs):
+        for h in range(1, k + 1):
+            dst = d * k + h
+            if h == 1:
+                steps.append((d, None, dst, True) if d == 0 else (d, 0, dst, False))
+            else:
+                steps.append((d, dst - 1, dst, False))
+    return steps
+
+
+def window_spatial_embedding(x, edge_index, edge_weight=None, k=2, bidirectional=True, undirected=False,
+                             add_self_loops=False, remove_self_loops=False, gcn_norm=False, out=None):
+    """``torch.cat(sgp_spatial_embedding(rearrange(x, 'b t n f -> b n (t f)'), ...), -1)`` of the reference's
+    ``SGPOnlineModel`` (lib/nn/models/sgp_online.py:55-61) for a CUDA window ``x [b, t, n, f]``, read where it lies
+    (any batch / step / node strides): ``k * directions`` launches of csrc/window_hops.hip write the blocks of one
+    ``[b, n, (1 + k * directions) * t * f]`` buffer (``out``, or a new one), bit-equal to that composition on the
+    generic CSR kernel.
+
+    ``edge_index`` is a CUDA ``[2, E]`` list: the operators are built on its device with
+    ``DeviceShiftOperator.from_edges(check=False)``, no host read, the backward one from the swapped list and
+    normalised on its own; ``gcn_norm`` (or ``undirected``, which symmetrises and excludes ``bidirectional``)
+    normalises the forward operator symmetrically.  Or a list / tuple of one or two ready ``DeviceShiftOperator``s
+    (forward, backward), which a loop over a fixed graph builds once.  No gradient flows through the hops."""
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise ValueError(f"x: expected a window [b, t, n, f], got {tuple(x.shape) if torch.is_tensor(x) else type(x)}")
+    if x.requires_grad:
+        raise RuntimeError("window_spatial_embedding has no gradient with respect to x: detach it")
+    if not x.is_cuda:
+        raise RuntimeError("window_spatial_embedding runs on the GPU and has no CPU fallback: move x to the device")
+    if x.dtype != torch.float32:
+        x = x.float()
+    if x.shape[3] > 1 and x.stride(3) != 1:
+        x = x.contiguous()
+    b, t, n, f = x.shape
+    if isinstance(edge_index, DeviceShiftOperator):
+        edge_index = [edge_index]
+    if isinstance(edge_index, (list, tuple)):
+        ops = list(edge_index)
+        if len(ops) != (2 if bidirectional else 1) or not all(isinstance(op, DeviceShiftOperator) for op in ops):
+            raise ValueError(f"expected {2 if bidirectional else 1} DeviceShiftOperator(s), forward first")
+    else:
+        if undirected and bidirectional:
+            raise ValueError("undirected symmetrises the operator: bidirectional must be False")
+        if not _is_device_list(edge_index):
+            raise RuntimeError("window_spatial_embedding builds its operators on the GPU: edge_index must be a CUDA "
+                               "[2, E] tensor (or ready DeviceShiftOperators)")
+        build = dict(set_diag=add_self_loops, remove_diag=remove_self_loops, check=False)
+        ops = [DeviceShiftOperator.from_edges(edge_index, edge_weight, n, gcn_norm=bool(gcn_norm or undirected),
+                                              undirected=undirected, **build)]
+        if bidirectional:
+            ops.append(DeviceShiftOperator.from_edges(edge_index, edge_weight, n, gcn_norm=False, transpose=True, **build))
+    for op in ops:
+        if op.num_nodes != n or op.num_cols != n:
+            raise ValueError(f"operator of {op.num_nodes} x {op.num_cols} for a window of {n} nodes")
+    n_dirs = len(ops)
+    if out is None:
+        out = torch.empty(b, n, (1 + k * n_dirs) * t * f, dtype=torch.float32, device=x.device)
+    for d, src, dst, write0 in window_hop_schedule(k, n_dirs):
+        csr = None if d is None else (ops[d].rowptr, ops[d].col, ops[d].val)
+        hip.window_hop(x, out, k, n_dirs, csr, src_block=src, dst_block=dst if csr is not None else None,
+                       write_block0=write0)
+    return out
+
+
 def _row_normalise(a, gcn_norm):
     import scipy.sparse as sp
     deg = np.asarray(a.sum(1)).ravel().astype(np.float32)
