@@ -725,10 +725,20 @@ int sgp_window_gather(const void* X, int32_t src_fmt, int64_t x_step_stride, int
  * form: 0 = the one sgp_window_hop_form names; SGP_WINDOW_HOP_DIRECT gathers the source per element / per 16 bytes
  * from memory; SGP_WINDOW_HOP_PLANES (window source, steps > 1, n * feat <= 16384) stages the [n, feat] planes of one
  * step for up to 4 batch items in LDS and gathers there.  Asking for PLANES outside its domain is SGP_EUNSUP.  An empty
- * shape returns 0 without a launch. */
+ * shape returns 0 without a launch.
+ *
+ * sgp_window_hop_plan (host only) answers with the function the entry launches from what a launch of that shape and
+ * `form` does, as out[0..9]: the form taken; the kernel (0 = window_hop_rows, 1 = window_hop_scalar, 2 =
+ * window_hop_planes); its lanes (lanes per row chunk for rows, lanes per row for planes, 0 for scalar); grid x, y, z;
+ * the batch items of one workgroup (4 for rows, 256 / W clamped to 1 .. batch for scalar, the staged planes' count for
+ * planes); rows per workgroup and trips of its row loop (planes; otherwise 0 and 1); dynamic LDS bytes.  It refuses
+ * with the entry's codes what the entry refuses from these arguments: a bad size, a window too wide, an unknown form,
+ * PLANES outside its domain, a grid y or z above 65535.  An empty shape gives a grid of 0 x 0 x 0. */
 #define SGP_WINDOW_HOP_DIRECT 1
 #define SGP_WINDOW_HOP_PLANES 2
 int32_t sgp_window_hop_form(int32_t from_window, int32_t has_operator, int32_t steps, int32_t n, int32_t feat);
+int sgp_window_hop_plan(int32_t from_window, int32_t has_operator, int32_t batch, int32_t steps, int32_t n,
+                        int32_t feat, int32_t form, int64_t* out);
 int sgp_window_hop_f32(const int32_t* rowptr, const int32_t* col, const float* val,
                        const float* x, int64_t x_batch_stride, int64_t x_step_stride, int64_t x_node_stride,
                        float* out, int32_t src_block, int32_t dst_block, int32_t write_block0,

@@ -208,6 +208,77 @@ __global__ __launch_bounds__(kPlaneThreads) void window_hop_planes(Hop h, int pb
 
 int chain_lanes(int W) { return W % 4 == 0 ? sgp_spmm_csr_form(W, 1, 0) : 0; }
 
+// The launch geometry of one hop: the one computation behind sgp_window_hop_f32 and sgp_window_hop_plan.
+enum { kRows = 0, kScalar = 1, kPlanes = 2 };
+struct HopPlan {
+    int form, kernel, lanes;              // lanes: LPR (rows), G (planes), 0 (scalar)
+    unsigned gx, gy, gz;                  // all 0: an empty shape, nothing to launch
+    int chunk;                            // batch items per workgroup: 4 (rows), bc (scalar), pb (planes)
+    int rows_per_wg, row_trips;           // planes; otherwise 0 and 1
+    size_t lds;
+};
+
+int plan_hop(const char* what, bool win, bool hop, int batch, int steps, int n, int feat, int form, HopPlan& p) {
+    SGP_REQUIRE(batch >= 0 && steps >= 0 && n >= 0 && feat >= 0, "%s: bad size", what);
+    SGP_REQUIRE((long long)steps * feat < (1ll << 24), "%s: window too wide", what);
+    SGP_REQUIRE(form == 0 || form == SGP_WINDOW_HOP_DIRECT || form == SGP_WINDOW_HOP_PLANES, "%s: unknown form", what);
+    const int natural = sgp_window_hop_form(win, hop, steps, n, feat);
+    const int W = steps * feat;
+    p = HopPlan{form ? form : natural, kScalar, 0, 0, 0, 0, 0, 0, 1, 0};
+    if (batch == 0 || n == 0 || W == 0) return 0;
+    if (form == SGP_WINDOW_HOP_PLANES && natural != SGP_WINDOW_HOP_PLANES)
+        return sgp::fail(SGP_EUNSUP, "%s: the staged form needs a window source of more than one step "
+                                     "whose [n, f] plane holds at most %d floats", what, kStageFloats);
+    const int lpr = chain_lanes(W);
+    p.gx = (n + 3) / 4;
+
+    if (p.form == SGP_WINDOW_HOP_PLANES) {
+        const int G = lpr ? 64 / lpr : 1;
+        const int nf = n * feat;
+        int pb = kStageFloats / nf;
+        pb = pb > kPlaneBatch ? kPlaneBatch : pb;
+        pb = pb > batch ? batch : pb;
+        const int gy = (batch + pb - 1) / pb;
+        SGP_REQUIRE(gy <= 65535, "%s: batch too large for one launch (chunk it)", what);
+        // a few workgroups per CU: every row chunk stages its planes again (coalesced, from L2)
+        const int slots = kPlaneThreads / G;
+        const long long wgs = (long long)steps * gy;
+        long long rc = (1024 + wgs - 1) / wgs;
+        const long long rc_max = (n + slots - 1) / slots;
+        rc = rc < 1 ? 1 : (rc > rc_max ? rc_max : rc);
+        int rows_per_wg = (int)((n + rc - 1) / rc);
+        rows_per_wg = (rows_per_wg + slots - 1) / slots * slots;
+        const int gz = (n + rows_per_wg - 1) / rows_per_wg;
+        SGP_REQUIRE(gz <= 65535, "%s: too many row chunks", what);
+        p.kernel = kPlanes;
+        p.lanes = G;
+        p.gx = steps; p.gy = gy; p.gz = gz;
+        p.chunk = pb;
+        p.rows_per_wg = rows_per_wg;
+        p.row_trips = rows_per_wg / slots;
+        p.lds = (size_t)pb * nf * sizeof(float);
+        return 0;
+    }
+    if (lpr == 0) {
+        int bc = 256 / W;
+        bc = bc < 1 ? 1 : (bc > batch ? batch : bc);
+        const int gy = (batch + bc - 1) / bc;
+        SGP_REQUIRE(gy <= 65535, "%s: batch too large for one launch (chunk it)", what);
+        p.gy = gy; p.gz = 1;
+        p.chunk = bc;
+        return 0;
+    }
+    const unsigned gy = (batch + 3) / 4;
+    SGP_REQUIRE(gy <= 65535, "%s: batch too large for one launch (chunk it)", what);
+    const int gz = (W + 4 * lpr - 1) / (4 * lpr);
+    SGP_REQUIRE(gz <= 65535, "%s: window too wide for one launch", what);      // (the runtime refused this launch before)
+    p.kernel = kRows;
+    p.lanes = lpr;
+    p.gy = gy; p.gz = gz;
+    p.chunk = 4;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -217,11 +288,26 @@ int32_t sgp_window_hop_form(int32_t from_window, int32_t has_operator, int32_t s
     return (long long)n * feat <= kStageFloats ? SGP_WINDOW_HOP_PLANES : SGP_WINDOW_HOP_DIRECT;
 }
 
+int sgp_window_hop_plan(int32_t from_window, int32_t has_operator, int32_t batch, int32_t steps, int32_t n,
+                        int32_t feat, int32_t form, int64_t* out) {
+    const char* what = "sgp_window_hop_plan";
+    SGP_REQUIRE(out, "%s: null pointer", what);
+    SGP_REQUIRE(has_operator || from_window, "%s: nothing to do without an operator", what);
+    HopPlan p;
+    if (int rc = plan_hop(what, from_window != 0, has_operator != 0, batch, steps, n, feat, form, p)) return rc;
+    out[0] = p.form; out[1] = p.kernel; out[2] = p.lanes;
+    out[3] = p.gx; out[4] = p.gy; out[5] = p.gz;
+    out[6] = p.chunk; out[7] = p.rows_per_wg; out[8] = p.row_trips;
+    out[9] = (int64_t)p.lds;
+    return 0;
+}
+
 int sgp_window_hop_f32(const int32_t* rowptr, const int32_t* col, const float* val,
                        const float* x, int64_t x_bs, int64_t x_ts, int64_t x_ns,
                        float* out, int32_t src_block, int32_t dst_block, int32_t write_block0,
                        int32_t batch, int32_t steps, int32_t n, int32_t feat, int32_t n_blocks,
                        int32_t form, sgp_stream_t stream) {
+    const char* what = "sgp_window_hop_f32";
     SGP_REQUIRE(batch >= 0 && steps >= 0 && n >= 0 && feat >= 0 && n_blocks >= 1, "sgp_window_hop_f32: bad size");
     SGP_REQUIRE((long long)steps * feat < (1ll << 24) && (long long)steps * feat * n_blocks < (1ll << 31),
                 "sgp_window_hop_f32: window too wide");
@@ -240,41 +326,19 @@ int sgp_window_hop_f32(const int32_t* rowptr, const int32_t* col, const float* v
     }
     const int W = steps * feat;
     if (batch == 0 || n == 0 || W == 0) return 0;
-    const int lpr = chain_lanes(W);
-    if (lpr != 0)
+    if (chain_lanes(W) != 0)
         SGP_REQUIRE(((uintptr_t)out & 15) == 0, "sgp_window_hop_f32: out must be 16-byte aligned");
+    HopPlan p;
+    if (int rc = plan_hop(what, win, hop, batch, steps, n, feat, form, p)) return rc;
     Hop h{rowptr, col, val, x, x_bs, x_ts, x_ns, feat, out, (long long)W * n_blocks,
           W, src_block, dst_block, write_block0 ? 1 : 0, n, batch};
     hipStream_t s = (hipStream_t)stream;
-    const int natural = sgp_window_hop_form(win, hop, steps, n, feat);
-    if (form == SGP_WINDOW_HOP_PLANES && natural != SGP_WINDOW_HOP_PLANES)
-        return sgp::fail(SGP_EUNSUP, "sgp_window_hop_f32: the staged form needs a window source of more than one step "
-                                     "whose [n, f] plane holds at most %d floats", kStageFloats);
-    if (form == 0) form = natural;
-    const unsigned gx = (n + 3) / 4;
+    const dim3 grid(p.gx, p.gy, p.gz);
 
-    if (form == SGP_WINDOW_HOP_PLANES) {
-        const int G = lpr ? 64 / lpr : 1;
-        const int nf = n * feat;
-        int pb = kStageFloats / nf;
-        pb = pb > kPlaneBatch ? kPlaneBatch : pb;
-        pb = pb > batch ? batch : pb;
-        const int gy = (batch + pb - 1) / pb;
-        SGP_REQUIRE(gy <= 65535, "sgp_window_hop_f32: batch too large for one launch (chunk it)");
-        // a few workgroups per CU: every row chunk stages its planes again (coalesced, from L2)
-        const int slots = kPlaneThreads / G;
-        const long long wgs = (long long)steps * gy;
-        long long rc = (1024 + wgs - 1) / wgs;
-        const long long rc_max = (n + slots - 1) / slots;
-        rc = rc < 1 ? 1 : (rc > rc_max ? rc_max : rc);
-        int rows_per_wg = (int)((n + rc - 1) / rc);
-        rows_per_wg = (rows_per_wg + slots - 1) / slots * slots;
-        const int gz = (n + rows_per_wg - 1) / rows_per_wg;
-        SGP_REQUIRE(gz <= 65535, "sgp_window_hop_f32: too many row chunks");
-        const dim3 grid(steps, gy, gz);
-        const size_t lds = (size_t)pb * nf * sizeof(float);
-#define SGP_PLANES(GG) hipLaunchKernelGGL((window_hop_planes<GG>), grid, dim3(kPlaneThreads), lds, s, h, pb, rows_per_wg)
-        switch (G) {
+    if (p.kernel == kPlanes) {
+#define SGP_PLANES(GG) \
+    hipLaunchKernelGGL((window_hop_planes<GG>), grid, dim3(kPlaneThreads), p.lds, s, h, p.chunk, p.rows_per_wg)
+        switch (p.lanes) {
             case 16: SGP_PLANES(16); break;
             case 8: SGP_PLANES(8); break;
             case 4: SGP_PLANES(4); break;
@@ -284,25 +348,17 @@ int sgp_window_hop_f32(const int32_t* rowptr, const int32_t* col, const float* v
 #undef SGP_PLANES
         return sgp::check_launch("window_hop_planes");
     }
-
-    if (lpr == 0) {
-        int bc = 256 / W;
-        bc = bc < 1 ? 1 : (bc > batch ? batch : bc);
-        const int gy = (batch + bc - 1) / bc;
-        SGP_REQUIRE(gy <= 65535, "sgp_window_hop_f32: batch too large for one launch (chunk it)");
-        if (win) hipLaunchKernelGGL((window_hop_scalar<true>), dim3(gx, gy), dim3(256), 0, s, h, bc);
-        else hipLaunchKernelGGL((window_hop_scalar<false>), dim3(gx, gy), dim3(256), 0, s, h, bc);
+    if (p.kernel == kScalar) {
+        if (win) hipLaunchKernelGGL((window_hop_scalar<true>), grid, dim3(256), 0, s, h, p.chunk);
+        else hipLaunchKernelGGL((window_hop_scalar<false>), grid, dim3(256), 0, s, h, p.chunk);
         return sgp::check_launch("window_hop_scalar");
     }
-    const unsigned gy = (batch + 3) / 4;
-    SGP_REQUIRE(gy <= 65535, "sgp_window_hop_f32: batch too large for one launch (chunk it)");
 #define SGP_ROWS(LPR)                                                                                         \
     do {                                                                                                      \
-        const dim3 grid(gx, gy, (W + 4 * LPR - 1) / (4 * LPR));                                               \
         if (win) hipLaunchKernelGGL((window_hop_rows<LPR, true>), grid, dim3(256), 0, s, h);                  \
         else hipLaunchKernelGGL((window_hop_rows<LPR, false>), grid, dim3(256), 0, s, h);                     \
     } while (0)
-    switch (lpr) {
+    switch (p.lanes) {
         case 64: SGP_ROWS(64); break;
         case 32: SGP_ROWS(32); break;
         case 16: SGP_ROWS(16); break;

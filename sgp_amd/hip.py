@@ -1093,6 +1093,32 @@ def window_hop_form(from_window, has_operator, steps, n, feat):
     return {v: k for k, v in WINDOW_HOP_FORMS.items() if k}[code]
 
 
+_WINDOW_HOP_PLAN_KEYS = ("form", "kernel", "lanes", "grid_x", "grid_y", "grid_z", "batch_chunk", "rows_per_wg",
+                         "row_trips", "lds_bytes")
+WINDOW_HOP_KERNELS = ("rows", "scalar", "planes")
+
+
+def window_hop_plan(from_window, has_operator, batch, steps, n, feat, form=None):
+    """What one launch of :func:`window_hop` of that shape does, as a dict (host only: ``sgp_window_hop_plan``, the
+    function the entry launches from): ``form`` ("direct" / "planes"), ``kernel`` ("rows" / "scalar" / "planes"),
+    ``lanes`` (lanes per row chunk for rows, lanes per row for planes, 0 for scalar), ``grid_x`` / ``grid_y`` /
+    ``grid_z``, ``batch_chunk`` (batch items per workgroup), ``rows_per_wg`` and ``row_trips`` (planes; otherwise 0
+    and 1), ``lds_bytes``.  Raises as the entry would: ValueError on a bad size or form, NotImplementedError for
+    ``form="planes"`` outside its domain."""
+    if form not in WINDOW_HOP_FORMS:
+        raise ValueError(f"form={form!r}: expected one of {sorted(map(str, WINDOW_HOP_FORMS))}")
+    out = (c_i64 * len(_WINDOW_HOP_PLAN_KEYS))()
+    rc = load().sgp_window_hop_plan(int(bool(from_window)), int(bool(has_operator)), int(batch), int(steps), int(n),
+                                    int(feat), WINDOW_HOP_FORMS[form], ctypes.addressof(out))
+    if rc == SGP_EINVAL:
+        raise ValueError(f"window_hop_plan: {load().sgp_last_error().decode()}")
+    _check(rc, "sgp_window_hop_plan")
+    plan = {k: int(out[i]) for i, k in enumerate(_WINDOW_HOP_PLAN_KEYS)}
+    plan["form"] = {v: k for k, v in WINDOW_HOP_FORMS.items() if k}[plan["form"]]
+    plan["kernel"] = WINDOW_HOP_KERNELS[plan["kernel"]]
+    return plan
+
+
 # ---------------------------------------------------------------- k-hop subgraph sampling (subgraph.hip)
 def _flat(t, name, dtype, numel=None):
     """1-D contiguous CUDA tensor of ``dtype`` (and at least ``numel`` entries) -> its pointer."""

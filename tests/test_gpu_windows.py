@@ -171,6 +171,47 @@ def test_kernel_bad_node_sets_the_node_bit(bad, f):
         assert torch.equal(mask, want != 0)
 
 
+# more rows than the grid has row slots (16384 / gx), more pieces than it has lanes (4096 x 256): the second trips of
+# the kernel's two grid-stride loops, and its unsigned row and piece divisions on values that are not tiny
+STRIDE_LOOPS = {
+    # id: (steps, nodes, feat, batch, count, element path forced, node index)
+    "rows>16384,gx=1": (40, 37, 1, 1500, 12, False, False),
+    "rows>cap,gx=5": (40, 130, 8, 300, 12, True, False),
+    "pieces>4096x256": (8, 70000, 15, 2, 2, False, True),
+}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("shape", sorted(STRIDE_LOOPS))
+def test_kernel_stride_loops_take_a_second_trip(shape, dtype):
+    n_steps, n, f, batch, count, misalign, with_node = STRIDE_LOOPS[shape]
+    g = torch.Generator().manual_seed(n + batch)
+    if misalign:                                             # one element off 16-byte alignment: the element path
+        flat = torch.randn(n_steps * n * f + 1, generator=g).to(dtype).cuda()
+        x = flat[1:].view(n_steps, n, f)
+        assert x.data_ptr() % 16 == flat.element_size()
+    else:
+        x = torch.randn(n_steps, n, f, generator=g).to(dtype).cuda()
+        assert f % 4 != 0
+    node = torch.randperm(n, generator=g).int().cuda() if with_node else None
+    pieces, rows = n * f, batch * count
+    gx = min(-(-pieces // 256), 4096) if pieces > 64 else 1
+    assert rows > 16384 // gx or pieces > 4096 * 256          # by the launch code as it stands; the comparison holds anyway
+    good = torch.randint(0, n_steps - count + 1, (batch,), generator=g, dtype=torch.int32)
+    good[0] = n_steps - count                                # the last legal start
+    bad = batch * 2 // 3
+    st = good.clone()
+    st[bad] = n_steps - count + 1                            # one bad start among the many rows
+    err = err_word()
+    got = hip.window_gather(x, st.cuda(), 0, count, 1, err, node=node)
+    want = R.window_gather(x, good.cuda(), 0, count, 1, node)
+    assert float(want[bad].abs().sum()) != 0
+    want[bad] = 0                                            # exactly that sample's rows are zeros
+    assert got.dtype == torch.float32 and got.shape == want.shape == (batch, count, n, f)
+    assert torch.equal(got, want)
+    assert int(err.item()) == hip.WINDOW_ERR_START
+
+
 # ---- WindowSampler against SubgraphSampler ---------------------------------------------------------------------------
 TS, NS, FS, FU = 64, 1000, 3, 5                            # the sampler cases of tests/test_gpu_subgraph.py
 S_WIN, S_HOR, S_LAG, S_DELAY, S_B, S_K, S_ROOTS = 5, 7, 3, 1, 3, 2, 37
