@@ -590,10 +590,36 @@ int sgp_reservoir_window_f32(const float* x, int64_t x_batch_stride, int64_t x_s
 int64_t sgp_gesn_workspace_bytes(int32_t N, int32_t R, int32_t L);
 /* sgp_gesn_tune(persistent): 1 (default, also SGP_TUNE=gesn_persistent=1) lets sgp_gesn_f32 run the
  * sequence in ONE cooperative launch per 256 steps when the shape allows it (R % 16 == 0, R <= 384,
- * L <= 8, the (layer, column group, row tile) items fit one workgroup per CU; csrc/gesn_persist.hip:
+ * L <= 8, not R = 144 .. 256 with L > 1, the (layer, column group, row tile) items fit one workgroup per CU; csrc/gesn_persist.hip:
  * layers as a wavefront, weights in registers, one grid barrier per step); 0 = always two launches
  * per (step, layer); < 0 = query.  Returns the setting. */
 int sgp_gesn_tune(int32_t persistent);
+/* Two read-only queries on which path sgp_gesn_f32 takes (tests/gesn_forms.py).  Why the persistent kernel does not
+ * serve a shape or a call: */
+#define SGP_GESN_WHY_TUNE_OFF    1  /* sgp_gesn_tune(0) / SGP_TUNE=gesn_persistent=0 */
+#define SGP_GESN_WHY_R_MOD_16    2  /* R is no multiple of 16 */
+#define SGP_GESN_WHY_R_ABOVE_384 3
+#define SGP_GESN_WHY_LAYERS      4  /* L > 8 */
+#define SGP_GESN_WHY_ITEMS       5  /* more (layer, column group, row tile group) items than CUs at every LDS carve-up */
+#define SGP_GESN_WHY_OUT_ALIGN   6  /* sgp_gesn_last_run only: `out` rows cannot take 16-byte stores */
+#define SGP_GESN_WHY_SCRATCH     7  /* sgp_gesn_last_run only: this build of the kernel uses scratch memory */
+#define SGP_GESN_WHY_LAUNCH      8  /* the runtime refused: the cooperative launch, or no device to plan for */
+#define SGP_GESN_WHY_FORM_OFF    9  /* an instantiation that is switched off: R = 144 .. 256 with L > 1 (gesn_persist.hip) */
+/* sgp_gesn_plan: what sgp_gesn_f32 does for [N nodes, R units, L layers] on a device of `cus` compute units (cus <= 0:
+ * the current device's; with cus > 0 no device call is made), from the functions the launches themselves go through.
+ * out[8] (int64):
+ *   0: 1 = the persistent kernel serves the shape   1: else why not (SGP_GESN_WHY_*), 0 when served
+ *   2: KSB of gesn_persistent<KSB> (2, 4, 6)   3: row tiles of 16 nodes per workgroup (1 .. 4)
+ *   4: workgroups   5: dynamic LDS bytes                                  (2 .. 5: 0 when not served)
+ *   6: NV of the stepwise gesn_update_kernel<NV> (1, 2, 4, 6, 8)
+ *   7: 1 = the stepwise GEMM on the states takes its 16-byte (VEC) form, for a 16-byte aligned h_state
+ * sgp_gesn_edge_cap: adjacency entries a workgroup of the persistent kernel keeps in LDS; a workgroup whose rows hold
+ * more reads col / val from global memory.
+ * sgp_gesn_last_run: what the last sgp_gesn_f32 call of this process did.  out[3] (int64): steps run by the persistent
+ * kernel, steps run stepwise, and why (SGP_GESN_WHY_*) the persistent kernel did not serve the latter (0 if it served all). */
+int sgp_gesn_plan(int32_t N, int32_t R, int32_t L, int32_t cus, int64_t* out);
+int sgp_gesn_edge_cap(void);
+int sgp_gesn_last_run(int64_t* out);
 int sgp_gesn_f32(const int32_t* rowptr, const int32_t* col, const float* val,
                  const float* x, int64_t x_row_stride, int64_t x_step_stride,
                  const float* const* w_ih, const float* const* w_hh, const float* const* b,

@@ -20,6 +20,8 @@ int run_chunk(const int32_t* rowptr, const int32_t* col, const float* val, const
               const float* wcat, const float* wpk, const float* bcat, float* cbuf, float* h_state, float* out,
               long long ors, long long oss, unsigned* bar, const double* alpha, int act,
               int tc, int N, int R, int L, hipStream_t stream);
+void plan_query(int N, int R, int L, int cus, int64_t* out);
+void note_run(long long persistent_steps, long long stepwise_steps, int why);
 }
 
 namespace {
@@ -151,11 +153,19 @@ __global__ __launch_bounds__(64) void gesn_update_kernel(
     }
 }
 
+// ---- which instantiation a launch takes: launch_gemm, launch_update and sgp_gesn_plan all go through these
+bool gemm_is_vec(int K, long long lda, long long ldw, bool a_aligned16, bool w_aligned16) {
+    return K > 0 && K % 16 == 0 && lda % 4 == 0 && ldw % 4 == 0 && a_aligned16 && w_aligned16;
+}
+int update_nv(int R) {                      // NV of gesn_update_kernel
+    const int nv = (R + 63) / 64;
+    return nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 6 ? 6 : 8;
+}
+
 int launch_gemm(const float* A, long long lda, const float* W, long long ldw, const float* bias,
                 float* C, long long ldc, int M, int N, int K, hipStream_t stream) {
     if (M == 0 || N == 0) return 0;
-    const bool vec = K > 0 && K % 16 == 0 && lda % 4 == 0 && ldw % 4 == 0 &&
-                     sgp::aligned16(A) && sgp::aligned16(W);
+    const bool vec = gemm_is_vec(K, lda, ldw, sgp::aligned16(A), sgp::aligned16(W));
     const dim3 grid((M + 15) / 16, (N + 15) / 16), block(256);
     if (vec)
         hipLaunchKernelGGL(gemm_nt_kernel<true>, grid, block, 0, stream, A, lda, W, ldw, bias, C, ldc, M, N, K);
@@ -172,12 +182,13 @@ int launch_update(const int32_t* rowptr, const int32_t* col, const float* val,
     hipLaunchKernelGGL(gesn_update_kernel<NV>, dim3(n_nodes), dim3(64), 0, stream, rowptr, col,  \
                        val, z, ldz, p, ldp, h_in, (float)alpha, (float)(1.0 - alpha), act,       \
                        h_out, out_row, out_stride, n_nodes, R)
-    const int nv = (R + 63) / 64;
-    if (nv <= 1) SGP_GESN_LAUNCH(1);
-    else if (nv <= 2) SGP_GESN_LAUNCH(2);
-    else if (nv <= 4) SGP_GESN_LAUNCH(4);
-    else if (nv <= 6) SGP_GESN_LAUNCH(6);
-    else SGP_GESN_LAUNCH(8);
+    switch (update_nv(R)) {
+        case 1: SGP_GESN_LAUNCH(1); break;
+        case 2: SGP_GESN_LAUNCH(2); break;
+        case 4: SGP_GESN_LAUNCH(4); break;
+        case 6: SGP_GESN_LAUNCH(6); break;
+        default: SGP_GESN_LAUNCH(8); break;
+    }
 #undef SGP_GESN_LAUNCH
     return sgp::check_launch("gesn_update");
 }
@@ -243,6 +254,7 @@ int sgp_gesn_f32(const int32_t* rowptr, const int32_t* col, const float* val,
     SGP_REQUIRE(T >= 0 && N >= 0 && F > 0 && R > 0 && L > 0, "sgp_gesn_f32: bad size");
     SGP_REQUIRE(act >= SGP_ACT_TANH && act <= SGP_ACT_TANH_REL, "sgp_gesn_f32: unknown activation %d", act);
     if (R > 512) return sgp::fail(SGP_EUNSUP, "sgp_gesn_f32: reservoir size %d > 512 not supported", R);
+    sgp_gesn::note_run(0, 0, 0);              // (sgp_gesn_last_run: filled in where the call ends well)
     if (T == 0 || N == 0) return 0;
     SGP_REQUIRE(rowptr && col && val && x && w_ih && w_hh && b && alpha && out && h_state && workspace,
                 "sgp_gesn_f32: null pointer");
@@ -287,8 +299,10 @@ int sgp_gesn_f32(const int32_t* rowptr, const int32_t* col, const float* val,
     // sequence to the stepwise path below, which restarts from h_state
     int t_done = 0;
     bool used_persistent = false;
+    int why = SGP_GESN_WHY_TUNE_OFF;          // why the persistent kernel does not serve the steps from t_done on
     constexpr int kBarSticky = 400;           // (gesn_persist.hip) failure word outside the per-launch memset
     if (sgp_gesn::mode()) {
+        why = 0;
         e = hipMemsetAsync(reinterpret_cast<unsigned*>(base + ws.bar) + kBarSticky, 0, sizeof(unsigned), stream);
         if (e != hipSuccess) return sgp::fail((int)e, "sgp_gesn_f32: %s", hipGetErrorString(e));
         for (; t_done < T && !rc; t_done += kStepChunk) {
@@ -304,7 +318,7 @@ int sgp_gesn_f32(const int32_t* rowptr, const int32_t* col, const float* val,
                                               out_row_stride, out_step_stride,
                                               reinterpret_cast<unsigned*>(base + ws.bar), alpha, act,
                                               tc, N, R, L, stream);
-            if (r > 0) break;                      // refused: nothing was launched for this chunk
+            if (r > 0) { why = r; break; }         // refused (r: its SGP_GESN_WHY_*): nothing was launched for this chunk
             if (r < 0) return r;
             used_persistent = true;
         }
@@ -317,7 +331,10 @@ int sgp_gesn_f32(const int32_t* rowptr, const int32_t* col, const float* val,
             if (e != hipSuccess) return sgp::fail((int)e, "sgp_gesn_f32: %s", hipGetErrorString(e));
             if (failed) return sgp::fail(SGP_EUNSUP, "sgp_gesn_f32: grid barrier of the persistent kernel timed out");
         }
-        if (t_done >= T) return 0;
+        if (t_done >= T) {
+            sgp_gesn::note_run(T, 0, 0);
+            return 0;
+        }
     }
     float* hcur = h_state;
     float* hnext = base + ws.hb;
@@ -344,7 +361,19 @@ int sgp_gesn_f32(const int32_t* rowptr, const int32_t* col, const float* val,
         e = hipMemcpyAsync(h_state, hcur, (size_t)L * NR * sizeof(float), hipMemcpyDeviceToDevice, stream);
         if (e != hipSuccess) return sgp::fail((int)e, "sgp_gesn_f32: state copy: %s", hipGetErrorString(e));
     }
+    if (!rc) sgp_gesn::note_run(t_done, T - t_done, why);
     return rc;
+}
+
+int sgp_gesn_plan(int32_t N, int32_t R, int32_t L, int32_t cus, int64_t* out) {
+    SGP_REQUIRE(out, "sgp_gesn_plan: null pointer");
+    SGP_REQUIRE(N > 0 && R > 0 && L > 0, "sgp_gesn_plan: bad size");
+    if (R > 512) return sgp::fail(SGP_EUNSUP, "sgp_gesn_plan: reservoir size %d > 512 not supported", R);
+    sgp_gesn::plan_query(N, R, L, cus, out);
+    out[6] = update_nv(R);
+    // the GEMM on h: rows of R floats from h_state / the workspace (16-byte aligned) against the staged [2R, R] weights
+    out[7] = gemm_is_vec(R, R, R, true, true);
+    return 0;
 }
 
 }  // extern "C"

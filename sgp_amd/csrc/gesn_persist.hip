@@ -398,14 +398,30 @@ size_t lds_bytes(int R, int RT) {
     return (size_t)(RT * 16 * (R + 4) + 16) * 4 + (size_t)RT * 16 * 64 * 16 + (size_t)kEdgeCap * 8 + (kMaxRT * 16 + 1 + 3) * 4;
 }
 
-// Plans the launch; returns false when the shape is not served (the caller then uses gesn.hip's path).
-bool plan(int N, int R, int L, PArgs& a, int& n_blocks, size_t& lds) {
+// What the last sgp_gesn_f32 call of the process did (sgp_gesn_last_run): steps per path, SGP_GESN_WHY_* of the rest
+long long g_last[3] = {0, 0, 0};
+void note_run(long long persistent_steps, long long stepwise_steps, int why) {
+    g_last[0] = persistent_steps; g_last[1] = stepwise_steps; g_last[2] = why;
+}
+int edge_cap() { return kEdgeCap; }
+
+// The launch arithmetic for `cus` compute units, host only: plan() and sgp_gesn_plan both go through this.
+// Returns 0 (served; a's n_rt, rt_per_wg, n_rtg, item_base and n_cg are set) or the SGP_GESN_WHY_* of the refusal.
+int plan_shape(int N, int R, int L, int cus, PArgs& a, int& n_blocks, size_t& lds) {
+    if (!mode()) return SGP_GESN_WHY_TUNE_OFF;
+    if (R % 16 != 0) return SGP_GESN_WHY_R_MOD_16;
     // (R <= 384: the 512-wide instantiation needs more than the 128 VGPRs a 1024-thread workgroup gets)
-    if (R % 16 != 0 || R > 384 || L > kMaxLayers || N <= 0) return false;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        return false;
+    if (R > 384) return SGP_GESN_WHY_R_ABOVE_384;
+    if (L > kMaxLayers) return SGP_GESN_WHY_LAYERS;
+    // gesn_persistent<4> with layers above 0 is switched off: hipcc joins the asm load of p's second slice (features
+    // 128 ..) with the accumulator by register copies placed right behind the load (v_mov v14, v20 .. after
+    // global_load_dwordx4 v[20:23] .. sc1, no s_waitcnt between: it does not count loads issued from asm), so the
+    // copies hold whatever the registers held.  Measured: tests/test_gpu_gesn_forms.py, R = 144 .. 256 with L > 1
+    // off by O(1); one layer, and KSB 2 and 6 (no such copy in their code), are right.  Until the update phase keeps
+    // p out of the loop-carried registers these shapes take the stepwise path.
+    if (ksb_of(R) == 4 && L > 1) return SGP_GESN_WHY_FORM_OFF;
+    if (cus <= 0) return SGP_GESN_WHY_LAUNCH;            // the runtime named no device / no CU count
+    if (N <= 0 || L <= 0 || R <= 0) return SGP_GESN_WHY_ITEMS;
     a.n_rt = (N + 15) / 16;
     for (int rt = 1; rt <= kMaxRT; ++rt) {
         lds = lds_bytes(R, rt);
@@ -420,13 +436,38 @@ bool plan(int N, int R, int L, PArgs& a, int& n_blocks, size_t& lds) {
         a.item_base[L] = items;
         if (items <= cus) {                // one 1024-thread workgroup per CU
             a.rt_per_wg = rt; a.n_rtg = n_rtg; n_blocks = items;
-            return true;
+            return 0;
         }
     }
-    return false;
+    return SGP_GESN_WHY_ITEMS;
 }
 
-// One chunk of tc steps.  0 = done, > 0 = the launch was refused (caller falls back), < 0 = error.
+int device_cus() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return cus;
+}
+
+// Plans the launch on the current device; 0 when the shape is served, else why not (the caller then uses gesn.hip's path).
+int plan(int N, int R, int L, PArgs& a, int& n_blocks, size_t& lds) {
+    return plan_shape(N, R, L, device_cus(), a, n_blocks, lds);
+}
+
+// sgp_gesn_plan's persistent half: out[0 .. 5] = served, why, KSB, rt_per_wg, workgroups, dynamic LDS bytes
+void plan_query(int N, int R, int L, int cus, int64_t* out) {
+    PArgs a;
+    int n_blocks = 0;
+    size_t lds = 0;
+    const int why = plan_shape(N, R, L, cus > 0 ? cus : device_cus(), a, n_blocks, lds);
+    out[0] = why == 0; out[1] = why;
+    out[2] = why ? 0 : ksb_of(R); out[3] = why ? 0 : a.rt_per_wg; out[4] = why ? 0 : n_blocks; out[5] = why ? 0 : (int64_t)lds;
+}
+
+// One chunk of tc steps.  0 = done, > 0 = the launch was refused (its SGP_GESN_WHY_*; caller falls back), < 0 = error.
 int launch(PArgs& a, int n_blocks, size_t lds, hipStream_t stream) {
     const int ksb = ksb_of(a.R);                           // R <= 64 ksb
     const void* kern = ksb <= 2 ? reinterpret_cast<const void*>(gesn_persistent<2>)
@@ -437,14 +478,15 @@ int launch(PArgs& a, int n_blocks, size_t lds, hipStream_t stream) {
     // could store / reuse such a register early -- refuse it (the stepwise path then serves the call).
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, kern);
-    if (e != hipSuccess || fa.localSizeBytes != 0) { (void)hipGetLastError(); return 1; }
+    if (e != hipSuccess) { (void)hipGetLastError(); return SGP_GESN_WHY_LAUNCH; }
+    if (fa.localSizeBytes != 0) return SGP_GESN_WHY_SCRATCH;
     e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { (void)hipGetLastError(); return 1; }
+    if (e != hipSuccess) { (void)hipGetLastError(); return SGP_GESN_WHY_LAUNCH; }
     e = hipMemsetAsync(a.bar, 0, kBarWords * sizeof(unsigned), stream);
-    if (e != hipSuccess) { (void)hipGetLastError(); return 1; }
+    if (e != hipSuccess) { (void)hipGetLastError(); return SGP_GESN_WHY_LAUNCH; }
     void* params[] = {&a};
     e = hipLaunchCooperativeKernel(kern, dim3(n_blocks), dim3(1024), params, (unsigned)lds, stream);
-    if (e != hipSuccess) { (void)hipGetLastError(); return 1; }
+    if (e != hipSuccess) { (void)hipGetLastError(); return SGP_GESN_WHY_LAUNCH; }
     return 0;
 }
 
@@ -455,8 +497,8 @@ int run_chunk(const int32_t* rowptr, const int32_t* col, const float* val, const
     PArgs a;
     int n_blocks = 0;
     size_t lds = 0;
-    if (ors % 4 != 0 || oss % 4 != 0 || !sgp::aligned16(out)) return 1;   // 16-byte row stores
-    if (!plan(N, R, L, a, n_blocks, lds)) return 1;
+    if (const int why = plan(N, R, L, a, n_blocks, lds)) return why;
+    if (ors % 4 != 0 || oss % 4 != 0 || !sgp::aligned16(out)) return SGP_GESN_WHY_OUT_ALIGN;   // 16-byte row stores
     a.rowptr = rowptr; a.col = col; a.val = val; a.p0 = p0; a.wcat = wcat; a.wpk = wpk; a.bcat = bcat;
     a.cbuf = cbuf; a.h_state = h_state; a.out = out; a.ors = ors; a.oss = oss; a.bar = bar;
     for (int l = 0; l < kMaxLayers; ++l) {
@@ -479,4 +521,12 @@ int pack(const float* wcat, float* wpk, int R, int L, hipStream_t stream) {
 extern "C" int sgp_gesn_tune(int32_t persistent) {
     if (persistent >= 0) sgp_gesn::g_mode = persistent != 0;
     return sgp_gesn::mode();
+}
+
+extern "C" int sgp_gesn_edge_cap(void) { return sgp_gesn::edge_cap(); }
+
+extern "C" int sgp_gesn_last_run(int64_t* out) {
+    SGP_REQUIRE(out, "sgp_gesn_last_run: null pointer");
+    for (int i = 0; i < 3; ++i) out[i] = sgp_gesn::g_last[i];
+    return 0;
 }

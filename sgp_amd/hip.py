@@ -732,6 +732,37 @@ def gesn_sequence(rowptr, col, val, x, weights, alphas, activation, out, h_state
     return out
 
 
+# reason codes of the two queries below, by name ("tune_off", "r_mod_16", "r_above_384", "layers", "items",
+# "out_align", "scratch", "launch"); 0 = served
+GESN_WHY = {k[len("SGP_GESN_WHY_"):].lower(): v for k, v in _DEFINES.items() if k.startswith("SGP_GESN_WHY_")}
+_GESN_WHY_NAMES = {v: k for k, v in GESN_WHY.items()}
+_GESN_PLAN_KEYS = ("persistent", "why", "ksb", "rt_per_wg", "workgroups", "lds_bytes", "nv", "gemm_vec")
+
+
+def gesn_plan(n, r, layers, cus=0):
+    """What ``gesn_sequence`` does for [n nodes, r units, ``layers``] on ``cus`` compute units (0: the current
+    device's), as a dict (``sgp_gesn_plan``; host only when ``cus`` > 0).  ``why`` is None or a key of ``GESN_WHY``."""
+    out = (c_i64 * len(_GESN_PLAN_KEYS))()
+    _check(load().sgp_gesn_plan(int(n), int(r), int(layers), int(cus), ctypes.addressof(out)), "sgp_gesn_plan")
+    d = {k: int(out[i]) for i, k in enumerate(_GESN_PLAN_KEYS)}
+    d["persistent"], d["gemm_vec"] = bool(d["persistent"]), bool(d["gemm_vec"])
+    d["why"] = _GESN_WHY_NAMES[d["why"]] if d["why"] else None
+    return d
+
+
+def gesn_edge_cap():
+    """Adjacency entries a workgroup of the persistent DynGESN kernel keeps in LDS (``sgp_gesn_edge_cap``)."""
+    return int(load().sgp_gesn_edge_cap())
+
+
+def gesn_last_run():
+    """``{"persistent_steps", "stepwise_steps", "why"}`` of the process's last ``sgp_gesn_f32`` call."""
+    out = (c_i64 * 3)()
+    _check(load().sgp_gesn_last_run(ctypes.addressof(out)), "sgp_gesn_last_run")
+    return {"persistent_steps": int(out[0]), "stepwise_steps": int(out[1]),
+            "why": _GESN_WHY_NAMES[int(out[2])] if out[2] else None}
+
+
 @_on_device
 def gemm_nt(a, w, bias, out):
     """out[m, n] = sum_k a[m, k] w[n, k] (+ bias[n]); 2-D float32 CUDA, unit inner strides."""

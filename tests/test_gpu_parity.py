@@ -472,18 +472,23 @@ def test_gesn_against_oracle(n, f, r, L, act):
 def test_gesn_long_sequence():
     """T = 301 spans two chunks of the layer-0 input GEMM (256 steps each) and an odd number of
     ping-pong swaps of the state buffers; it must equal the same sequence run in short pieces
-    (state carried by the caller) bit for bit, and match the oracle."""
+    (state carried by the caller) bit for bit, and match the oracle.  This is the STEPWISE path's check
+    (R = 40 is no multiple of 16, asserted below); the persistent kernel's split-call identity is
+    tests/test_gpu_gesn_forms.py::test_split_calls_on_the_persistent_path_are_bit_identical."""
+    from sgp_amd import hip
     torch.manual_seed(17)
     n, f, r, L, t = 60, 2, 40, 2, 301
     ei, ew = synthetic.sparse_traffic_graph(n, 400, seed=3)
     enc = sgp_amd.GESNEncoder(f, r, L, .9, .9, .7, 1., True)
     x = torch.randn(t, n, f)
     y = enc(x, ei, ew)
+    assert hip.gesn_last_run() == {"persistent_steps": 0, "stepwise_steps": t, "why": "r_mod_16"}
     from sgp_amd.nn.encoders.dyn_gesn_encoder import gesn_operator
     op = gesn_operator(ei, ew, n)
     pieces, h = [], None
     for t0 in range(0, t, 50):
         o, h = enc.reservoir(x[None, t0:t0 + 50], op, h=None if h is None else list(h))
+        assert hip.gesn_last_run()["stepwise_steps"] == o.shape[1]
         pieces.append(o[0])
     assert torch.equal(torch.cat(pieces).cpu(), y.cpu())
     layers = [dict(w_ih=l.w_ih.data, w_hh=l.w_hh.data, b_ih=l.b_ih.data, alpha=float(l.alpha))
@@ -496,12 +501,15 @@ def test_gesn_long_sequence():
 
 
 @pytest.mark.parametrize("n,f,r,L,act,t", [(207, 2, 320, 3, "tanh", 40), (325, 2, 320, 3, "tanh", 9),
-                                            (70, 3, 64, 1, "relu", 300), (33, 1, 512, 2, "self_norm", 12),
-                                            (500, 2, 48, 4, "tanh", 20), (16, 2, 16, 8, "tanh", 5)])
+                                            (70, 3, 64, 1, "relu", 300), (33, 1, 272, 2, "self_norm", 12),
+                                            (500, 2, 48, 4, "tanh", 20), (16, 2, 16, 8, "tanh", 5),
+                                            (33, 1, 512, 2, "self_norm", 12)])
 def test_gesn_persistent_kernel_equals_stepwise_path(n, f, r, L, act, t):
     """The one-launch-per-256-steps kernel (csrc/gesn_persist.hip: layer wavefront, weights in
     registers, grid barrier per step) against the two-launches-per-(step, layer) path: the same
-    products in another summation order of the K split, so 1e-5; states carried identically."""
+    products in another summation order of the K split, so 1e-5; states carried identically.  Which
+    path each run took is asserted (hip.gesn_last_run); the last case, R = 512, is the stepwise list:
+    the persistent kernel does not serve it, and both runs are the stepwise path's."""
     from sgp_amd import hip
     from sgp_amd.nn.encoders.dyn_gesn_encoder import gesn_operator
     lib = hip.load()
@@ -514,8 +522,12 @@ def test_gesn_persistent_kernel_equals_stepwise_path(n, f, r, L, act, t):
     try:
         assert lib.sgp_gesn_tune(1) == 1
         y1, h1 = res(x, op)
+        want = {"persistent_steps": t, "stepwise_steps": 0, "why": None} if r <= 384 else \
+            {"persistent_steps": 0, "stepwise_steps": t, "why": "r_above_384"}
+        assert hip.gesn_last_run() == want, hip.gesn_last_run()
         assert lib.sgp_gesn_tune(0) == 0
         y0, h0 = res(x, op)
+        assert hip.gesn_last_run() == {"persistent_steps": 0, "stepwise_steps": t, "why": "tune_off"}
     finally:
         lib.sgp_gesn_tune(1)
     assert torch.isfinite(y1).all()
