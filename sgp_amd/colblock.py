@@ -15,19 +15,26 @@ block, local row 511 = a row nobody owns, weight 0; the last one of a list carri
 spare rounds of such entries (the kernel's look-ahead reads them).  Storage is round-major: entry i of slot s of a segment that starts at
 round q sits at ``(q + i) * 64 + s``; ``segptr[wg * n_blocks + b]`` = q.
 """
+from dataclasses import dataclass
+
 import numpy as np
 import torch
 
+from .planrecord import PlanRecord
 
-class ColBlockPlan:
-    def __init__(self, entries, segptr, wg_row0, n_wg, n_blocks, cols_per_block, n_rows, n_cols, pad_share):
-        self.entries, self.segptr, self.wg_row0 = entries, segptr, wg_row0
-        self.n_wg, self.n_blocks, self.cols_per_block = n_wg, n_blocks, cols_per_block
-        self.n_rows, self.n_cols, self.pad_share = n_rows, n_cols, pad_share
 
-    def to(self, device):
-        return ColBlockPlan(self.entries.to(device), self.segptr.to(device), self.wg_row0.to(device), self.n_wg,
-                            self.n_blocks, self.cols_per_block, self.n_rows, self.n_cols, self.pad_share)
+@dataclass(eq=False)
+class ColBlockPlan(PlanRecord):
+    KIND = "colblock"
+    entries: torch.Tensor     # int32 [rounds * 64, 2], round-major
+    segptr: torch.Tensor      # int32 [n_wg * n_blocks + 1], first round of every segment
+    wg_row0: torch.Tensor     # int32 [n_wg + 1], first row of every workgroup
+    n_wg: int
+    n_blocks: int
+    cols_per_block: int
+    n_rows: int
+    n_cols: int
+    pad_share: float
 
 
 def row_ranges(rowptr, n_rows, n_wg, rows_cap):

@@ -22,7 +22,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import hip, tune
+from . import colblock, hip, mixplan, plancache, tune
 from .tileplan import build_reordered_plan, build_tile_plan, locality_order
 
 
@@ -244,21 +244,33 @@ class ShiftOperator:
         plan with <= 64-row tiles that every LDS-staged kernel accepts, even where a tall-tile plan
         (VALU kernel only) exists."""
         key = (feat % 64 == 0, str(device))
-        if key not in self._plans:
-            plan = std = None
-            if feat % 64 == 0 and self.nnz() > 0:
-                from . import plancache
-                if limits is None:
-                    limits = hip.tiled_limits(feat)
-                tl = hip.tall_tile_limits(feat)
-                plan, std = plancache.fetch(self, "tile", (sorted(limits.items()), sorted(tl.items())),
-                                            lambda: self._build_tile_plans(limits, tl))
-            if std is not None:
-                self._plans[(key, "std")] = std.to(device)
-            self._plans[key] = None if plan is None else plan.to(device)
+        if key not in self._plans and feat % 64 == 0 and self.nnz() > 0:
+            if limits is None:
+                limits = hip.tiled_limits(feat)
+            tl = hip.tall_tile_limits(feat)
+            self._placed(key, "tile", (sorted(limits.items()), sorted(tl.items())),
+                         lambda: self._build_tile_plans(limits, tl), device)
         if not tall and (key, "std") in self._plans:     # also on the call that built both variants
             return self._plans[(key, "std")]
-        return self._plans[key]
+        return self._plans.setdefault(key, None)
+
+    def _placed(self, key, kind, params, build, device, keep=None):
+        """Fetch-and-place behind the plan getters: what ``build()`` returns (host side: a plan, the list of a long-row
+        operator's passes, or None) -- through the plan cache as (``kind``, ``params``) unless ``kind`` is None -- moved to
+        ``device`` and remembered under ``key`` of ``self._plans``.  ``keep``: the caller's test of the host plan; a plan
+        that fails it is dropped before anything moves.  The tile getter's pair ``(plan, std)`` puts ``std``, where
+        there is one, under ``(key, "std")``."""
+        plan = build() if kind is None else plancache.fetch(self, kind, params, build)
+        if isinstance(plan, tuple):
+            plan, std = plan
+            if std is not None:
+                self._plans[(key, "std")] = std.to(device)
+        if isinstance(plan, list):
+            plan = SplitPasses(p.to(device) for p in plan)
+        elif plan is not None:
+            plan = plan.to(device) if keep is None or keep(plan) else None
+        self._plans[key] = plan
+        return plan
 
     def _build_tile_plans(self, limits, tl):
         """Host side of ``tile_plan``: ``(plan, std)`` -- the plan the staged kernels get and, where a tall-tile plan (VALU
@@ -302,20 +314,14 @@ class ShiftOperator:
         """Column-blocked plan (``sgp_amd.colblock``, kernel ``sgp_spmm_colblock_f32``) for graphs
         without locality, or None (feature widths that are not multiples of 64, >= ``colblock.MAX_COLS`` = 2^22 columns)."""
         key = ("colblock", feat, str(device))
-        if key not in self._plans:
-            plan = None
-            from . import colblock
-            if feat % 64 == 0 and self.num_cols < colblock.MAX_COLS and self.nnz() > 0:
-                lib = hip.load()
-                plan = colblock.build_colblock_plan(self.rowptr.numpy(), self.col.numpy(), self.val.numpy(),
-                                                    self.num_nodes, self.num_cols, feat,
-                                                    rows_cap=lib.sgp_spmm_colblock_rows_cap(),
-                                                    round_pad=lib.sgp_spmm_colblock_round_pad(),
-                                                    l2_bytes=tune.get("colblock_l2_mb", 2.5, float) * 2 ** 20)
-                if plan is not None:
-                    plan = plan.to(device)
-            self._plans[key] = plan
-        return self._plans[key]
+        if key not in self._plans and feat % 64 == 0 and self.num_cols < colblock.MAX_COLS and self.nnz() > 0:
+            lib = hip.load()
+            # (kind None: kept out of the on-disk cache on purpose -- the plan follows a tune value and is cheap to build)
+            self._placed(key, None, None, lambda: colblock.build_colblock_plan(
+                self.rowptr.numpy(), self.col.numpy(), self.val.numpy(), self.num_nodes, self.num_cols, feat,
+                rows_cap=lib.sgp_spmm_colblock_rows_cap(), round_pad=lib.sgp_spmm_colblock_round_pad(),
+                l2_bytes=tune.get("colblock_l2_mb", 2.5, float) * 2 ** 20), device)
+        return self._plans.setdefault(key, None)
 
     def mix_plan(self, feat, device, strict=True):
         """Mixed dense / sparse plan (``sgp_amd.mixplan``, kernel ``sgp_spmm_mix_f32``) on the tiles and
@@ -323,53 +329,38 @@ class ShiftOperator:
         two-phase stream, and blocks of 16 rows that share enough columns for the dense form to pay
         (k-NN-like graphs; ``SGP_TUNE=mix_min_share=..``, default 0.25 of the (group, column) pairs)."""
         key = ("mix", feat % 64 == 0, str(device), bool(strict))
-        if key not in self._plans:
-            plan = None
-            base = self.tile_plan(feat, device, tall=False)
-            if base is not None and base.pipe is not None and (base.group_fill >= 0.5 or not strict):
-                from . import mixplan, plancache
-                lib = hip.load()
-                thr, dh = tune.get("mix_thr", 4, int), lib.sgp_spmm_mix_max_dense(int(self.num_cols > self.num_nodes))
+        if key in self._plans:
+            return self._plans[key]
+        base = self.tile_plan(feat, device, tall=False)
+        if base is not None and base.pipe is not None and (base.group_fill >= 0.5 or not strict):
+            lib = hip.load()
+            thr, dh = tune.get("mix_thr", 4, int), lib.sgp_spmm_mix_max_dense(int(self.num_cols > self.num_nodes))
 
-                def build():
-                    order = None
-                    if base.reordered:
-                        order = locality_order(self.rowptr.numpy(), self.col.numpy(), self.num_nodes)
-                    return mixplan.build_mix_plan(self.rowptr.numpy(), self.col.numpy(), self.val.numpy(), self.num_nodes,
-                                                  base, thr=thr, dh=dh, order=order)
-                # (the base plan is a function of the operator and the kernels' limits, which the key carries)
-                plan = plancache.fetch(self, "mix", (thr, dh, sorted(hip.tiled_limits(feat).items())), build)
-                min_share = tune.get("mix_min_share", 0.25, float) if strict else -1.0
-                if plan is not None and (plan.dense_share < min_share
-                                         or plan.max_union > lib.sgp_spmm_mix_max_union()):
-                    plan = None
-                if plan is not None:
-                    plan = plan.to(device)
-            self._plans[key] = plan
-        return self._plans[key]
+            def build():
+                order = None
+                if base.reordered:
+                    order = locality_order(self.rowptr.numpy(), self.col.numpy(), self.num_nodes)
+                return mixplan.build_mix_plan(self.rowptr.numpy(), self.col.numpy(), self.val.numpy(), self.num_nodes,
+                                              base, thr=thr, dh=dh, order=order)
+            min_share = tune.get("mix_min_share", 0.25, float) if strict else -1.0
+            # (the base plan is a function of the operator and the kernels' limits, which the key carries)
+            self._placed(key, "mix", (thr, dh, sorted(hip.tiled_limits(feat).items())), build, device,
+                         keep=lambda p: p.dense_share >= min_share and p.max_union <= lib.sgp_spmm_mix_max_union())
+        return self._plans.setdefault(key, None)
 
     def split_plan(self, device):
         """Plan of the split-fp16 hop (``sgp_amd.splitplan``, kernel ``sgp_spmm_split_f32``) or None.  Operators with
         rows longer than a wave's column budget (the reference's full PV-US / CER-En graphs) get a LIST of plans, one
         per pass over a segment of the columns (``splitplan.build_split_passes``); ``hip.spmm_split`` takes either."""
         key = ("split", str(device))
-        if key not in self._plans:
-            plan = None
-            if self.nnz() > 0:
-                from . import plancache
-                lib = hip.load()
-                lim, wide = hip.split_limits(), hip.split_limits(wide=True)
-                if tune.get("split_wide", 1, int) == 0:
-                    wide = None
-                plan = plancache.fetch(self, "split", (sorted(lim.items()), wide and sorted(wide.items()),
-                                                       tune.get("split_passes", 1, int), _split_order_mode()),
-                                       lambda: self._build_split_plan(lim, wide))
-                if isinstance(plan, list):
-                    plan = SplitPasses(p.to(device) for p in plan)
-                elif plan is not None:
-                    plan = plan.to(device)
-            self._plans[key] = plan
-        return self._plans[key]
+        if key not in self._plans and self.nnz() > 0:
+            lim, wide = hip.split_limits(), hip.split_limits(wide=True)
+            if tune.get("split_wide", 1, int) == 0:
+                wide = None
+            self._placed(key, "split", (sorted(lim.items()), wide and sorted(wide.items()),
+                                        tune.get("split_passes", 1, int), _split_order_mode()),
+                         lambda: self._build_split_plan(lim, wide), device)
+        return self._plans.setdefault(key, None)
 
     def _build_split_plan(self, lim, wide=None):
         """Host side of ``split_plan``: a SplitPlan, a list of them (long rows, one per pass) or None.  ``wide``: limits of

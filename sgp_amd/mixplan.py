@@ -27,6 +27,7 @@ import itertools
 import numpy as np
 import torch
 
+from .planrecord import PlanRecord
 from .tileplan import GROUP_ROWS, GROUPS_PER_TILE, build_phase_stream, tile_unions
 
 BLOCK_GROUPS = 4
@@ -218,31 +219,25 @@ def mix_reference(mix, n_tiles, x):
     return y
 
 
-class MixPlan:
+class MixPlan(PlanRecord):
     """Device-ready arrays of ``sgp_spmm_mix_f32`` (torch tensors) + plan statistics."""
+    KIND = "mix"
     TENSORS = ("uptr", "ucol", "usplit", "gptr", "gsup", "gidx", "gw", "rowmap", "dptr", "didx", "dw")
+    SCALARS = ("max_union", "max_tile_quads", "max_range_steps", "max_dense", "n_dense", "dense_share", "fill", "thr", "dh")
+    FIELDS = TENSORS + SCALARS + ("n_tiles", "n_rows", "reordered", "mean_phase_cost")
 
     def __init__(self, arrays, n_tiles, n_rows, reordered=False):
+        """From the dict of numpy arrays and statistics ``build_mix_stream`` returns."""
         self.n_tiles, self.n_rows, self.reordered = int(n_tiles), int(n_rows), reordered
         for k in self.TENSORS:
-            v = arrays[k]
-            setattr(self, k, v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v)))
-        for k in ("max_union", "max_tile_quads", "max_range_steps", "max_dense", "n_dense", "dense_share",
-                  "fill", "thr", "dh"):
+            setattr(self, k, torch.from_numpy(np.ascontiguousarray(arrays[k])))
+        for k in self.SCALARS:
             setattr(self, k, arrays[k])
         pc = arrays["phase_cost"]
         self.mean_phase_cost = float(np.mean(pc)) if len(pc) else 0.0
 
     def arrays(self):
         return {k: getattr(self, k).cpu().numpy() for k in self.TENSORS}
-
-    def to(self, device):
-        d = {k: getattr(self, k).to(device) for k in self.TENSORS}
-        for k in ("max_union", "max_tile_quads", "max_range_steps", "max_dense", "n_dense", "dense_share",
-                  "fill", "thr", "dh"):
-            d[k] = getattr(self, k)
-        d["phase_cost"] = [self.mean_phase_cost]
-        return MixPlan(d, self.n_tiles, self.n_rows, self.reordered)
 
 
 def build_mix_plan(rowptr, col, val, n_rows, base, thr=4, dh=10, order=None, pad_dense=False):

@@ -1,17 +1,25 @@
 """On-disk cache of the host-side hop plans (split / tile / mix), keyed by a hash of the operator's CSR arrays, the
-kernel limits and a format version: the second ``encode_dataset`` of an experiment sweep (reference: one call per run,
-lib/utils.py:27-32) pays no planning at all.  Off unless a directory is named -- ``SGP_AMD_CACHE=/path`` or
-``sgp_amd.plancache.set_dir(path)``; files are ``torch.save`` pickles of the plan objects (CPU tensors), so the
-directory must be one the user trusts, like any checkpoint directory."""
+kernel limits, a format version and a fingerprint of the planners' source: the second ``encode_dataset`` of an
+experiment sweep (reference: one call per run, lib/utils.py:27-32) pays no planning at all.  Off unless a directory is
+named -- ``SGP_AMD_CACHE=/path`` or ``sgp_amd.plancache.set_dir(path)``.  A file is a ``torch.save`` of plan STATES
+(``planrecord.PlanRecord.state``: dicts, lists and tuples of CPU tensors, numbers and strings) and is read with
+``torch.load(weights_only=True)``, which builds nothing else: a file that holds anything more -- a plan object pickled by
+an older version, a file someone else put there -- does not load, counts as a miss and is replaced."""
 import hashlib
 import os
 import tempfile
 
 import torch
 
-VERSION = 9          # (9: split plans may be dealt in blob order and say so in their stats; 8: band tables) bump when a plan format or a planner's output changes
+from . import colblock, mixplan, splitplan, tileplan
+
+VERSION = 10         # (10: plan states instead of pickled plan objects) bump when the file format changes; a changed planner shows in the fingerprint
 _dir = None
 stats = {"hits": 0, "misses": 0, "stores": 0}
+_KINDS = {c.KIND: c for c in (tileplan.TilePlan, mixplan.MixPlan, splitplan.SplitPlan, colblock.ColBlockPlan)}
+# the sources that decide what a plan holds (with the library's ABI version: the native planner's interface)
+_SOURCES = ("splitplan.py", "tileplan.py", "mixplan.py", "colblock.py", "graph.py", os.path.join("csrc", "plan_split.hip"))
+_fingerprint = None
 
 
 def set_dir(path):
@@ -35,30 +43,57 @@ def operator_hash(op):
     return h
 
 
+def fingerprint():
+    """Hash of the planners' source files and the library's ABI version, computed once per process: plans made by
+    other planner code are never served."""
+    global _fingerprint
+    if _fingerprint is None:
+        from . import hip
+        m = hashlib.blake2b(digest_size=8)
+        m.update(f"abi {hip._DEFINES['SGP_ABI_VERSION']}".encode())
+        here = os.path.dirname(os.path.abspath(__file__))
+        for name in _SOURCES:
+            with open(os.path.join(here, name), "rb") as f:
+                m.update(f.read())
+        _fingerprint = m.hexdigest()
+    return _fingerprint
+
+
 def _path(op, kind, params):
     d = directory()
     if d is None:
         return None
-    tag = hashlib.blake2b(repr((VERSION, kind, params)).encode(), digest_size=8).hexdigest()
+    tag = hashlib.blake2b(repr((VERSION, fingerprint(), kind, params)).encode(), digest_size=8).hexdigest()
     return os.path.join(d, f"{kind}-{operator_hash(op)}-{tag}.pt")
 
 
-_MISS = object()
+def _state(plan):
+    """What ``fetch`` stores for what ``build()`` returned: a plan's state, a list or tuple of them, or None."""
+    if isinstance(plan, (list, tuple)):
+        return type(plan)(_state(p) for p in plan)
+    return None if plan is None else plan.state()
+
+
+def _plan(state):
+    if isinstance(state, (list, tuple)):
+        return type(state)(_plan(s) for s in state)
+    return None if state is None else _KINDS[state["kind"]].from_state(state)
 
 
 def fetch(op, kind, params, build):
-    """The plan ``build()`` returns (CPU tensors inside, or None), from the cache when a file for (operator, kind,
-    params) exists; a fresh build is stored.  A file that does not load (truncated, another version of the package)
-    counts as a miss and is replaced."""
+    """The plan ``build()`` returns (CPU tensors inside; a list or tuple of plans; None), from the cache when a file
+    for (operator, kind, params) exists; a fresh build is stored.  A file that does not load (truncated, another version
+    of the package, anything but plan states) counts as a miss and is replaced."""
     path = _path(op, kind, params)
     if path is None:
         return build()
     if os.path.exists(path):
         try:
-            got = torch.load(path, map_location="cpu", weights_only=False)
-            if isinstance(got, dict) and got.get("version") == VERSION and got.get("params") == repr(params):
+            got = torch.load(path, map_location="cpu", weights_only=True)
+            if got["version"] == VERSION and got["params"] == repr(params) and got["fingerprint"] == fingerprint():
+                plan = _plan(got["plan"])
                 stats["hits"] += 1
-                return got["plan"]
+                return plan
         except Exception:
             pass
     stats["misses"] += 1
@@ -67,7 +102,7 @@ def fetch(op, kind, params, build):
         os.makedirs(os.path.dirname(path), exist_ok=True)
         fd, tmp = tempfile.mkstemp(dir=os.path.dirname(path), suffix=".tmp")
         os.close(fd)
-        torch.save({"version": VERSION, "params": repr(params), "plan": plan}, tmp)
+        torch.save({"version": VERSION, "params": repr(params), "fingerprint": fingerprint(), "plan": _state(plan)}, tmp)
         os.replace(tmp, path)                              # atomic: concurrent ranks never see half a file
         stats["stores"] += 1
     except OSError:

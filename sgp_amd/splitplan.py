@@ -27,32 +27,44 @@ banded time-major walk of ``sgp_spmm_split_banded_f32``.
 Columns a wave does not use up to ``32 * chunks`` are padded with weight 0 and the address of staged row 0
 (finite data, so 0 * x stays 0).  Duplicate entries of a row are summed before the split.
 """
+from dataclasses import dataclass, field
+from typing import Optional
+
 import numpy as np
 import torch
 
+from .planrecord import PlanRecord
 
-class SplitPlan:
-    def __init__(self, hdr, rowid, ucol, afr, adr, rinv, n_tiles, n_rows, n_cols, norm_inf, stats):
-        self.hdr, self.rowid, self.ucol, self.afr, self.adr, self.rinv = hdr, rowid, ucol, afr, adr, rinv
-        self.n_tiles, self.n_rows, self.n_cols = n_tiles, n_rows, n_cols
-        self.norm_inf, self.stats = norm_inf, stats
-        self.accumulate = False          # later passes of an operator whose long rows were cut into column segments
-        self.bands = {}                  # column budget -> (band_first int32 [n_bands + 1] beside the plan's arrays, largest band)
-        self.ucol_host = ucol if ucol.device.type == "cpu" else None     # what further band tables are cut from
 
-    def __setstate__(self, state):       # (plans pickled before the band table existed)
-        self.__dict__.update(state)
-        self.__dict__.setdefault("bands", {})
-        self.__dict__.setdefault("ucol_host", self.ucol if self.ucol.device.type == "cpu" else None)
+@dataclass(eq=False)
+class SplitPlan(PlanRecord):
+    KIND = "split"
+    HOST = ("ucol_host",)
+    hdr: torch.Tensor
+    rowid: torch.Tensor
+    ucol: torch.Tensor
+    afr: torch.Tensor
+    adr: torch.Tensor
+    rinv: torch.Tensor
+    n_tiles: int
+    n_rows: int
+    n_cols: int
+    norm_inf: float
+    stats: dict
+    accumulate: bool = False                              # later passes of an operator whose long rows were cut into column segments
+    bands: dict = field(default_factory=dict)             # column budget -> (band_first int32 [n_bands + 1] beside the plan's arrays, largest band)
+    ucol_host: Optional[torch.Tensor] = None              # the CPU ``ucol``, what further band tables are cut from: stays on the host
 
-    def to(self, device):
-        p = SplitPlan(self.hdr.to(device), self.rowid.to(device), self.ucol.to(device), self.afr.to(device),
-                      self.adr.to(device), self.rinv.to(device), self.n_tiles, self.n_rows, self.n_cols, self.norm_inf,
-                      self.stats)
-        p.accumulate = self.accumulate
-        p.bands = {k: (t.to(device), m) for k, (t, m) in self.bands.items()}
-        p.ucol_host = self.ucol_host
-        return p
+    def __post_init__(self):
+        if self.ucol_host is None and self.ucol.device.type == "cpu":
+            self.ucol_host = self.ucol
+
+    @classmethod
+    def from_state(cls, state):
+        plan = super().from_state(state)
+        plan.ucol_host = None                             # (not part of a state: found again as at construction)
+        plan.__post_init__()
+        return plan
 
     def band_table(self, col_budget):
         """``(band_first, largest band)`` for bands of at most ``col_budget`` distinct staged rows: ``band_first`` (int32,

@@ -9,11 +9,13 @@ import numpy as np
 import torch
 
 from . import tune
+from .planrecord import PlanRecord
 
 
 @dataclass
-class TilePlan:
+class TilePlan(PlanRecord):
     """Arrays of ``sgp_spmm_tiled_f32`` (include/sgp_amd.h)."""
+    KIND = "tile"
     trow: torch.Tensor        # int32 [n_tiles + 1], first row of every tile
     uptr: torch.Tensor        # int32 [n_tiles + 1]
     ucol: torch.Tensor        # int32 [sum of per-tile distinct columns]
@@ -33,17 +35,6 @@ class TilePlan:
     rowmap: Optional[torch.Tensor] = None   # int32 [64 * n_tiles] output row of every (tile, slot), -1 = none
     pipe: Optional[dict] = None             # two-phase row-group stream of sgp_spmm_res_f32 / _mix (build_phase_stream)
     reordered: bool = False                 # tiles follow locality_order, not the row numbering
-
-    def to(self, device):
-        mv = lambda t: None if t is None else t.to(device)
-        pipe = None if self.pipe is None else {
-            k: (v.to(device) if torch.is_tensor(v) else v) for k, v in self.pipe.items()}
-        return TilePlan(self.trow.to(device), self.uptr.to(device), self.ucol.to(device),
-                        self.erow.to(device), self.ecol.to(device), self.eval.to(device),
-                        self.tile_rows, self.n_tiles, self.n_rows, self.max_union,
-                        self.max_row_edges, mv(self.gptr), self.group_fill,
-                        mv(self.gidx), mv(self.gw), self.max_tile_quads, mv(self.rowmap), pipe,
-                        self.reordered)
 
 
 def tile_unions(rowptr, col, trow):
@@ -538,15 +529,9 @@ def build_tile_plan(rowptr, col, val, n_rows, max_union, max_tile_rows, max_row_
             plan.rowmap = torch.from_numpy(rowmap)
             plan.max_tile_quads = int(np.diff(gptr[::GROUPS_PER_TILE].astype(np.int64)).max())
             ps = build_phase_stream(trow, uptr, ucol, lcol, row_of_edge, np.asarray(val), slots)
-            plan.pipe = dict(usplit=torch.from_numpy(ps["usplit"]), gptr=torch.from_numpy(ps["gptr"]),
-                             gsup=torch.from_numpy(ps["gsup"]),
-                             uptr=torch.from_numpy(ps["uptr"]), ucol=torch.from_numpy(ps["ucol"]),
-                             max_union=ps["max_union"],
-                             gidx=torch.from_numpy(ps["gidx"]), gw=torch.from_numpy(ps["gw"]),
-                             rowmap=torch.from_numpy(ps["rowmap"]), fill=ps["fill"],
-                             max_tile_quads=ps["max_tile_quads"],
-                             max_range_steps=ps["max_range_steps"],
-                             phase_cost=ps["phase_cost"])
+            # the stream's arrays as tensors, its numbers as they are (phase_cost: a statistic, as floats so that it has a mean)
+            stream = dict(ps, phase_cost=ps["phase_cost"].astype(np.float64))
+            plan.pipe = {k: torch.from_numpy(v) if isinstance(v, np.ndarray) else v for k, v in stream.items()}
             if equalize is None:
                 equalize = tune.get("equal_cost_tiles", 0, int) == 1
             if equalize and trow_override is None and tr == 64 and n_tiles >= 512:
