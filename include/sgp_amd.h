@@ -922,6 +922,31 @@ int sgp_ridge_predict_score_f32(const int64_t* segs, int32_t n_segs, const int32
                                 const uint8_t* mask, int64_t m_ss, int64_t m_ns, int64_t m_cs,
                                 float* yhat, double* sums, void* work, int64_t work_bytes, sgp_stream_t stream);
 
+/* The same pass for a PATH of n_alphas = G regularisation strengths solved from one Gram: W [D, G*H*C] fp32 row-major,
+ * column (g * H + l) * C + c = alpha g, lag l + 1, channel c; b [G*H*C] fp64; yhat [G, S, H, N, C] or NULL; sums
+ * [G, H, 4] fp64 or NULL.  The kernel ADDS into sums (the caller zeroes it; chunks staged from the host accumulate).
+ * Segments, steps, scaler, y and mask as in sgp_ridge_predict_score_f32, and so is the arithmetic of every output
+ * column: v_mfma_f32_16x16x4_f32 with the same k per lane in the same panel order, fp32 partials over at most 64
+ * feature columns added in fp64, the bias in fp64, the inverse transform with scale + 5e-8f in fp32, y + 5e-8f in
+ * fp32; with the g-th column block of W and b the single-alpha entry writes the same yhat bit for bit.  W is not held
+ * in LDS but streamed: per 32-column K panel one X stage [64 x 32] and one W stage [32 x 16 TP], the columns walked in
+ * passes of TP <= 8 16-column tiles (a row block with several passes stages X again).  There is no LDS refusal.  The
+ * masked sums go through one slab per workgroup in `work` and a final kernel, in a fixed order, without atomics.
+ * Limits (SGP_EINVAL): G 1 .. 64, H*C 1 .. 256, G*H*C <= 4096, n_cols <= 16384.
+ * sgp_ridge_path_form -- host only, computed by the functions the entry launches with -- fills out[] (int64) with
+ *   {16-column tiles = ceil(G*H*C / 16), tiles per pass TP, passes, workgroups, the most 64-row blocks a workgroup
+ *    walks, 32-column K panels, dynamic LDS bytes (the kernel adds 768 static bytes)}
+ * and sgp_ridge_path_workspace_bytes is what the entry needs (-1 on a bad size): workgroups x passes x TP x 16 x 32. */
+int64_t sgp_ridge_path_workspace_bytes(int64_t n_rows, int32_t n_cols, int32_t n_out, int32_t n_alphas);
+int sgp_ridge_path_form(int64_t n_rows, int32_t n_cols, int32_t n_out, int32_t n_alphas, int64_t* out);
+int sgp_ridge_predict_score_path_f32(const int64_t* segs, int32_t n_segs, const int32_t* steps, int64_t n_steps,
+                                     int64_t n_nodes, const float* W, const double* b, int32_t n_alphas,
+                                     int32_t horizon, int32_t channels,
+                                     const float* scale, const float* bias, int64_t sc_node_stride,
+                                     const float* y, int64_t y_ss, int64_t y_ns,
+                                     const uint8_t* mask, int64_t m_ss, int64_t m_ns, int64_t m_cs,
+                                     float* yhat, double* sums, void* work, int64_t work_bytes, sgp_stream_t stream);
+
 
 /* ------------------------------------------------ Decoder MLP and readout -----
  * The trained layers of SGPModel after its input layer (decoder_mlp.hip), forward and backward.  EXACT-FP32

@@ -12,7 +12,7 @@ from .edgetables import EdgeTables, csr_tables, sort_plan, stable_sort_by_key
 from .graph import ShiftOperator
 from .nn.encoders import GESNEncoder, SGPEncoder, SGPSpatialEncoder, SGPTemporalEncoder
 from .nn.reservoir import GESNLayer, GraphESN, Reservoir, ReservoirLayer
-from .readout import RidgeReadout, closed_form_readout
+from .readout import RidgeReadout, RidgePath, closed_form_readout, ridge_solve_path
 from .scalers import MinMaxScaler, RobustScaler, Scaler, StandardScaler
 from .metrics import (MaskedMAE, MaskedMAPE, MaskedMRE, MaskedMSE, MetricSet, masked_loss, masked_mae, masked_mape,
                       masked_mse)

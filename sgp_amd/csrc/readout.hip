@@ -445,6 +445,182 @@ __global__ void ridge_score_final_kernel(const double* __restrict__ part, int n_
     sums[e] = s;
 }
 
+// ------------------------------------------------------------------ predict + score, alpha path
+// The same product for G alphas at once: W is [D][G * H * C], far too wide to keep in LDS, so its 32-row panels are
+// streamed through LDS beside the X stage.  The output columns are walked in passes of TP 16-column tiles (12 VGPRs a
+// tile: 4 fp32 accumulators and their 4 fp64 spills; at 8 tiles the kernel still fits the 256 registers of the two
+// waves per SIMD its launch bound asks for, without scratch); a row block with
+// more than one pass stages its X panels again (from L2).  The arithmetic of one output column is that of
+// ridge_predict_kernel instruction for instruction: the same k per lane, the same panel order, fp32 partials over 64
+// columns added in fp64, the same epilogue.  The masked sums of a (row block, pass) are reduced in a fixed order (row
+// groups of a wave by shuffle, the four waves through LDS) and added into the workgroup's own slab.
+constexpr int QT_MAX = 8;           // 16-column tiles per pass
+constexpr int QG_MAX = 64;          // alphas
+constexpr int QHC_MAX = 256;        // horizon x channels
+constexpr int QJ_MAX = 4096;        // alphas x horizon x channels
+
+// LDS row stride of a W stage: the rows k and k + 1 that the two halves of a 32-lane group read land on other banks
+__host__ __device__ constexpr int path_wld(int pw) { return pw % 32 == 0 ? pw + 16 : pw; }
+
+template <int TP>
+__global__ __launch_bounds__(256, 2) void ridge_path_kernel(Segs S, const int32_t* __restrict__ steps, int64_t n_nodes,
+                                                       int64_t n_steps, int64_t n_rows, const float* __restrict__ W,
+                                                       const double* __restrict__ bvec, int G, int H, int C,
+                                                       int npass, int npan, Score sc, double* __restrict__ part) {
+    constexpr int PW = 16 * TP, WLD = path_wld(PW), WQ = PW / 8;      // WQ: W stage elements per thread
+    extern __shared__ float lds[];
+    float* X = lds;                                  // [PRB][PLD]
+    float* Wl = X + PRB * PLD;                       // [PKB][WLD]
+    double* red = reinterpret_cast<double*>(Wl + PKB * WLD);  // [4][PW][4]; both sizes above are even
+    __shared__ int rstep[PRB], rnode[PRB], rsidx[PRB];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int HC = H * C, J = G * HC, D = S.ncols, JP = npass * PW;
+
+    const int ldcol = tid & (PKB - 1), ldrow = tid >> 5;     // X staging: one column, rows ldrow + 8q
+    const int64_t nrb = (n_rows + PRB - 1) / PRB;
+    float v[PRB / 8], wv[WQ];
+    auto load = [&](int kp, int j0) {
+        const ColSrc c = resolve(S, kp * PKB + ldcol, 0);
+#pragma unroll
+        for (int q = 0; q < PRB / 8; ++q) {
+            const int row = ldrow + 8 * q;
+            v[q] = fetch(c, rstep[row], rnode[row], 0.f);
+        }
+#pragma unroll
+        for (int q = 0; q < WQ; ++q) {                       // W stage: element tid + 256 q of [PKB][PW]
+            const int e = tid + 256 * q, k = kp * PKB + e / PW, j = j0 + e % PW;
+            wv[q] = (k < D && j < J) ? W[(int64_t)k * J + j] : 0.f;
+        }
+    };
+
+    for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+        __syncthreads();                                     // previous block's epilogue done with rowinfo
+        if (tid < PRB) {
+            const int64_t r = rb * PRB + tid;
+            int st = -1, nd = 0, si = 0;
+            if (r < n_rows) {
+                const int64_t s = r / n_nodes;
+                nd = (int)(r - s * n_nodes);
+                si = (int)s;
+                st = steps[s];
+            }
+            rstep[tid] = st;
+            rnode[tid] = nd;
+            rsidx[tid] = si;
+        }
+        __syncthreads();
+        for (int p = 0; p < npass; ++p) {
+            const int j0 = p * PW;
+            sgp::f32x4 acc[TP];
+            double accd[TP][4];
+#pragma unroll
+            for (int t = 0; t < TP; ++t) {
+                acc[t] = (sgp::f32x4){0.f, 0.f, 0.f, 0.f};
+                accd[t][0] = accd[t][1] = accd[t][2] = accd[t][3] = 0.0;
+            }
+            load(0, j0);
+            for (int kp = 0; kp < npan; ++kp) {
+#pragma unroll
+                for (int q = 0; q < PRB / 8; ++q) X[(ldrow + 8 * q) * PLD + ldcol] = v[q];
+#pragma unroll
+                for (int q = 0; q < WQ; ++q) {
+                    const int e = tid + 256 * q;
+                    Wl[(e / PW) * WLD + e % PW] = wv[q];
+                }
+                __syncthreads();
+                if (kp + 1 < npan) load(kp + 1, j0);
+                // 16x16x4: A[i = lane & 15][k = lane >> 4] = X[row][k], B[k][j = lane & 15] = W[k][j]
+#pragma unroll
+                for (int ks = 0; ks < PKB / 4; ++ks) {
+                    const int k = ks * 4 + (lane >> 4);
+                    const float a = X[(w * 16 + (lane & 15)) * PLD + k];
+                    const float* wr = Wl + k * WLD + (lane & 15);
+#pragma unroll
+                    for (int t = 0; t < TP; ++t)
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wr[16 * t], acc[t], 0, 0, 0);
+                }
+                __syncthreads();
+                if ((kp & 1) || kp + 1 == npan) {            // fp32 partial over at most 64 columns, then fp64
+#pragma unroll
+                    for (int t = 0; t < TP; ++t) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) accd[t][r] += (double)acc[t][r];
+                        acc[t] = (sgp::f32x4){0.f, 0.f, 0.f, 0.f};
+                    }
+                }
+            }
+            // epilogue: lane holds output column j = j0 + 16 t + (lane & 15) = (g H + l) C + c of rows
+            // 4 (lane >> 4) + r of the wave's 16; a tile may straddle two alphas
+#pragma unroll
+            for (int t = 0; t < TP; ++t) {
+                const int j = j0 + 16 * t + (lane & 15);
+                double sums[4] = {0.0, 0.0, 0.0, 0.0};
+                if (j < J) {
+                    const int g = j / HC, jr = j - g * HC, l = jr / C, c = jr - l * C;
+                    const double bj = bvec[j];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = w * 16 + (lane >> 4) * 4 + r;
+                        const int st = rstep[row];
+                        if (st < 0) continue;
+                        const int64_t n = rnode[row];
+                        double yh = accd[t][r] + bj;
+                        if (sc.scale) {
+                            // tsl inverse_transform: x * (scale + epsilon) + bias, the sum rounded to the scaler's fp32
+                            const float s1 = sc.scale[n * sc.sc_ns + c] + 5e-8f;
+                            yh = yh * (double)s1 + (double)sc.bias[n * sc.sc_ns + c];
+                        }
+                        if (sc.yhat)
+                            sc.yhat[((((int64_t)g * n_steps + rsidx[row]) * H + l) * n_nodes + n) * C + c] = (float)yh;
+                        if (sc.y) {
+                            const int64_t ts = (int64_t)st + l + 1;
+                            const bool m = sc.mask ? sc.mask[ts * sc.m_ss + n * sc.m_ns + c * sc.m_cs] != 0 : true;
+                            if (m) {
+                                const float yt = sc.y[ts * sc.y_ss + n * sc.y_ns + c];
+                                const double e = yh - (double)yt;
+                                sums[0] += fabs(e);
+                                sums[1] += e * e;
+                                sums[2] += fabs(e / (double)(yt + 5e-8f));   // tsl masked_mape: y + epsilon in fp32
+                                sums[3] += 1.0;
+                            }
+                        }
+                    }
+                }
+                if (sc.y) {                                  // the wave's four row groups, then one slot per wave
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        sums[q] += __shfl_xor(sums[q], 16);
+                        sums[q] += __shfl_xor(sums[q], 32);
+                        if (lane < 16) red[((w * PW) + 16 * t + lane) * 4 + q] = sums[q];
+                    }
+                }
+            }
+            if (sc.y) {
+                __syncthreads();
+                const bool first = rb == (int64_t)blockIdx.x;    // the workgroup's first row block stores its slab
+                for (int e = tid; e < PW * 4; e += 256) {
+                    const double s = ((red[e] + red[PW * 4 + e]) + red[2 * PW * 4 + e]) + red[3 * PW * 4 + e];
+                    double* d = part + ((int64_t)blockIdx.x * JP + j0) * 4 + e;
+                    *d = first ? s : *d + s;
+                }
+            }
+        }
+    }
+}
+
+// sums[g][l][q] += sum over workgroups, then channels, in order (the caller's sums accumulate over calls)
+__global__ void ridge_path_final_kernel(const double* __restrict__ part, int n_blocks, int jp, int GH, int C,
+                                        double* __restrict__ sums) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= GH * 4) return;
+    const int gl = e >> 2, q = e & 3;
+    double s = 0.0;
+    for (int b = 0; b < n_blocks; ++b)
+        for (int c = 0; c < C; ++c) s += part[((int64_t)b * jp + gl * C + c) * 4 + q];
+    sums[e] += s;
+}
+
+
 // ------------------------------------------------------------------ host side
 int parse_segs(const int64_t* segs, int32_t n_segs, Segs& S, const char* what) {
     SGP_REQUIRE(segs, "%s: null pointer (segment table)", what);
@@ -533,6 +709,32 @@ int64_t predict_grid(int64_t n_rows) {
     const int64_t nrb = predict_blocks(n_rows);
     return nrb < PGRID ? nrb : PGRID;
 }
+
+// alpha path: 16-column tiles of all G x H x C columns, dealt evenly to the fewest passes of at most QT_MAX tiles
+struct PathForm {
+    int tiles, tp, passes, panels;
+    int64_t grid, trips, lds;
+};
+
+int path_form(int64_t n_rows, int n_cols, int n_out, int n_alphas, PathForm& f, const char* what) {
+    SGP_REQUIRE(n_rows >= 1 && n_cols >= 1 && n_cols <= 16384, "%s: bad size (%lld rows, %d columns)", what,
+                (long long)n_rows, (int)n_cols);
+    SGP_REQUIRE(n_alphas >= 1 && n_alphas <= QG_MAX, "%s: %d alphas (1 .. %d)", what, (int)n_alphas, QG_MAX);
+    SGP_REQUIRE(n_out >= 1 && n_out <= QHC_MAX, "%s: horizon x channels must be 1 .. %d", what, QHC_MAX);
+    SGP_REQUIRE((int64_t)n_alphas * n_out <= QJ_MAX, "%s: %d alphas x %d outputs (at most %d columns of W)", what,
+                (int)n_alphas, (int)n_out, QJ_MAX);
+    f.tiles = (n_alphas * n_out + 15) / 16;
+    f.passes = (f.tiles + QT_MAX - 1) / QT_MAX;
+    f.tp = (f.tiles + f.passes - 1) / f.passes;
+    f.panels = predict_dpad(n_cols) / PKB;
+    f.grid = predict_grid(n_rows);
+    f.trips = (predict_blocks(n_rows) + f.grid - 1) / f.grid;
+    const int pw = 16 * f.tp;
+    f.lds = (int64_t)PRB * PLD * 4 + (int64_t)PKB * path_wld(pw) * 4 + (int64_t)4 * pw * 4 * 8;
+    return 0;
+}
+
+int64_t path_work_bytes(const PathForm& f) { return f.grid * f.passes * f.tp * 16 * 4 * 8; }
 
 }  // namespace
 
@@ -691,6 +893,79 @@ int sgp_ridge_predict_score_f32(const int64_t* segs, int32_t n_segs, const int32
     if (!sums) return 0;
     hipLaunchKernelGGL(ridge_score_final_kernel, dim3(1), dim3(256), 0, st, part, (int)grid, 16 * nt, (int)horizon,
                        (int)channels, sums);
+    return sgp::check_launch(what);
+}
+
+int64_t sgp_ridge_path_workspace_bytes(int64_t n_rows, int32_t n_cols, int32_t n_out, int32_t n_alphas) {
+    PathForm f;
+    if (path_form(n_rows, n_cols, n_out, n_alphas, f, "sgp_ridge_path_workspace_bytes")) return -1;
+    return path_work_bytes(f);
+}
+
+int sgp_ridge_path_form(int64_t n_rows, int32_t n_cols, int32_t n_out, int32_t n_alphas, int64_t* out) {
+    const char* what = "sgp_ridge_path_form";
+    SGP_REQUIRE(out, "%s: null pointer", what);
+    PathForm f;
+    if (int rc = path_form(n_rows, n_cols, n_out, n_alphas, f, what)) return rc;
+    out[0] = f.tiles;
+    out[1] = f.tp;
+    out[2] = f.passes;
+    out[3] = f.grid;
+    out[4] = f.trips;
+    out[5] = f.panels;
+    out[6] = f.lds;
+    return 0;
+}
+
+int sgp_ridge_predict_score_path_f32(const int64_t* segs, int32_t n_segs, const int32_t* steps, int64_t n_steps,
+                                     int64_t n_nodes, const float* W, const double* b, int32_t n_alphas,
+                                     int32_t horizon, int32_t channels,
+                                     const float* scale, const float* bias, int64_t sc_node_stride,
+                                     const float* y, int64_t y_ss, int64_t y_ns,
+                                     const uint8_t* mask, int64_t m_ss, int64_t m_ns, int64_t m_cs,
+                                     float* yhat, double* sums, void* work, int64_t work_bytes, sgp_stream_t stream) {
+    const char* what = "sgp_ridge_predict_score_path_f32";
+    Segs S;
+    if (int rc = parse_segs(segs, n_segs, S, what)) return rc;
+    if (int rc = check_rows(steps, n_steps, n_nodes, what)) return rc;
+    SGP_REQUIRE(W && b && work, "%s: null pointer", what);
+    SGP_REQUIRE((scale == nullptr) == (bias == nullptr), "%s: scale and bias go together", what);
+    SGP_REQUIRE((y == nullptr) == (sums == nullptr), "%s: y and sums go together", what);
+    SGP_REQUIRE(y || yhat, "%s: nothing to compute (no y and no yhat)", what);
+    SGP_REQUIRE(horizon >= 1 && channels >= 1 && (int64_t)horizon * channels <= QHC_MAX,
+                "%s: horizon x channels must be 1 .. %d", what, QHC_MAX);
+    SGP_REQUIRE(sc_node_stride >= 0 && y_ss >= 0 && y_ns >= 0 && m_ss >= 0 && m_ns >= 0 && m_cs >= 0,
+                "%s: negative stride", what);
+    const int64_t n_rows = n_steps * n_nodes;
+    PathForm f;
+    if (int rc = path_form(n_rows, S.ncols, horizon * channels, n_alphas, f, what)) return rc;
+    SGP_REQUIRE(work_bytes >= path_work_bytes(f), "%s: workspace of %lld bytes is too small", what,
+                (long long)work_bytes);
+    Score sc{scale, bias, sc_node_stride, y, y_ss, y_ns, mask, m_ss, m_ns, m_cs, yhat};
+    hipStream_t st = (hipStream_t)stream;
+    double* part = static_cast<double*>(work);
+#define SGP_RIDGE_PATH_LAUNCH(TP)                                                                                      \
+    case TP:                                                                                                           \
+        hipLaunchKernelGGL(ridge_path_kernel<TP>, dim3((unsigned)f.grid), dim3(256), (size_t)f.lds, st, S, steps,     \
+                           n_nodes, n_steps, n_rows, W, b, (int)n_alphas, (int)horizon, (int)channels, f.passes,      \
+                           f.panels, sc, part);                                                                        \
+        break
+    switch (f.tp) {
+        SGP_RIDGE_PATH_LAUNCH(1);
+        SGP_RIDGE_PATH_LAUNCH(2);
+        SGP_RIDGE_PATH_LAUNCH(3);
+        SGP_RIDGE_PATH_LAUNCH(4);
+        SGP_RIDGE_PATH_LAUNCH(5);
+        SGP_RIDGE_PATH_LAUNCH(6);
+        SGP_RIDGE_PATH_LAUNCH(7);
+        default: SGP_RIDGE_PATH_LAUNCH(8);
+    }
+#undef SGP_RIDGE_PATH_LAUNCH
+    if (int rc = sgp::check_launch(what)) return rc;
+    if (!sums) return 0;
+    const int gh = n_alphas * horizon;
+    hipLaunchKernelGGL(ridge_path_final_kernel, dim3((unsigned)((gh * 4 + 255) / 256)), dim3(256), 0, st, part,
+                       (int)f.grid, f.passes * f.tp * 16, gh, (int)channels, sums);
     return sgp::check_launch(what);
 }
 

@@ -2542,3 +2542,40 @@ def ridge_predict_score(segs, steps, n_nodes, w, b, horizon, channels, scale=Non
                                            P(scale), P(bias), sc_node_stride, P(y), *ys, P(mask), *ms,
                                            P(yhat), P(sums), ws.data_ptr(), ws.numel() * 8, _stream(steps)),
            "sgp_ridge_predict_score_f32")
+
+
+_RIDGE_PATH_FORM_KEYS = ("tiles", "tiles_per_pass", "passes", "grid", "blocks_per_wg", "panels", "lds_bytes")
+
+
+def ridge_path_form(n_rows, n_cols, n_out, n_alphas):
+    """The launch form of ``ridge_predict_score_path`` for these sizes (``n_out`` = horizon x channels), as a dict (host
+    only: ``sgp_ridge_path_form``).  ValueError on a size the entry refuses."""
+    out = (c_i64 * len(_RIDGE_PATH_FORM_KEYS))()
+    rc = load().sgp_ridge_path_form(int(n_rows), int(n_cols), int(n_out), int(n_alphas), ctypes.addressof(out))
+    if rc == SGP_EINVAL:
+        raise ValueError(f"ridge_path_form: {load().sgp_last_error().decode()}")
+    _check(rc, "sgp_ridge_path_form")
+    return {k: int(out[i]) for i, k in enumerate(_RIDGE_PATH_FORM_KEYS)}
+
+
+@_on_device
+def ridge_predict_score_path(segs, steps, n_nodes, w, b, n_alphas, horizon, channels, scale=None, bias=None,
+                             sc_node_stride=0, y=None, mask=None, yhat=None, sums=None):
+    """``w`` [D, G * H * C] fp32, ``b`` [G * H * C] fp64, ``yhat`` [G, S, H, N, C], ``sums`` [G, H, 4] fp64: the kernel
+    ADDS into ``sums``.  ``y`` / ``mask`` as for ``ridge_predict_score``."""
+    lib = require_gpu()
+    n_rows, n_cols = steps.numel() * n_nodes, sum(s[3] * s[5] for s in segs)
+    nbytes = lib.sgp_ridge_path_workspace_bytes(n_rows, n_cols, horizon * channels, n_alphas)
+    if nbytes < 0:
+        raise ValueError(f"ridge readout path: {lib.sgp_last_error().decode()}")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=steps.device)
+    P = lambda t: t.data_ptr() if t is not None else None
+    ys = (y.stride(0), y.stride(1)) if y is not None else (0, 0)
+    ms = (mask.stride(0), mask.stride(1), mask.stride(2)) if mask is not None else (0, 0, 0)
+    rc = lib.sgp_ridge_predict_score_path_f32(_ridge_table(segs), len(segs), steps.data_ptr(), steps.numel(), n_nodes,
+                                              w.data_ptr(), b.data_ptr(), n_alphas, horizon, channels,
+                                              P(scale), P(bias), sc_node_stride, P(y), *ys, P(mask), *ms,
+                                              P(yhat), P(sums), ws.data_ptr(), ws.numel() * 8, _stream(steps))
+    if rc == SGP_EINVAL:
+        raise ValueError(f"sgp_ridge_predict_score_path_f32: {lib.sgp_last_error().decode()}")
+    _check(rc, "sgp_ridge_predict_score_path_f32")

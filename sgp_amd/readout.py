@@ -13,7 +13,9 @@ columns are slices of the device tensors (include/sgp_amd.h, "Ridge readout") --
 * one Cholesky factorisation of the D x D feature block and a solve with all H x C right-hand sides, fp64 on the
   host (D^3 / 3 flop: 3e8 for D = 963, off the hot path), falling back the way sklearn does (cholesky -> svd);
 * ``sgp_ridge_predict_score_f32``: one pass over the val / test rows for every lag, with tsl's inverse transform and
-  masked sums in the epilogue.
+  masked sums in the epilogue;
+* ``sgp_ridge_predict_score_path_f32``: the same pass for a whole path of alphas solved from the one Gram
+  (:meth:`RidgeReadout.solve_path`, :class:`RidgePath`; ``closed_form_readout(l2_reg=[...])`` selects among them).
 
 There is no CPU fallback: CPU tensors raise.  Embeddings that live on the host are staged in step chunks through
 :meth:`RidgeReadout.accumulate` + :meth:`RidgeReadout.solve` (the Gram is additive; the shift is fixed by the first
@@ -55,6 +57,31 @@ def ridge_solve(gxx, gxy, alpha):
     keep = (s > 1e-15) & (lam > D * _F64_EPS * float(lam.max()))
     dinv = torch.where(keep, 1.0 / (lam + float(alpha)), torch.zeros_like(lam))
     return V @ (dinv[:, None] * (V.T @ gxy))
+
+
+MAX_ALPHAS = 64            # include/sgp_amd.h: sgp_ridge_predict_score_path_f32
+
+
+def _check_alphas(alphas):
+    """The alphas of a path as a list of floats: 1 .. MAX_ALPHAS finite, non-negative values."""
+    alphas = alphas.tolist() if hasattr(alphas, "tolist") else alphas
+    alphas = [float(a) for a in (alphas if isinstance(alphas, (list, tuple)) else [alphas])]
+    if not alphas:
+        raise ValueError("ridge path: no alphas")
+    if len(alphas) > MAX_ALPHAS:
+        raise ValueError(f"ridge path: {len(alphas)} alphas, more than {MAX_ALPHAS}")
+    for a in alphas:
+        if not (a >= 0.0 and a != float("inf")):
+            raise ValueError(f"ridge path: alpha {a} is negative or not finite")
+    return alphas
+
+
+def ridge_solve_path(gxx, gxy, alphas):
+    """``[G, D, M]`` fp64: slice g is ``ridge_solve(gxx, gxy, alphas[g])`` bit for bit (one factorisation per alpha, each
+    with ridge_solve's own choice between Cholesky and the eigen fallback; 15 ms each at D = 963)."""
+    gxx = gxx.double().cpu()
+    gxy = gxy.double().cpu()
+    return torch.stack([ridge_solve(gxx, gxy, a) for a in _check_alphas(alphas)])
 
 
 def gram_to_coef(gram, n_rows, shift, n_features, alpha, fit_intercept=True):
@@ -239,6 +266,17 @@ class RidgeReadout:
         self.n_samples_ = self._n
         return self
 
+    def solve_path(self, alphas):
+        """The readouts of every alpha of ``alphas`` from the accumulated Gram, as a :class:`RidgePath`.  This readout's
+        own ``alpha``, ``coef_`` and device weights are left as they are."""
+        alphas = _check_alphas(alphas)
+        if self._gram is None:
+            raise RuntimeError("ridge readout: nothing accumulated")
+        g = self._gram.double().cpu()                       # one copy for every alpha
+        shift = self._shift.cpu() if self._shift is not None else None
+        sol = [gram_to_coef(g, self._n, shift, self._lay.D, a, self.fit_intercept) for a in alphas]
+        return RidgePath(self, alphas, torch.stack([w for w, _ in sol]), torch.stack([b for _, b in sol]))
+
     # -- predict / score
     def _predict_layout(self, segments, steps):
         if not hasattr(self, "coef_"):
@@ -320,6 +358,132 @@ def metrics_from_sums(sums):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- alpha path
+def _score_operands(y_raw, mask, scaler, steps_h, N, C, H, dev):
+    """(y, mask, scale, bias, scaler node stride) as the scoring kernels take them (the checks of RidgeReadout.score)."""
+    if not torch.is_tensor(y_raw) or y_raw.dim() != 3 or y_raw.shape[1:] != (N, C):
+        raise ValueError(f"ridge readout: y_raw must be [T, {N}, {C}]")
+    if int(steps_h.max()) + H >= y_raw.shape[0]:
+        raise ValueError("ridge readout: steps + horizon reach past the end of y_raw")
+    if not y_raw.is_cuda:
+        raise RuntimeError("sgp_amd's ridge readout needs its tensors on an MI355X and has no CPU fallback")
+    y = y_raw.float()
+    if C > 1 and y.stride(2) != 1:
+        y = y.contiguous()
+    m = None
+    if mask is not None:
+        m = torch.as_tensor(mask).to(device=dev, dtype=torch.uint8)
+        if m.dim() != 3 or m.shape[0] != y.shape[0] or m.shape[1] != N or m.shape[2] not in (1, C):
+            raise ValueError(f"ridge readout: mask must be [T, {N}, {C} or 1]")
+        m = m.contiguous().expand(-1, -1, C)                 # channel stride 0 when broadcast
+    sc = bi = None
+    sc_ns = 0
+    if scaler is not None:
+        sc, sc_ns = _scaler_param(scaler.scale, N, C, dev)
+        bi, bi_ns = _scaler_param(scaler.bias, N, C, dev)
+        if bi_ns != sc_ns:
+            bi = bi.expand(N, C).contiguous() if bi_ns == 0 else bi
+            sc = sc.expand(N, C).contiguous() if sc_ns == 0 else sc
+            sc_ns = C
+    return y, m, sc, bi, sc_ns
+
+
+class RidgePath:
+    """The readouts of G alphas solved from one Gram (:meth:`RidgeReadout.solve_path`), scored together in one pass
+    over the embedding (``sgp_ridge_predict_score_path_f32``).
+
+    ``alphas`` (list of floats); ``coef_path_ [G, H, D, C]`` and ``intercept_path_ [G, H, C]``: slice g is the
+    ``coef_`` / ``intercept_`` of ``RidgeReadout(alphas[g])`` solved on the same Gram, bit for bit."""
+
+    def __init__(self, parent, alphas, W, b):
+        lay = parent._lay
+        self.alphas = list(alphas)
+        self.fit_intercept = parent.fit_intercept
+        self._lay, self._key, self._n = lay, parent._key, parent._n
+        H = lay.tseg[5] if lay.tseg is not None else 1
+        G, D, M = W.shape
+        C = M // H
+        self.horizon, self.channels, self.plain = H, C, parent._key[3]
+        self._w, self._b = W, b                               # kernel order: [G, D, H * C], [G, H * C], fp64, host
+        dev = parent._gram.device
+        # the kernel's W [D, G * H * C]: column (g H + l) C + c
+        self._w_dev = W.float().permute(1, 0, 2).reshape(D, G * M).contiguous().to(dev)
+        self._b_dev = b.reshape(G * M).contiguous().to(dev)
+        user = torch.empty_like(W)
+        user[:, lay.perm] = W
+        self.coef_path_ = user.view(G, D, H, C).permute(0, 2, 1, 3).contiguous()
+        self.intercept_path_ = b.view(G, H, C).clone()
+        self.n_samples_ = parent._n
+
+    def __len__(self):
+        return len(self.alphas)
+
+    def _predict_layout(self, segments, steps):
+        lay = _Layout(segments, None, 0, steps, steps is None)
+        if lay.widths != list(self._lay.widths):
+            raise ValueError(f"ridge readout: segment widths {lay.widths}, fitted on {self._lay.widths}")
+        return lay, lay.on_device()
+
+    def predict(self, segments, steps=None):
+        """Predictions of every alpha in the targets' (preprocessed) scale: ``[G, S, H, N, C]``; ``[G, R, M]`` for the
+        plain case."""
+        lay, steps_d = self._predict_layout(segments, steps)
+        G, S, N, H, C = len(self), steps_d.numel(), lay.n_nodes, self.horizon, self.channels
+        yhat = torch.empty(G, S, H, N, C, dtype=torch.float32, device=steps_d.device)
+        hip.ridge_predict_score_path(lay.segs, steps_d, N, self._w_dev, self._b_dev, G, H, C, yhat=yhat)
+        return yhat.view(G, S, C) if steps is None else yhat
+
+    def score(self, segments, steps, y_raw, mask=None, scaler=None, sums=None, return_pred=False):
+        """:meth:`RidgeReadout.score` for every alpha in one pass: ``mae`` / ``mse`` / ``mape`` / ``count`` are
+        ``[G, H]`` fp64 tensors, ``overall`` a list of G dicts, ``sums`` the device ``[G, H, 4]`` tensor of masked sums.
+        Passing the ``sums`` of an earlier call adds this call's rows to it (chunks staged from the host); the metrics
+        returned then cover everything accumulated."""
+        lay, steps_d = self._predict_layout(segments, steps)
+        G, S, N, H, C = len(self), steps_d.numel(), lay.n_nodes, self.horizon, self.channels
+        dev = steps_d.device
+        y, m, sc, bi, sc_ns = _score_operands(y_raw, mask, scaler, lay.steps_h, N, C, H, dev)
+        if sums is None:
+            sums = torch.zeros(G, H, 4, dtype=torch.float64, device=dev)
+        elif (not torch.is_tensor(sums) or sums.shape != (G, H, 4) or sums.dtype != torch.float64
+              or sums.device != dev or not sums.is_contiguous()):
+            raise ValueError(f"ridge path: sums must be the contiguous float64 [{G}, {H}, 4] tensor of an earlier score()")
+        yhat = torch.empty(G, S, H, N, C, dtype=torch.float32, device=dev) if return_pred else None
+        hip.ridge_predict_score_path(lay.segs, steps_d, N, self._w_dev, self._b_dev, G, H, C, sc, bi, sc_ns,
+                                     y=y, mask=m, yhat=yhat, sums=sums)
+        per = [metrics_from_sums(s) for s in sums.cpu()]
+        out = {k: torch.stack([p[k] for p in per]) for k in ("mae", "mse", "mape", "count")}
+        out["overall"] = [p["overall"] for p in per]
+        out["sums"] = sums
+        if return_pred:
+            out["pred"] = yhat
+        return out
+
+    @staticmethod
+    def best(scores, metric="mae", per_lag=False):
+        """The index of the alpha with the smallest overall ``metric`` of a :meth:`score` result (``per_lag``: a list of
+        H indices, one per lag).  Ties go to the smallest index."""
+        if per_lag:
+            m = scores[metric]
+            return [min(range(m.shape[0]), key=lambda g: float(m[g, l])) for l in range(m.shape[1])]
+        vals = [o[metric] for o in scores["overall"]]
+        return min(range(len(vals)), key=lambda g: vals[g])
+
+    def readout(self, g):
+        """A fitted ``RidgeReadout(alphas[g])``: coefficients and device weights taken from the path, no further solve
+        (it holds no Gram: ``accumulate`` starts a new fit)."""
+        g = range(len(self))[g]
+        r = RidgeReadout(alpha=self.alphas[g], fit_intercept=self.fit_intercept)
+        r._lay, r._key = self._lay, self._key
+        r.horizon, r.channels, r.plain = self.horizon, self.channels, self.plain
+        dev = self._w_dev.device
+        r._w_dev = self._w[g].float().contiguous().to(dev)
+        r._b_dev = self._b[g].contiguous().to(dev)
+        r.coef_ = self.coef_path_[g].clone()
+        r.intercept_ = self.intercept_path_[g].clone()
+        r.n_samples_ = self.n_samples_
+        return r
+
+
 # ---------------------------------------------------------------------------------------------- the driver body
 def _as_tensor(x):
     return x if torch.is_tensor(x) else torch.as_tensor(x)
@@ -331,13 +495,22 @@ def _steps(split, horizon):
     return s[:-horizon] if horizon > 0 else s
 
 
+def _is_sequence(x):
+    return isinstance(x, (list, tuple)) or (hasattr(x, "ndim") and x.ndim >= 1)
+
+
 def closed_form_readout(dataset, train_steps, val_steps, test_steps, horizon, l2_reg=0.0):
     """run_closed_form.py:169-247 on the device.  ``dataset``: the duck-typed interface ``encode_dataset`` uses
     after ``encode_dataset(..., return_device=True)`` -- ``get_tensors``, ``scalers['data']`` (``bias``,
     ``scale``), ``mask`` and ``encoded_x`` on the device.  The split arguments are the data module's step slices
     (``dm.train_slice`` ...); their last ``horizon`` steps are dropped as in the reference.  Returns
     ``{'val': ..., 'test': ...}``, each with per-lag ``mae`` / ``mse`` / ``mape`` ([H] tensors) and ``overall``,
-    and logs the reference's lines."""
+    and logs the reference's lines.
+
+    ``l2_reg`` may be a sequence of alphas (the sweep the reference's users do by hand over ``--l2-reg``): one Gram,
+    one :meth:`RidgeReadout.solve_path`, one scoring pass over the val steps for all of them; the alpha of the smallest
+    overall val MAE is selected, its metrics go out under the keys above, and ``alpha`` (the selected one), ``alphas``
+    and ``val_path`` (the :meth:`RidgePath.score` of every candidate) are added."""
     enc = getattr(dataset, "encoded_x", None)
     if enc is None:
         enc = dataset.exogenous["encoded_x"]
@@ -352,11 +525,25 @@ def closed_form_readout(dataset, train_steps, val_steps, test_steps, horizon, l2
     data = _as_tensor(data).to(dev, torch.float32).contiguous()
     raw = _as_tensor(raw).to(dev, torch.float32).contiguous()
     mask = _as_tensor(dataset.mask)
-    model = RidgeReadout(alpha=l2_reg).fit([data, enc], data, _steps(train_steps, horizon), horizon)
     scaler = dataset.scalers["data"]
     out = {}
-    for name, split in (("val", val_steps), ("test", test_steps)):
-        out[name] = model.score([data, enc], _steps(split, horizon), raw, mask, scaler)
+    if _is_sequence(l2_reg):
+        # one Gram, one solve per alpha, one pass over the val rows for all of them; the test rows for the selected one
+        alphas = _check_alphas(l2_reg)
+        path = RidgeReadout(alpha=alphas[0]).accumulate([data, enc], data, _steps(train_steps, horizon),
+                                                        horizon).solve_path(alphas)
+        val = path.score([data, enc], _steps(val_steps, horizon), raw, mask, scaler)
+        best = path.best(val)
+        for g, a in enumerate(alphas):
+            logger.info(f"l2_reg {a:g}: val_mae {val['overall'][g]['mae']:.4f}" + (" (selected)" if g == best else ""))
+        model = path.readout(best)
+        out["val"] = {k: val[k][best] for k in ("mae", "mse", "mape", "count", "overall")}
+        out["test"] = model.score([data, enc], _steps(test_steps, horizon), raw, mask, scaler)
+        out.update(alpha=alphas[best], alphas=alphas, val_path=val)
+    else:
+        model = RidgeReadout(alpha=l2_reg).fit([data, enc], data, _steps(train_steps, horizon), horizon)
+        for name, split in (("val", val_steps), ("test", test_steps)):
+            out[name] = model.score([data, enc], _steps(split, horizon), raw, mask, scaler)
     for lag in range(1, horizon + 1):
         for metric in ("mae", "mse", "mape"):
             for name in ("val", "test"):
