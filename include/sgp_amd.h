@@ -1575,6 +1575,50 @@ int sgp_csr_take_rows_f32(const int32_t* a_rowptr, const int32_t* a_col, const f
                           int32_t* rowptr, int32_t* col, float* val, int64_t capacity, int32_t* nnz, int32_t* err, void* ws,
                           int64_t ws_bytes, sgp_stream_t stream);
 
+/* ------------------------------------- AZ-whiteness test of residuals ---
+ * The integer core of tsl's az_whiteness_test (whiteness.hip).  x is an fp32 series [steps, nodes, feat] with unit
+ * feature stride and the given step / node strides (in elements); mask: NULL (all valid) or bytes of the same shape
+ * with strides of their own (non-zero = valid).  A masked-out entry is never looked at; a NaN / inf under a valid one
+ * is counted into *nonfinite.  The prepared edge list (edge_u < edge_v, int32, sorted) comes from
+ * sgp_amd.whiteness.prepare_graph; an endpoint outside [0, nodes) is compared unsigned and skipped.  Every sum is an
+ * int64 that the entries ADD to (the caller zeroes the state once; consecutive time chunks accumulate); integer
+ * atomics only, so the state does not depend on the launch shape or the run.
+ *
+ * sgp_az_pack_f32: planes [3, feat, nodes, words] uint64, words = ceil(steps / 64): bit b of word w describes step
+ *   64 w + b: plane 0 negative (the sign bit), 1 non-zero and valid, 2 valid; the high bits of a ragged last word are
+ *   zero.  The same launch adds the temporal sums st[f] = sum sgn(x[t] x[t - 1]) and mt[f] = #{both valid} over the
+ *   pairs inside the chunk (each word against itself shifted by one bit, the bit shifted in being the step below the
+ *   word) and, with carry_in, the pair across the chunk boundary.  carry_in / carry_out: NULL or [nodes * feat] bytes,
+ *   bit 0 | 1 | 2 = the three planes' bit of the step before this chunk / of its last step (two different buffers).
+ * sgp_az_edge_counts: s[e, f] += sum_t sgn(x[t, u, f] x[t, v, f]) = popc(nz) - 2 popc((neg_u ^ neg_v) & nz) with
+ *   nz = nz_u & nz_v, and m[e, f] += popc(valid_u & valid_v), over the `words` words of the planes.  regime 0 "words":
+ *   a wave per (edge, feature), lanes along the words; regime 1 "edges": a lane per (feature, edge) walks its words
+ *   (sgp_amd.whiteness.launch_plan chooses).
+ * sgp_az_direct_f32: the general form, no planes.  multivariate != 0: s[e] += sum_t sgn(sum_f x[t, u, f] x[t, v, f])
+ *   with masked-out entries as 0, the dot product in fp64 (f ascending; fp32 products are exact there), m[e] += #{t:
+ *   some feature of u and some feature of v valid}, st[0] / mt[0] likewise over (t - 1, t) with mt counting valid
+ *   pairs over the features as well (the reference's count).  multivariate == 0: one test per feature, s / m
+ *   [n_edges, feat], st / mt [feat]: the integers of the bit-plane path.  A lane owns an edge (edge, feature) over a
+ *   slab of `slab` steps; node tiles behind the edge tiles take the temporal pairs.  prev_x [nodes, feat] fp32 /
+ *   prev_mask bytes (contiguous): the step before this chunk, or NULL.
+ * sgp_az_finish: rec [n_tests, 5] fp64 = Ct_s = sum_e w_e s[e, k] | W_s = sum_e w_e^2 m[e, k] | st[k] | mt[k] |
+ *   *nonfinite, the fp64 sums in one fixed order (thread-strided partials, then a halving tree).  The host reads rec
+ *   once and forms the statistic.
+ *   replaces az_whiteness_test / _az_whiteness_test (tsl/ops/test.py:81-288) */
+int sgp_az_pack_f32(const float* x, int64_t x_step_stride, int64_t x_node_stride, const uint8_t* mask,
+                    int64_t mask_step_stride, int64_t mask_node_stride, int64_t steps, int64_t nodes, int32_t feat,
+                    const uint8_t* carry_in, uint8_t* carry_out, uint64_t* planes, int64_t* st, int64_t* mt,
+                    int64_t* nonfinite, sgp_stream_t stream);
+int sgp_az_edge_counts(const uint64_t* planes, const int32_t* edge_u, const int32_t* edge_v, int64_t n_edges, int64_t nodes,
+                       int32_t feat, int64_t words, int32_t regime, int64_t* s, int64_t* m, sgp_stream_t stream);
+int sgp_az_direct_f32(const float* x, int64_t x_step_stride, int64_t x_node_stride, const uint8_t* mask,
+                      int64_t mask_step_stride, int64_t mask_node_stride, const float* prev_x, const uint8_t* prev_mask,
+                      int64_t steps, int64_t nodes, int32_t feat, int32_t multivariate, const int32_t* edge_u,
+                      const int32_t* edge_v, int64_t n_edges, int32_t slab, int64_t* s, int64_t* m, int64_t* st, int64_t* mt,
+                      int64_t* nonfinite, sgp_stream_t stream);
+int sgp_az_finish(const int64_t* s, const int64_t* m, const double* weight, int64_t n_edges, int32_t n_tests,
+                  const int64_t* st, const int64_t* mt, const int64_t* nonfinite, double* rec, sgp_stream_t stream);
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

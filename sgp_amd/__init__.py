@@ -22,5 +22,6 @@ from .predictors import Predictor, SubgraphPredictor
 from .sgp_preprocessing import (preprocess_adj, preprocess_dataset, reservoir_preprocessing_,
                                 sgp_spatial_embedding, sgp_spatial_support, window_spatial_embedding)
 from .utils import encode_dataset, self_normalizing_activation
+from .whiteness import AZWhiteness, AZWhitenessMultiTestResult, AZWhitenessTestResult, az_whiteness_test
 
 __version__ = "0.1.0"

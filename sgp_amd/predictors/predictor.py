@@ -266,3 +266,31 @@ class Predictor(nn.Module):
         for i, batch in self._take(batches, -1):
             self.test_step(batch, i)
         return self._epoch_log("test", self.test_metrics)
+
+    @torch.no_grad()
+    def whiteness(self, batches, edge_index, edge_weight=None, at=0, **test_args):
+        """The AZ-whiteness test (``sgp_amd.whiteness``) of the residuals ``y_hat[:, at] - y[:, at]`` at horizon step
+        ``at``, under ``mask[:, at]``: does the forecaster's error still carry structure in space or time?
+
+        Precondition: ``batches`` are consecutive, unshuffled, stride-1 windows, as the test loader produces them, so
+        that sample b of a batch is the time step after sample b - 1 and the batches follow each other; the temporal
+        part of the statistic pairs consecutive samples.  ``test_args``: ``multivariate``, ``lamb``,
+        ``edge_weight_temporal``.  The residual series is never assembled: every batch is one chunk of an
+        ``AZWhiteness``, whose result is returned."""
+        from ..whiteness import AZWhiteness
+        unknown = set(test_args) - {"multivariate", "lamb", "edge_weight_temporal"}
+        if unknown:
+            raise TypeError(f"whiteness: unexpected arguments {sorted(unknown)}")
+        self._require_gpu()
+        self.eval()
+        test = None
+        for _, batch in self._take(batches, -1):
+            y, y_hat, mask = self.predict_batch(batch, preprocess=False, postprocess=True, return_target=True)
+            res = y_hat[:, at] - y[:, at]
+            if test is None:
+                test = AZWhiteness(edge_index, edge_weight, num_nodes=res.shape[1], n_features=res.shape[2],
+                                   multivariate=test_args.get("multivariate", False))
+            test.update(res, None if mask is None else mask[:, at])
+        if test is None:
+            raise ValueError("whiteness: no batches")
+        return test.compute(test_args.get("lamb", 0.5), test_args.get("edge_weight_temporal"))
