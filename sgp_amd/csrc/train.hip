@@ -6,6 +6,7 @@
 //   sgp_masked_metrics_f32     one pass over y_hat, y, mask for the sums behind mae / mse / mape / mre of every horizon
 //                              step, added into a persistent [H, 6] fp64 state.
 //   sgp_masked_loss_f32 / _bwd MaskedMAE / MSE / MAPE as a loss, optionally at one horizon step.
+//   sgp_masked_*_nodes_f32     the same kernels where y / mask hold the root nodes of a sampled batch only.
 // Every reduction is a fixed tree over fixed partials: no float atomics, bit-identical from run to run.
 //
 // Chunk table (device, int64 [n_chunks][3]): (tensor id, element offset, length).  A chunk never crosses a tensor; its
@@ -158,18 +159,51 @@ __device__ __forceinline__ bool counts(bool m, float val, int mask_nans, int mas
     return m && !(mask_nans && isnan(val)) && !(mask_inf && isinf(val));
 }
 
+// Where the prediction of element `a` of y / mask lives: a policy, passed to the kernels by value, whose at(a, ah)
+// gives the address in y_hat, or false for an element that has none (it is skipped).  The unit walk, the order of the
+// sums and the partials do not depend on the policy, so the root-node path is bit-equal to the whole-batch path on
+// y_hat[..., tn, :].contiguous(): a documented property, held by the tests.
+struct WholeBatch {                         // y_hat has the shape of y: the element's own address
+    __device__ __forceinline__ bool at(long long a, long long& ah) const { ah = a; return true; }
+};
+
+enum { TN_ERR_RANGE = 1, TN_ERR_REPEAT = 2 };
+
+// y_hat is contiguous [B, H, nodes_all, C], y and mask are [B, H, roots, C], and root j sits at node tn[j] of y_hat
+template <class I>
+struct RootNodes {
+    const I* tn;
+    int* err;                               // bit TN_ERR_RANGE is set when tn[j] is no node
+    long long nodes_all, Rn;                // Rn = roots * C, whatever `at` makes of the walk's R
+    int channels;
+    // element a = (bh * roots + j) * C + c of y
+    __device__ __forceinline__ bool at(long long a, long long& ah) const {
+        long long bh, r;
+        if (((unsigned long long)a | (unsigned long long)Rn) >> 32) { bh = a / Rn; r = a - bh * Rn; }
+        else { const unsigned q = (unsigned)a / (unsigned)Rn; bh = q; r = (unsigned)a - q * (unsigned)Rn; }
+        const long long j = r / channels, c = r - j * channels;
+        const I id = tn[j];
+        if (!sgp::in_range(id, nodes_all)) { atomicOr(err, TN_ERR_RANGE); return false; }
+        ah = (bh * nodes_all + (long long)id) * channels + c;
+        return true;
+    }
+};
+
+template <class Where>
 __global__ __launch_bounds__(TR_THREADS) void masked_metrics_kernel(const float* __restrict__ yh, const float* __restrict__ y,
-                                                                    const unsigned char* __restrict__ mask, long long J,
-                                                                    long long H, long long R, long long nseg, Transform tr,
-                                                                    int mask_nans, int mask_inf, double* __restrict__ partial) {
+                                                                    const unsigned char* __restrict__ mask, Where where,
+                                                                    long long J, long long H, long long R, long long nseg,
+                                                                    Transform tr, int mask_nans, int mask_inf,
+                                                                    double* __restrict__ partial) {
     __shared__ double lds[MET_COLS * TR_WAVES];
     const long long u = blockIdx.x, h = u / nseg, seg = u - h * nseg;
     const long long j1 = (seg + 1) * MET_SEG < J ? (seg + 1) * MET_SEG : J;
     double s[MET_COLS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (long long j = seg * MET_SEG + threadIdx.x; j < j1; j += TR_THREADS) {
-        long long r;
+        long long r, ah;
         const long long a = addr_of(j, R, H, h, r);
-        const float t = y[a], d = inverse_transform(yh[a], tr, r) - t;
+        if (!where.at(a, ah)) continue;
+        const float t = y[a], d = inverse_transform(yh[ah], tr, r) - t;        // r / channels: the position in y
         const bool m = mask ? mask[a] != 0 : true;
         const float ad = fabsf(d);
         if (counts(m, ad, mask_nans, mask_inf)) { s[0] += (double)ad; s[1] += 1.0; s[2] += (double)(d * d); s[5] += (double)t; }
@@ -203,18 +237,28 @@ __device__ __forceinline__ float loss_value(int kind, float d, float t) {
     return kind == LOSS_MAE ? fabsf(d) : (kind == LOSS_MSE ? d * d : fabsf(d / t));
 }
 
+// d loss / d y_hat of one element: 0 when the masking rules drop it (m: its mask byte, true without a mask)
+__device__ __forceinline__ float loss_grad(int kind, float d, float t, bool m, int mask_nans, float scale) {
+    if (!counts(m, loss_value(kind, d, t), mask_nans, kind == LOSS_MAPE)) return 0.f;
+    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f * d);
+    return kind == LOSS_MAE ? scale * sgn : (kind == LOSS_MSE ? scale * 2.f * d : scale * sgn / fabsf(t));
+}
+
+// (H, R, h): without `at` one flat row (1, J, 0); with it, step `at` of [B, H, R]
+template <class Where>
 __global__ __launch_bounds__(TR_THREADS) void masked_loss_kernel(const float* __restrict__ yh, const float* __restrict__ y,
-                                                                 const unsigned char* __restrict__ mask, long long J,
-                                                                 long long H, long long R, long long h, int kind,
-                                                                 int mask_nans, double* __restrict__ partial) {
+                                                                 const unsigned char* __restrict__ mask, Where where,
+                                                                 long long J, long long H, long long R, long long h,
+                                                                 int kind, int mask_nans, double* __restrict__ partial) {
     __shared__ double lds[2 * TR_WAVES];
     const long long seg = blockIdx.x;
     const long long j1 = (seg + 1) * MET_SEG < J ? (seg + 1) * MET_SEG : J;
     double s[2] = {0.0, 0.0};
     for (long long j = seg * MET_SEG + threadIdx.x; j < j1; j += TR_THREADS) {
-        long long r;
+        long long r, ah;
         const long long a = addr_of(j, R, H, h, r);
-        const float t = y[a], val = loss_value(kind, yh[a] - t, t);
+        if (!where.at(a, ah)) continue;
+        const float t = y[a], val = loss_value(kind, yh[ah] - t, t);
         if (counts(mask ? mask[a] != 0 : true, val, mask_nans, kind == LOSS_MAPE)) { s[0] += (double)val; s[1] += 1.0; }
     }
     wg_sum_waves<TR_THREADS>(s, lds);
@@ -233,6 +277,10 @@ __global__ __launch_bounds__(TR_THREADS) void masked_loss_final_kernel(const dou
     }
 }
 
+// Two backward kernels, on purpose: this one walks the whole-batch gradient by scalars (256 lanes, at most 8192
+// workgroups), masked_loss_nodes_bwd_kernel below writes the full-size root-node gradient four wide (at most 2048
+// workgroups).  Merging them would change the launch shape, and with it the speed, of one training step or the other;
+// they share loss_grad, the one place the gradient of an element is written.
 __global__ void masked_loss_bwd_kernel(const float* __restrict__ yh, const float* __restrict__ y,
                                        const unsigned char* __restrict__ mask, long long n, long long H, long long R,
                                        long long at, int kind, int mask_nans, const float* __restrict__ gout,
@@ -241,38 +289,14 @@ __global__ void masked_loss_bwd_kernel(const float* __restrict__ yh, const float
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
         float g = 0.f;
         if (at < 0 || (e / R) % H == at) {
-            const float t = y[e], d = yh[e] - t;
-            if (counts(mask ? mask[e] != 0 : true, loss_value(kind, d, t), mask_nans, kind == LOSS_MAPE)) {
-                const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f * d);
-                g = kind == LOSS_MAE ? scale * sgn : (kind == LOSS_MSE ? scale * 2.f * d : scale * sgn / fabsf(t));
-            }
+            const float t = y[e];
+            g = loss_grad(kind, yh[e] - t, t, mask ? mask[e] != 0 : true, mask_nans, scale);
         }
         grad[e] = g;
     }
 }
 
-// ------------------------------------------------------------------------------------------------ the same, on root nodes
-// y_hat is contiguous [B, H, nodes_all, C]; y and mask are [B, H, roots, C] and root j sits at node tn[j] of y_hat.
-// The unit walk is the one above over the SLICED index space (R = roots * C), so thread, order and partials are those
-// of the kernels above on y_hat[..., tn, :].contiguous(); only the address of the prediction differs.
-enum { TN_ERR_RANGE = 1, TN_ERR_REPEAT = 2 };
-
-struct Nodes { long long nodes_all; int channels; };
-
-// address in y_hat of sliced element `a` = (bh * roots + j) * C + c; false (and bit 0 of err) when tn[j] is no node
-template <class I>
-__device__ __forceinline__ bool node_addr(long long a, long long R, const I* __restrict__ tn, const Nodes& nd,
-                                          int* __restrict__ err, long long& ah) {
-    long long bh, r;
-    if (((unsigned long long)a | (unsigned long long)R) >> 32) { bh = a / R; r = a - bh * R; }
-    else { const unsigned q = (unsigned)a / (unsigned)R; bh = q; r = (unsigned)a - q * (unsigned)R; }
-    const long long j = r / nd.channels, c = r - j * nd.channels;
-    const I id = tn[j];
-    if (!sgp::in_range(id, nd.nodes_all)) { atomicOr(err, TN_ERR_RANGE); return false; }
-    ah = (bh * nd.nodes_all + (long long)id) * nd.channels + c;
-    return true;
-}
-
+// ------------------------------------------------------------------------------------------------ root nodes: table, backward
 // inv[tn[j]] = j over a table the entry has filled with -1; atomicMax keeps the larger j of a node named twice
 template <class I>
 __global__ __launch_bounds__(TR_THREADS) void target_nodes_table_kernel(const I* __restrict__ tn, long long roots,
@@ -285,56 +309,6 @@ __global__ __launch_bounds__(TR_THREADS) void target_nodes_table_kernel(const I*
     }
 }
 
-template <class I>
-__global__ __launch_bounds__(TR_THREADS) void masked_metrics_nodes_kernel(const float* __restrict__ yh, const float* __restrict__ y,
-                                                                          const unsigned char* __restrict__ mask,
-                                                                          const I* __restrict__ tn, Nodes nd, long long J,
-                                                                          long long H, long long R, long long nseg, Transform tr,
-                                                                          int mask_nans, int mask_inf, int* __restrict__ err,
-                                                                          double* __restrict__ partial) {
-    __shared__ double lds[MET_COLS * TR_WAVES];
-    const long long u = blockIdx.x, h = u / nseg, seg = u - h * nseg;
-    const long long j1 = (seg + 1) * MET_SEG < J ? (seg + 1) * MET_SEG : J;
-    double s[MET_COLS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (long long j = seg * MET_SEG + threadIdx.x; j < j1; j += TR_THREADS) {
-        long long r, ah;
-        const long long a = addr_of(j, R, H, h, r);
-        if (!node_addr(a, R, tn, nd, err, ah)) continue;
-        const float t = y[a], d = inverse_transform(yh[ah], tr, r) - t;        // r / channels is the ROOT position
-        const bool m = mask ? mask[a] != 0 : true;
-        const float ad = fabsf(d);
-        if (counts(m, ad, mask_nans, mask_inf)) { s[0] += (double)ad; s[1] += 1.0; s[2] += (double)(d * d); s[5] += (double)t; }
-        const float q = fabsf(d / t);
-        if (counts(m, q, mask_nans, 1)) { s[3] += (double)q; s[4] += 1.0; }
-    }
-    wg_sum_waves<TR_THREADS>(s, lds);
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < MET_COLS; ++k) partial[u * MET_COLS + k] = s[k];
-}
-
-template <class I>
-__global__ __launch_bounds__(TR_THREADS) void masked_loss_nodes_kernel(const float* __restrict__ yh, const float* __restrict__ y,
-                                                                       const unsigned char* __restrict__ mask,
-                                                                       const I* __restrict__ tn, Nodes nd, long long J,
-                                                                       long long H, long long R, long long h, long long Rn,
-                                                                       int kind, int mask_nans, int* __restrict__ err,
-                                                                       double* __restrict__ partial) {
-    __shared__ double lds[2 * TR_WAVES];
-    const long long seg = blockIdx.x;
-    const long long j1 = (seg + 1) * MET_SEG < J ? (seg + 1) * MET_SEG : J;
-    double s[2] = {0.0, 0.0};
-    for (long long j = seg * MET_SEG + threadIdx.x; j < j1; j += TR_THREADS) {
-        long long r, ah;
-        const long long a = addr_of(j, R, H, h, r);                             // (H, R, h) as in sgp_masked_loss_f32
-        if (!node_addr(a, Rn, tn, nd, err, ah)) continue;                       // Rn = roots * C whatever `at` is
-        const float t = y[a], val = loss_value(kind, yh[ah] - t, t);
-        if (counts(mask ? mask[a] != 0 : true, val, mask_nans, kind == LOSS_MAPE)) { s[0] += (double)val; s[1] += 1.0; }
-    }
-    wg_sum_waves<TR_THREADS>(s, lds);
-    if (threadIdx.x == 0) { partial[2 * seg] = s[0]; partial[2 * seg + 1] = s[1]; }
-}
-
 // One element of the full gradient: row `n` of block bh = b * H + h, channel c, at flat address e of y_hat.
 __device__ __forceinline__ float loss_nodes_grad(const float* __restrict__ yh, const float* __restrict__ y,
                                                  const unsigned char* __restrict__ mask, const int* __restrict__ inv,
@@ -344,10 +318,8 @@ __device__ __forceinline__ float loss_nodes_grad(const float* __restrict__ yh, c
     const int j = inv[n];
     if (!sgp::in_range(j, roots) || !(at < 0 || bh % H == at)) return 0.f;
     const long long a = (bh * roots + j) * channels + c;
-    const float t = y[a], d = yh[e] - t;
-    if (!counts(mask ? mask[a] != 0 : true, loss_value(kind, d, t), mask_nans, kind == LOSS_MAPE)) return 0.f;
-    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f * d);
-    return kind == LOSS_MAE ? scale * sgn : (kind == LOSS_MSE ? scale * 2.f * d : scale * sgn / fabsf(t));
+    const float t = y[a];
+    return loss_grad(kind, yh[e] - t, t, mask ? mask[a] != 0 : true, mask_nans, scale);
 }
 
 // The whole gradient [B, H, nodes_all, C] in one pass: thread -> V consecutive elements (V = 4: one 16-byte store),
@@ -385,7 +357,7 @@ constexpr long long MAX_GRID = 2147483647LL;
 
 // ---- launch arithmetic of the root-node entries: the entries and sgp_masked_nodes_form both go through these
 constexpr long long NODES_BWD_CAP = 2048;       // workgroups of the backward: 8 of 256 threads on each of 256 CUs
-long long nodes_loss_J(long long batch, long long horizon, long long roots, long long channels, int at) {
+long long loss_J(long long batch, long long horizon, long long roots, long long channels, int at) {
     return at < 0 ? batch * horizon * roots * channels : batch * roots * channels;
 }
 int nodes_bwd_vec(long long n_all, bool aligned16) { return aligned16 && n_all >= 4 ? 4 : 1; }
@@ -396,6 +368,95 @@ long long nodes_bwd_trips(long long n_all, int vec) {
 }
 unsigned nodes_table_grid(long long roots) { return sgp::grid_for(roots, TR_THREADS, 1024); }
 bool index_ok(int index_bytes) { return index_bytes == 4 || index_bytes == 8; }
+
+// f(I{}) with I the index type of `index_bytes` (which index_ok has passed)
+template <class F>
+void with_index(int index_bytes, F&& f) {
+    if (index_bytes == 8) f((long long)0);
+    else f((int)0);
+}
+
+// ---- the host half of the loss / metrics entries.  `who` is the entry the caller used: it starts every message.
+// what every loss entry asks of (kind, at, mask_nans)
+int loss_args_ok(const char* who, int kind, int at, int horizon, int mask_nans) {
+    SGP_REQUIRE(kind >= LOSS_MAE && kind <= LOSS_MAPE, "%s: kind is 0 (mae), 1 (mse) or 2 (mape)", who);
+    SGP_REQUIRE(at >= -1 && (at < 0 || at < horizon), "%s: at outside the horizon", who);
+    SGP_REQUIRE(mask_nans == 0 || mask_nans == 1, "%s: mask_nans is 0 or 1", who);
+    return 0;
+}
+
+// The operands of [B, H, roots, C] y / mask against the prediction; nd is null in the whole-batch entries, whose
+// y_hat has the shape of y (they pass their row as `roots` where they have no node axis).
+struct NodesArg { const void* tn; int index_bytes; long long nodes_all; int* err; };
+struct Operands {
+    const float* y_hat; const float* y; const uint8_t* mask; const NodesArg* nd;
+    long long batch; int horizon; long long roots; int channels;
+};
+
+// the checks both routines below start with; the caller has tested its own pointers into `ptrs`
+int operands_ok(const char* who, const Operands& o, bool ptrs, bool sizes) {
+    SGP_REQUIRE(ptrs && o.y_hat && o.y && (!o.nd || (o.nd->tn && o.nd->err)), "%s: null pointer", who);
+    SGP_REQUIRE(sizes && o.batch >= 0 && o.horizon >= 0 && o.roots >= 0 && o.channels >= 0 && (!o.nd || o.nd->nodes_all >= 0),
+                "%s: bad size", who);
+    SGP_REQUIRE(!o.nd || index_ok(o.nd->index_bytes), "%s: index_bytes is 4 (int32) or 8 (int64)", who);
+    return 0;
+}
+
+// f(policy) with the "where is the prediction" policy of the operands
+template <class F>
+void with_where(const Operands& o, F&& f) {
+    if (!o.nd) return f(WholeBatch{});
+    with_index(o.nd->index_bytes, [&](auto i) {
+        using I = decltype(i);
+        f(RootNodes<I>{(const I*)o.nd->tn, o.nd->err, o.nd->nodes_all, o.roots * o.channels, o.channels});
+    });
+}
+
+// behind sgp_masked_metrics_f32 and sgp_masked_metrics_nodes_f32
+int masked_metrics_run(const char* who, const Operands& o, const float* scale, const float* bias, long long sc_node_stride,
+                       int mask_nans, int mask_inf, double* work, long long work_doubles, double* state,
+                       hipStream_t stream) {
+    if (int rc = operands_ok(who, o, work && state, sc_node_stride >= 0)) return rc;
+    SGP_REQUIRE((scale == nullptr) == (bias == nullptr), "%s: scale and bias come together", who);
+    SGP_REQUIRE((mask_nans == 0 || mask_nans == 1) && (mask_inf == 0 || mask_inf == 1), "%s: mask_nans / mask_inf are 0 or 1",
+                who);
+    const long long H = o.horizon, R = o.roots * o.channels, J = o.batch * R, nseg = units_of(J);
+    if (nseg == 0 || H == 0) return 0;
+    SGP_REQUIRE(nseg * H <= MAX_GRID, "%s: too many units", who);
+    SGP_REQUIRE(work_doubles >= nseg * H * MET_COLS, "%s: workspace too small", who);
+    const Transform tr = {scale, bias, sc_node_stride, o.channels};
+    with_where(o, [&](auto where) {
+        using Where = decltype(where);
+        hipLaunchKernelGGL(masked_metrics_kernel<Where>, dim3((unsigned)(nseg * H)), dim3(TR_THREADS), 0, stream, o.y_hat,
+                           o.y, o.mask, where, J, H, R, nseg, tr, mask_nans, mask_inf, work);
+    });
+    if (int rc = sgp::check_launch(who)) return rc;
+    hipLaunchKernelGGL(masked_metrics_final_kernel, dim3((unsigned)H), dim3(TR_THREADS), 0, stream, (const double*)work,
+                       nseg, state);
+    return sgp::check_launch("masked_metrics_final");
+}
+
+// behind sgp_masked_loss_f32 and sgp_masked_loss_nodes_f32; the final kernel runs on empty operands too (loss 0, count 0)
+int masked_loss_run(const char* who, const Operands& o, int kind, int at, int mask_nans, double* work,
+                    long long work_doubles, float* loss, double* count, hipStream_t stream) {
+    if (int rc = operands_ok(who, o, work && loss && count, true)) return rc;
+    if (int rc = loss_args_ok(who, kind, at, o.horizon, mask_nans)) return rc;
+    const long long J = loss_J(o.batch, o.horizon, o.roots, o.channels, at), nseg = units_of(J);
+    SGP_REQUIRE(nseg <= MAX_GRID, "%s: too many units", who);
+    SGP_REQUIRE(work_doubles >= 2 * nseg, "%s: workspace too small", who);
+    if (nseg > 0) {
+        // without `at` the tensor is one flat row; with it, step `at` of [B, H, R]
+        const long long H = at < 0 ? 1LL : (long long)o.horizon, R = at < 0 ? J : o.roots * o.channels, h = at < 0 ? 0LL : at;
+        with_where(o, [&](auto where) {
+            using Where = decltype(where);
+            hipLaunchKernelGGL(masked_loss_kernel<Where>, dim3((unsigned)nseg), dim3(TR_THREADS), 0, stream, o.y_hat, o.y,
+                               o.mask, where, J, H, R, h, kind, mask_nans, work);
+        });
+        if (int rc = sgp::check_launch(who)) return rc;
+    }
+    hipLaunchKernelGGL(masked_loss_final_kernel, dim3(1), dim3(TR_THREADS), 0, stream, (const double*)work, nseg, loss, count);
+    return sgp::check_launch("masked_loss_final");
+}
 
 }  // namespace
 
@@ -453,51 +514,20 @@ int sgp_masked_metrics_f32(const float* y_hat, const float* y, const uint8_t* ma
                            int64_t nodes, int32_t channels, const float* scale, const float* bias,
                            int64_t sc_node_stride, int32_t mask_nans, int32_t mask_inf, double* work,
                            int64_t work_doubles, double* state, sgp_stream_t stream) {
-    SGP_REQUIRE(y_hat && y && work && state, "sgp_masked_metrics_f32: null pointer");
-    SGP_REQUIRE(batch >= 0 && horizon >= 0 && nodes >= 0 && channels >= 0 && sc_node_stride >= 0,
-                "sgp_masked_metrics_f32: bad size");
-    SGP_REQUIRE((scale == nullptr) == (bias == nullptr), "sgp_masked_metrics_f32: scale and bias come together");
-    SGP_REQUIRE((mask_nans == 0 || mask_nans == 1) && (mask_inf == 0 || mask_inf == 1),
-                "sgp_masked_metrics_f32: mask_nans / mask_inf are 0 or 1");
-    const long long R = nodes * channels, J = batch * R, nseg = units_of(J);
-    if (nseg == 0 || horizon == 0) return 0;
-    SGP_REQUIRE(nseg * horizon <= MAX_GRID, "sgp_masked_metrics_f32: too many units");
-    SGP_REQUIRE(work_doubles >= nseg * horizon * MET_COLS, "sgp_masked_metrics_f32: workspace too small");
-    Transform tr = {scale, bias, sc_node_stride, channels};
-    hipLaunchKernelGGL(masked_metrics_kernel, dim3((unsigned)(nseg * horizon)), dim3(TR_THREADS), 0, (hipStream_t)stream,
-                       y_hat, y, mask, J, (long long)horizon, R, nseg, tr, mask_nans, mask_inf, work);
-    if (int rc = sgp::check_launch("masked_metrics")) return rc;
-    hipLaunchKernelGGL(masked_metrics_final_kernel, dim3((unsigned)horizon), dim3(TR_THREADS), 0, (hipStream_t)stream,
-                       (const double*)work, nseg, state);
-    return sgp::check_launch("masked_metrics_final");
+    return masked_metrics_run("sgp_masked_metrics_f32", {y_hat, y, mask, nullptr, batch, horizon, nodes, channels}, scale,
+                              bias, sc_node_stride, mask_nans, mask_inf, work, work_doubles, state, (hipStream_t)stream);
 }
 
 int64_t sgp_masked_loss_workspace_doubles(int64_t batch, int32_t horizon, int64_t row, int32_t at) {
     if (batch < 0 || horizon < 0 || row < 0) return -1;
-    return 2 * units_of(at < 0 ? batch * horizon * row : batch * row);
+    return 2 * units_of(loss_J(batch, horizon, row, 1, at));
 }
 
 int sgp_masked_loss_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t batch, int32_t horizon,
                         int64_t row, int32_t kind, int32_t at, int32_t mask_nans, double* work, int64_t work_doubles,
                         float* loss, double* count, sgp_stream_t stream) {
-    SGP_REQUIRE(y_hat && y && work && loss && count, "sgp_masked_loss_f32: null pointer");
-    SGP_REQUIRE(batch >= 0 && horizon >= 0 && row >= 0, "sgp_masked_loss_f32: bad size");
-    SGP_REQUIRE(kind >= LOSS_MAE && kind <= LOSS_MAPE, "sgp_masked_loss_f32: kind is 0 (mae), 1 (mse) or 2 (mape)");
-    SGP_REQUIRE(at >= -1 && (at < 0 || at < horizon), "sgp_masked_loss_f32: at outside the horizon");
-    SGP_REQUIRE(mask_nans == 0 || mask_nans == 1, "sgp_masked_loss_f32: mask_nans is 0 or 1");
-    // without `at` the tensor is one flat row; with it, step `at` of [B, H, R]
-    const long long J = at < 0 ? batch * horizon * row : batch * row, nseg = units_of(J);
-    SGP_REQUIRE(nseg <= MAX_GRID, "sgp_masked_loss_f32: too many units");
-    SGP_REQUIRE(work_doubles >= 2 * nseg, "sgp_masked_loss_f32: workspace too small");
-    if (nseg > 0) {
-        hipLaunchKernelGGL(masked_loss_kernel, dim3((unsigned)nseg), dim3(TR_THREADS), 0, (hipStream_t)stream,
-                           y_hat, y, mask, J, at < 0 ? 1LL : (long long)horizon, at < 0 ? J : (long long)row,
-                           at < 0 ? 0LL : (long long)at, kind, mask_nans, work);
-        if (int rc = sgp::check_launch("masked_loss")) return rc;
-    }
-    hipLaunchKernelGGL(masked_loss_final_kernel, dim3(1), dim3(TR_THREADS), 0, (hipStream_t)stream,
-                       (const double*)work, nseg, loss, count);
-    return sgp::check_launch("masked_loss_final");
+    return masked_loss_run("sgp_masked_loss_f32", {y_hat, y, mask, nullptr, batch, horizon, row, 1}, kind, at, mask_nans,
+                           work, work_doubles, loss, count, (hipStream_t)stream);
 }
 
 int sgp_masked_loss_bwd_f32(const float* y_hat, const float* y, const uint8_t* mask, int64_t batch, int32_t horizon,
@@ -505,9 +535,7 @@ int sgp_masked_loss_bwd_f32(const float* y_hat, const float* y, const uint8_t* m
                             const double* count, float* grad, sgp_stream_t stream) {
     SGP_REQUIRE(y_hat && y && grad_out && count && grad, "sgp_masked_loss_bwd_f32: null pointer");
     SGP_REQUIRE(batch >= 0 && horizon >= 0 && row >= 0, "sgp_masked_loss_bwd_f32: bad size");
-    SGP_REQUIRE(kind >= LOSS_MAE && kind <= LOSS_MAPE, "sgp_masked_loss_bwd_f32: kind is 0 (mae), 1 (mse) or 2 (mape)");
-    SGP_REQUIRE(at >= -1 && (at < 0 || at < horizon), "sgp_masked_loss_bwd_f32: at outside the horizon");
-    SGP_REQUIRE(mask_nans == 0 || mask_nans == 1, "sgp_masked_loss_bwd_f32: mask_nans is 0 or 1");
+    if (int rc = loss_args_ok("sgp_masked_loss_bwd_f32", kind, at, horizon, mask_nans)) return rc;
     const long long n = batch * horizon * row;
     if (n == 0) return 0;
     hipLaunchKernelGGL(masked_loss_bwd_kernel, dim3(sgp::grid_for(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
@@ -521,11 +549,11 @@ int sgp_masked_nodes_form(int64_t batch, int32_t horizon, int64_t nodes_all, int
     SGP_REQUIRE(out, "sgp_masked_nodes_form: null pointer");
     SGP_REQUIRE(batch >= 0 && horizon >= 0 && nodes_all >= 0 && roots >= 0 && channels >= 0,
                 "sgp_masked_nodes_form: bad size");
-    SGP_REQUIRE(at >= -1 && (at < 0 || at < horizon), "sgp_masked_nodes_form: at outside the horizon");
+    if (int rc = loss_args_ok("sgp_masked_nodes_form", LOSS_MAE, at, horizon, 0)) return rc;      // (only `at` is the caller's)
     SGP_REQUIRE(index_ok(index_bytes), "sgp_masked_nodes_form: index_bytes is 4 (int32) or 8 (int64)");
     const long long n_all = batch * horizon * nodes_all * channels;
     const int vec = nodes_bwd_vec(n_all, grad_aligned16 != 0);
-    out[0] = units_of(nodes_loss_J(batch, horizon, roots, channels, at));
+    out[0] = units_of(loss_J(batch, horizon, roots, channels, at));
     out[1] = units_of(batch * roots * channels);
     out[2] = n_all > 0 ? (long long)nodes_bwd_grid(n_all, vec) : 0;
     out[3] = nodes_bwd_trips(n_all, vec);
@@ -544,13 +572,11 @@ int sgp_target_nodes_table(const void* target_nodes, int32_t index_bytes, int64_
     hipError_t e = hipMemsetAsync(inv, 0xFF, (size_t)nodes_all * sizeof(int32_t), (hipStream_t)stream);   // every entry -1
     if (e != hipSuccess) return sgp::fail((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
     if (roots == 0) return 0;
-    const dim3 grid(nodes_table_grid(roots)), block(TR_THREADS);
-    if (index_bytes == 8)
-        hipLaunchKernelGGL(target_nodes_table_kernel<long long>, grid, block, 0, (hipStream_t)stream,
-                           (const long long*)target_nodes, (long long)roots, (long long)nodes_all, inv, err);
-    else
-        hipLaunchKernelGGL(target_nodes_table_kernel<int>, grid, block, 0, (hipStream_t)stream,
-                           (const int*)target_nodes, (long long)roots, (long long)nodes_all, inv, err);
+    with_index(index_bytes, [&](auto i) {
+        using I = decltype(i);
+        hipLaunchKernelGGL(target_nodes_table_kernel<I>, dim3(nodes_table_grid(roots)), dim3(TR_THREADS), 0,
+                           (hipStream_t)stream, (const I*)target_nodes, (long long)roots, (long long)nodes_all, inv, err);
+    });
     return sgp::check_launch("target_nodes_table");
 }
 
@@ -559,62 +585,18 @@ int sgp_masked_metrics_nodes_f32(const float* y_hat, const float* y, const uint8
                                  int32_t channels, const float* scale, const float* bias, int64_t sc_node_stride,
                                  int32_t mask_nans, int32_t mask_inf, int32_t* err, double* work, int64_t work_doubles,
                                  double* state, sgp_stream_t stream) {
-    SGP_REQUIRE(y_hat && y && target_nodes && err && work && state, "sgp_masked_metrics_nodes_f32: null pointer");
-    SGP_REQUIRE(batch >= 0 && horizon >= 0 && nodes_all >= 0 && roots >= 0 && channels >= 0 && sc_node_stride >= 0,
-                "sgp_masked_metrics_nodes_f32: bad size");
-    SGP_REQUIRE(index_ok(index_bytes), "sgp_masked_metrics_nodes_f32: index_bytes is 4 (int32) or 8 (int64)");
-    SGP_REQUIRE((scale == nullptr) == (bias == nullptr), "sgp_masked_metrics_nodes_f32: scale and bias come together");
-    SGP_REQUIRE((mask_nans == 0 || mask_nans == 1) && (mask_inf == 0 || mask_inf == 1),
-                "sgp_masked_metrics_nodes_f32: mask_nans / mask_inf are 0 or 1");
-    const long long R = roots * channels, J = batch * R, nseg = units_of(J);
-    if (nseg == 0 || horizon == 0) return 0;
-    SGP_REQUIRE(nseg * horizon <= MAX_GRID, "sgp_masked_metrics_nodes_f32: too many units");
-    SGP_REQUIRE(work_doubles >= nseg * horizon * MET_COLS, "sgp_masked_metrics_nodes_f32: workspace too small");
-    Transform tr = {scale, bias, sc_node_stride, channels};
-    const Nodes nd = {nodes_all, channels};
-    const dim3 grid((unsigned)(nseg * horizon)), block(TR_THREADS);
-    if (index_bytes == 8)
-        hipLaunchKernelGGL(masked_metrics_nodes_kernel<long long>, grid, block, 0, (hipStream_t)stream, y_hat, y, mask,
-                           (const long long*)target_nodes, nd, J, (long long)horizon, R, nseg, tr, mask_nans, mask_inf, err,
-                           work);
-    else
-        hipLaunchKernelGGL(masked_metrics_nodes_kernel<int>, grid, block, 0, (hipStream_t)stream, y_hat, y, mask,
-                           (const int*)target_nodes, nd, J, (long long)horizon, R, nseg, tr, mask_nans, mask_inf, err, work);
-    if (int rc = sgp::check_launch("masked_metrics_nodes")) return rc;
-    hipLaunchKernelGGL(masked_metrics_final_kernel, dim3((unsigned)horizon), dim3(TR_THREADS), 0, (hipStream_t)stream,
-                       (const double*)work, nseg, state);
-    return sgp::check_launch("masked_metrics_final");
+    const NodesArg nd = {target_nodes, index_bytes, nodes_all, err};
+    return masked_metrics_run("sgp_masked_metrics_nodes_f32", {y_hat, y, mask, &nd, batch, horizon, roots, channels}, scale,
+                              bias, sc_node_stride, mask_nans, mask_inf, work, work_doubles, state, (hipStream_t)stream);
 }
 
 int sgp_masked_loss_nodes_f32(const float* y_hat, const float* y, const uint8_t* mask, const void* target_nodes,
                               int32_t index_bytes, int64_t batch, int32_t horizon, int64_t nodes_all, int64_t roots,
                               int32_t channels, int32_t kind, int32_t at, int32_t mask_nans, int32_t* err, double* work,
                               int64_t work_doubles, float* loss, double* count, sgp_stream_t stream) {
-    SGP_REQUIRE(y_hat && y && target_nodes && err && work && loss && count, "sgp_masked_loss_nodes_f32: null pointer");
-    SGP_REQUIRE(batch >= 0 && horizon >= 0 && nodes_all >= 0 && roots >= 0 && channels >= 0,
-                "sgp_masked_loss_nodes_f32: bad size");
-    SGP_REQUIRE(index_ok(index_bytes), "sgp_masked_loss_nodes_f32: index_bytes is 4 (int32) or 8 (int64)");
-    SGP_REQUIRE(kind >= LOSS_MAE && kind <= LOSS_MAPE, "sgp_masked_loss_nodes_f32: kind is 0 (mae), 1 (mse) or 2 (mape)");
-    SGP_REQUIRE(at >= -1 && (at < 0 || at < horizon), "sgp_masked_loss_nodes_f32: at outside the horizon");
-    SGP_REQUIRE(mask_nans == 0 || mask_nans == 1, "sgp_masked_loss_nodes_f32: mask_nans is 0 or 1");
-    const long long Rn = roots * channels, J = nodes_loss_J(batch, horizon, roots, channels, at), nseg = units_of(J);
-    SGP_REQUIRE(nseg <= MAX_GRID, "sgp_masked_loss_nodes_f32: too many units");
-    SGP_REQUIRE(work_doubles >= 2 * nseg, "sgp_masked_loss_nodes_f32: workspace too small");
-    if (nseg > 0) {
-        const Nodes nd = {nodes_all, channels};
-        const dim3 grid((unsigned)nseg), block(TR_THREADS);
-        const long long H = at < 0 ? 1LL : (long long)horizon, R = at < 0 ? J : Rn, h = at < 0 ? 0LL : (long long)at;
-        if (index_bytes == 8)
-            hipLaunchKernelGGL(masked_loss_nodes_kernel<long long>, grid, block, 0, (hipStream_t)stream, y_hat, y, mask,
-                               (const long long*)target_nodes, nd, J, H, R, h, Rn, kind, mask_nans, err, work);
-        else
-            hipLaunchKernelGGL(masked_loss_nodes_kernel<int>, grid, block, 0, (hipStream_t)stream, y_hat, y, mask,
-                               (const int*)target_nodes, nd, J, H, R, h, Rn, kind, mask_nans, err, work);
-        if (int rc = sgp::check_launch("masked_loss_nodes")) return rc;
-    }
-    hipLaunchKernelGGL(masked_loss_final_kernel, dim3(1), dim3(TR_THREADS), 0, (hipStream_t)stream,
-                       (const double*)work, nseg, loss, count);
-    return sgp::check_launch("masked_loss_final");
+    const NodesArg nd = {target_nodes, index_bytes, nodes_all, err};
+    return masked_loss_run("sgp_masked_loss_nodes_f32", {y_hat, y, mask, &nd, batch, horizon, roots, channels}, kind, at,
+                           mask_nans, work, work_doubles, loss, count, (hipStream_t)stream);
 }
 
 int sgp_masked_loss_nodes_bwd_f32(const float* y_hat, const float* y, const uint8_t* mask, const int32_t* inv,
@@ -624,9 +606,7 @@ int sgp_masked_loss_nodes_bwd_f32(const float* y_hat, const float* y, const uint
     SGP_REQUIRE(y_hat && inv && grad_out && count && grad && (y || roots == 0), "sgp_masked_loss_nodes_bwd_f32: null pointer");
     SGP_REQUIRE(batch >= 0 && horizon >= 0 && nodes_all >= 0 && roots >= 0 && channels >= 0 && roots <= 2147483647LL,
                 "sgp_masked_loss_nodes_bwd_f32: bad size");
-    SGP_REQUIRE(kind >= LOSS_MAE && kind <= LOSS_MAPE, "sgp_masked_loss_nodes_bwd_f32: kind is 0 (mae), 1 (mse) or 2 (mape)");
-    SGP_REQUIRE(at >= -1 && (at < 0 || at < horizon), "sgp_masked_loss_nodes_bwd_f32: at outside the horizon");
-    SGP_REQUIRE(mask_nans == 0 || mask_nans == 1, "sgp_masked_loss_nodes_bwd_f32: mask_nans is 0 or 1");
+    if (int rc = loss_args_ok("sgp_masked_loss_nodes_bwd_f32", kind, at, horizon, mask_nans)) return rc;
     const long long n_all = batch * horizon * nodes_all * channels;
     if (n_all == 0) return 0;
     const int vec = nodes_bwd_vec(n_all, sgp::aligned16(grad));

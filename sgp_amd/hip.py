@@ -1766,16 +1766,50 @@ def adam_step(table, params, grads, exp_avg, exp_avg_sq, *, lr, betas, eps, weig
                                  int(bool(decoupled)), _stream(table)), "sgp_adam_step_f32")
 
 
-def _bhr(y_hat, y, mask, what):
-    """Contiguous float32 CUDA ``y_hat``, ``y`` of one shape ``[B, H, ...]`` (uint8 ``mask`` of the same shape)."""
+def _masked_operands(y_hat, y, mask, what, nodes=False, tn=None, err=None):
+    """Contiguous float32 CUDA ``y_hat`` and ``y`` of one shape ``[B, H, ...]``; with ``nodes`` they are
+    ``[B, H, nodes_all, C]`` against ``[B, H, roots, C]`` and may differ on the node axis.  ``mask``: uint8, the shape
+    of ``y``.  ``tn`` / ``err``, when given: the ``[roots]`` index vector and the error word of the root-node kernels."""
+    layout = " [B, H, nodes, C]" if nodes else ""
     for name, t in (("y_hat", y_hat), ("y", y)):
-        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous float32 CUDA tensor")
-    if y_hat.shape != y.shape or y.dim() < 2:
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or (nodes and t.dim() != 4):
+            raise ValueError(f"{what}: {name} must be a contiguous float32 CUDA tensor{layout}")
+    if nodes and (y_hat.shape[:2] != y.shape[:2] or y_hat.shape[3] != y.shape[3]):
+        raise ValueError(f"{what}: y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} differ outside the node axis")
+    if not nodes and (y_hat.shape != y.shape or y.dim() < 2):
         raise ValueError(f"{what}: y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} must share a shape [B, H, ...]")
     if mask is not None and (mask.shape != y.shape or mask.dtype != torch.uint8 or not mask.is_cuda
                              or not mask.is_contiguous()):
         raise ValueError(f"{what}: mask must be a contiguous uint8 CUDA tensor of the shape of y")
+    if tn is not None:
+        _index_bytes(tn.dtype)
+        if tn.dim() != 1 or not tn.is_cuda or not tn.is_contiguous() or tn.numel() != y.shape[2]:
+            raise ValueError(f"{what}: target_nodes must be a contiguous CUDA vector of the {y.shape[2]} roots of y, "
+                             f"got {tuple(tn.shape)} on {tn.device}")
+    if err is not None and (err.dtype != torch.int32 or not err.is_cuda or err.numel() != 1):
+        raise ValueError(f"{what}: the error word is one int32 on the device")
+
+
+def _masked_metrics_launch(what, y_hat, y, mask, state, scale, bias, sc_node_stride, mask_nans, mask_inf, nodes=None):
+    """The metrics pass over checked operands; ``nodes``: ``(tn, err)`` of the root-node layout."""
+    lib = load()
+    B, H, N, C = y.shape
+    if tuple(state.shape) != (H, METRIC_COLS) or state.dtype != torch.float64 or not state.is_cuda \
+            or not state.is_contiguous():
+        raise ValueError(f"{what}: state must be contiguous float64 CUDA [{H}, {METRIC_COLS}]")
+    if not y.numel() or not y_hat.shape[2]:
+        return state
+    work = torch.empty(max(1, lib.sgp_masked_metrics_workspace_doubles(B, H, N, C)), dtype=torch.float64, device=y.device)
+    head = (y_hat.data_ptr(), y.data_ptr(), _ptr(mask))
+    flags = (_ptr(scale), _ptr(bias), int(sc_node_stride), int(bool(mask_nans)), int(bool(mask_inf)))
+    tail = (work.data_ptr(), work.numel(), state.data_ptr(), _stream(y))
+    if nodes is None:
+        _check(lib.sgp_masked_metrics_f32(*head, B, H, N, C, *flags, *tail), "sgp_masked_metrics_f32")
+    else:
+        tn, err = nodes
+        _check(lib.sgp_masked_metrics_nodes_f32(*head, tn.data_ptr(), _index_bytes(tn.dtype), B, H, y_hat.shape[2], N, C,
+                                                *flags, err.data_ptr(), *tail), "sgp_masked_metrics_nodes_f32")
+    return state
 
 
 @_on_device
@@ -1783,21 +1817,11 @@ def masked_metrics(y_hat, y, mask, state, scale=None, bias=None, sc_node_stride=
     """Add the masked sums of one batch ``[B, H, N, C]`` into ``state`` (float64 CUDA ``[H, METRIC_COLS]``): one pass
     over the batch and one fixed-order add, no host sync.  ``scale`` / ``bias``: the inverse transform of ``y_hat``
     (float32 CUDA, element (n, c) at ``n * sc_node_stride + c``)."""
-    lib = require_gpu()
-    _bhr(y_hat, y, mask, "masked_metrics")
+    require_gpu()
+    _masked_operands(y_hat, y, mask, "masked_metrics")
     if y.dim() != 4:
         raise ValueError("masked_metrics: expected [B, H, N, C]")
-    B, H, N, C = y.shape
-    if tuple(state.shape) != (H, METRIC_COLS) or state.dtype != torch.float64 or not state.is_cuda \
-            or not state.is_contiguous():
-        raise ValueError(f"masked_metrics: state must be contiguous float64 CUDA [{H}, {METRIC_COLS}]")
-    if not y.numel():
-        return state
-    work = torch.empty(max(1, lib.sgp_masked_metrics_workspace_doubles(B, H, N, C)), dtype=torch.float64, device=y.device)
-    _check(lib.sgp_masked_metrics_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), B, H, N, C, _ptr(scale), _ptr(bias),
-                                      int(sc_node_stride), int(bool(mask_nans)), int(bool(mask_inf)), work.data_ptr(),
-                                      work.numel(), state.data_ptr(), _stream(y)), "sgp_masked_metrics_f32")
-    return state
+    return _masked_metrics_launch("masked_metrics", y_hat, y, mask, state, scale, bias, sc_node_stride, mask_nans, mask_inf)
 
 
 def _loss_dims(y, at):
@@ -1807,22 +1831,34 @@ def _loss_dims(y, at):
     return B, H, (y.numel() // (B * H) if B * H else 0), (-1 if at is None else int(at))
 
 
-@_on_device
-def masked_loss(y_hat, y, mask=None, kind="mae", at=None, mask_nans=False):
-    """(loss [] float32, count [1] float64) of MaskedMAE / MaskedMSE / MaskedMAPE over ``[B, H, ...]``, all steps or
-    step ``at``: per-segment fp64 partials from many workgroups, added in a fixed order."""
-    lib = require_gpu()
-    _bhr(y_hat, y, mask, "masked_loss")
+def _masked_loss_launch(y_hat, y, mask, kind, at, mask_nans, nodes=None):
+    """(loss, count) over checked operands; ``nodes``: ``(tn, err)`` of the root-node layout."""
+    lib = load()
     B, H, R, at = _loss_dims(y, at)
-    if not y.numel():                                                   # nothing counts (and no address): 0, as tsl
+    if not y.numel() or not y_hat.numel():                              # nothing counts (and no address): 0, as tsl
         return torch.zeros((), dtype=torch.float32, device=y.device), torch.zeros(1, dtype=torch.float64, device=y.device)
     loss = torch.empty((), dtype=torch.float32, device=y.device)
     count = torch.empty(1, dtype=torch.float64, device=y.device)
     work = torch.empty(max(1, lib.sgp_masked_loss_workspace_doubles(B, H, R, at)), dtype=torch.float64, device=y.device)
-    _check(lib.sgp_masked_loss_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), B, H, R, LOSS_KINDS[kind], at,
-                                   int(bool(mask_nans)), work.data_ptr(), work.numel(), loss.data_ptr(),
-                                   count.data_ptr(), _stream(y)), "sgp_masked_loss_f32")
+    head = (y_hat.data_ptr(), y.data_ptr(), _ptr(mask))
+    flags = (LOSS_KINDS[kind], at, int(bool(mask_nans)))
+    tail = (work.data_ptr(), work.numel(), loss.data_ptr(), count.data_ptr(), _stream(y))
+    if nodes is None:
+        _check(lib.sgp_masked_loss_f32(*head, B, H, R, *flags, *tail), "sgp_masked_loss_f32")
+    else:
+        tn, err = nodes
+        _check(lib.sgp_masked_loss_nodes_f32(*head, tn.data_ptr(), _index_bytes(tn.dtype), B, H, y_hat.shape[2], y.shape[2],
+                                             y.shape[3], *flags, err.data_ptr(), *tail), "sgp_masked_loss_nodes_f32")
     return loss, count
+
+
+@_on_device
+def masked_loss(y_hat, y, mask=None, kind="mae", at=None, mask_nans=False):
+    """(loss [] float32, count [1] float64) of MaskedMAE / MaskedMSE / MaskedMAPE over ``[B, H, ...]``, all steps or
+    step ``at``: per-segment fp64 partials from many workgroups, added in a fixed order."""
+    require_gpu()
+    _masked_operands(y_hat, y, mask, "masked_loss")
+    return _masked_loss_launch(y_hat, y, mask, kind, at, mask_nans)
 
 
 @_on_device
@@ -1872,27 +1908,6 @@ def target_nodes_error(word, what="target_nodes"):
         raise ValueError(f"{what}: a node is named more than once")
 
 
-def _nodes_operands(y_hat, y, mask, tn, err, what):
-    """Checks of the root-node bindings -> (B, H, nodes_all, roots, C)."""
-    for name, t in (("y_hat", y_hat), ("y", y)):
-        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 4:
-            raise ValueError(f"{what}: {name} must be a contiguous float32 CUDA tensor [B, H, nodes, C]")
-    if y_hat.shape[:2] != y.shape[:2] or y_hat.shape[3] != y.shape[3]:
-        raise ValueError(f"{what}: y_hat {tuple(y_hat.shape)} and y {tuple(y.shape)} differ outside the node axis")
-    if mask is not None and (mask.shape != y.shape or mask.dtype != torch.uint8 or not mask.is_cuda
-                             or not mask.is_contiguous()):
-        raise ValueError(f"{what}: mask must be a contiguous uint8 CUDA tensor of the shape of y")
-    if tn is not None:
-        _index_bytes(tn.dtype)
-        if tn.dim() != 1 or not tn.is_cuda or not tn.is_contiguous() or tn.numel() != y.shape[2]:
-            raise ValueError(f"{what}: target_nodes must be a contiguous CUDA vector of the {y.shape[2]} roots of y, "
-                             f"got {tuple(tn.shape)} on {tn.device}")
-    if err is not None and (err.dtype != torch.int32 or not err.is_cuda or err.numel() != 1):
-        raise ValueError(f"{what}: the error word is one int32 on the device")
-    B, H, nodes_all, C = y_hat.shape
-    return B, H, nodes_all, y.shape[2], C
-
-
 @_on_device
 def target_nodes_table(tn, nodes_all, err):
     """int32 CUDA ``[nodes_all]``: the position of every node among ``tn``, -1 for the others; a bad ``tn`` sets
@@ -1913,19 +1928,9 @@ def target_nodes_table(tn, nodes_all, err):
 @_on_device
 def masked_loss_nodes(y_hat, y, mask, tn, err, kind="mae", at=None, mask_nans=False):
     """``masked_loss`` of ``y_hat[..., tn, :]`` against ``y`` without the slice: (loss, count), bit-equal to it."""
-    lib = require_gpu()
-    B, H, nodes_all, roots, C = _nodes_operands(y_hat, y, mask, tn, err, "masked_loss_nodes")
-    _, _, R, at = _loss_dims(y, at)
-    if not y.numel() or not nodes_all:
-        return torch.zeros((), dtype=torch.float32, device=y.device), torch.zeros(1, dtype=torch.float64, device=y.device)
-    loss = torch.empty((), dtype=torch.float32, device=y.device)
-    count = torch.empty(1, dtype=torch.float64, device=y.device)
-    work = torch.empty(max(1, lib.sgp_masked_loss_workspace_doubles(B, H, R, at)), dtype=torch.float64, device=y.device)
-    _check(lib.sgp_masked_loss_nodes_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), tn.data_ptr(), _index_bytes(tn.dtype),
-                                         B, H, nodes_all, roots, C, LOSS_KINDS[kind], at, int(bool(mask_nans)),
-                                         err.data_ptr(), work.data_ptr(), work.numel(), loss.data_ptr(), count.data_ptr(),
-                                         _stream(y)), "sgp_masked_loss_nodes_f32")
-    return loss, count
+    require_gpu()
+    _masked_operands(y_hat, y, mask, "masked_loss_nodes", True, tn, err)
+    return _masked_loss_launch(y_hat, y, mask, kind, at, mask_nans, (tn, err))
 
 
 @_on_device
@@ -1933,7 +1938,8 @@ def masked_loss_nodes_bwd(y_hat, y, mask, inv, kind, at, mask_nans, grad_out, co
     """The full gradient ``[B, H, nodes_all, C]`` of ``masked_loss_nodes`` in one launch (``inv``: the table of
     ``target_nodes_table``); ``out``: a float32 CUDA buffer of that shape to write into (every element is written)."""
     lib = require_gpu()
-    B, H, nodes_all, roots, C = _nodes_operands(y_hat, y, mask, None, None, "masked_loss_nodes_bwd")
+    _masked_operands(y_hat, y, mask, "masked_loss_nodes_bwd", True)
+    (B, H, nodes_all, C), roots = y_hat.shape, y.shape[2]
     _, _, _, at = _loss_dims(y, at)
     if inv.dtype != torch.int32 or not inv.is_cuda or not inv.is_contiguous() or inv.numel() != nodes_all:
         raise ValueError(f"masked_loss_nodes_bwd: the table must be contiguous int32 CUDA [{nodes_all}]")
@@ -1954,21 +1960,10 @@ def masked_metrics_nodes(y_hat, y, mask, tn, err, state, scale=None, bias=None, 
                          mask_inf=False):
     """``masked_metrics`` of ``y_hat[..., tn, :]`` against ``y`` without the slice; ``scale`` / ``bias`` are addressed
     by the root position (element (j, c) at ``j * sc_node_stride + c``)."""
-    lib = require_gpu()
-    B, H, nodes_all, roots, C = _nodes_operands(y_hat, y, mask, tn, err, "masked_metrics_nodes")
-    if tuple(state.shape) != (H, METRIC_COLS) or state.dtype != torch.float64 or not state.is_cuda \
-            or not state.is_contiguous():
-        raise ValueError(f"masked_metrics_nodes: state must be contiguous float64 CUDA [{H}, {METRIC_COLS}]")
-    if not y.numel() or not nodes_all:
-        return state
-    work = torch.empty(max(1, lib.sgp_masked_metrics_workspace_doubles(B, H, roots, C)), dtype=torch.float64,
-                       device=y.device)
-    _check(lib.sgp_masked_metrics_nodes_f32(y_hat.data_ptr(), y.data_ptr(), _ptr(mask), tn.data_ptr(),
-                                            _index_bytes(tn.dtype), B, H, nodes_all, roots, C, _ptr(scale), _ptr(bias),
-                                            int(sc_node_stride), int(bool(mask_nans)), int(bool(mask_inf)), err.data_ptr(),
-                                            work.data_ptr(), work.numel(), state.data_ptr(), _stream(y)),
-           "sgp_masked_metrics_nodes_f32")
-    return state
+    require_gpu()
+    _masked_operands(y_hat, y, mask, "masked_metrics_nodes", True, tn, err)
+    return _masked_metrics_launch("masked_metrics_nodes", y_hat, y, mask, state, scale, bias, sc_node_stride, mask_nans,
+                                  mask_inf, (tn, err))
 
 
 # ---------------------------------------------------------------- gated graph network edges (gated_gn.hip)

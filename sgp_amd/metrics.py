@@ -17,20 +17,31 @@ from .readout import TSL_EPSILON, _scaler_param
 _ABS, _CNT, _SQ, _APE, _APE_CNT, _YSUM = range(6)
 
 
+def _kernel_device(y_hat):
+    """The device the kernels run on: that of ``y_hat``, the current GPU for a CPU one."""
+    if y_hat.is_cuda:
+        return y_hat.device
+    hip.require_gpu()
+    return torch.device("cuda")
+
+
+def _kernel_operands(y_hat, y, mask, detach):
+    """``(y_hat, y, mask)`` as every kernel here takes them: on ``_kernel_device``, float32 and contiguous, the mask as
+    uint8.  ``detach``: the metrics leave the graph here; the losses must not (autograd carries the casts and copies)."""
+    dev = _kernel_device(y_hat)
+    if detach:
+        y_hat, y = y_hat.detach(), y.detach()
+    m = None if mask is None else mask.to(dev).bool().to(torch.uint8).contiguous()
+    return y_hat.to(dev, torch.float32).contiguous(), y.to(dev, torch.float32).contiguous(), m
+
+
 def _as_kernel_operands(y_hat, y, mask):
     if y_hat.shape != y.shape or (mask is not None and mask.shape != y.shape):
         raise ValueError(f"masked metric: shapes differ: {tuple(y_hat.shape)}, {tuple(y.shape)}"
                          + ("" if mask is None else f", mask {tuple(mask.shape)}"))
     if y.dim() != 4:
         raise ValueError(f"masked metric: expected [batch, horizon, nodes, channels], got {tuple(y.shape)}")
-    dev = y_hat.device
-    if not y_hat.is_cuda:
-        hip.require_gpu()
-        dev = torch.device("cuda")
-    yh = y_hat.detach().to(dev, torch.float32).contiguous()
-    yt = y.detach().to(dev, torch.float32).contiguous()
-    m = None if mask is None else mask.to(dev).bool().to(torch.uint8).contiguous()
-    return yh, yt, m
+    return _kernel_operands(y_hat, y, mask, detach=True)
 
 
 def _target_nodes_operands(y_hat, y, mask, target_nodes, what):
@@ -52,11 +63,7 @@ def _target_nodes_operands(y_hat, y, mask, target_nodes, what):
         raise ValueError(f"{what}: {target_nodes.numel()} target_nodes for the {y.shape[2]} roots of y")
     if mask is not None and mask.shape != y.shape:
         raise ValueError(f"{what}: mask {tuple(mask.shape)} differs from y {tuple(y.shape)}")
-    dev = y_hat.device
-    if not y_hat.is_cuda:
-        hip.require_gpu()
-        dev = torch.device("cuda")
-    return target_nodes.to(dev).contiguous()
+    return target_nodes.to(_kernel_device(y_hat)).contiguous()
 
 
 def _error_word(error_word, device):
@@ -105,9 +112,7 @@ def _nodes_update_operands(owner, y_hat, y, mask, transform, target_nodes, error
     transformed with torch ops, and the kernel of the unsliced path runs on the result."""
     tn = _target_nodes_operands(y_hat, y, mask, target_nodes, what)
     err = _own_error_word(owner, error_word, tn)
-    yh = y_hat.detach().to(tn.device, torch.float32).contiguous()
-    yt = y.detach().to(tn.device, torch.float32).contiguous()
-    m = None if mask is None else mask.to(tn.device).bool().to(torch.uint8).contiguous()
+    yh, yt, m = _kernel_operands(y_hat, y, mask, detach=True)
     ops = _transform_operands(transform, yh, nodes=yt.shape[2])
     if ops is None:
         yh, scale, bias, stride = _transform_operands(transform, slice_target_nodes(yh, tn, err))
@@ -298,32 +303,18 @@ class MaskedMRE(MaskedMetric):
 
 
 class _MaskedLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, y_hat, y, mask, kind, at, mask_nans):
-        loss, count = hip.masked_loss(y_hat, y, mask, kind, at, mask_nans)
-        ctx.save_for_backward(y_hat, y, mask, count)
-        ctx.cfg = (kind, at, mask_nans)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        y_hat, y, mask, count = ctx.saved_tensors
-        kind, at, mask_nans = ctx.cfg
-        if ctx.needs_input_grad[1] and kind == "mape":
-            raise NotImplementedError("masked_mape: no gradient with respect to the target")
-        g = g.to(torch.float32).reshape(1).contiguous()
-        grad = hip.masked_loss_bwd(y_hat, y, mask, kind, at, mask_nans, g, count)
-        return grad, (-grad if ctx.needs_input_grad[1] else None), None, None, None, None
-
-
-class _MaskedLossNodesFn(torch.autograd.Function):
-    """The loss on the root nodes: saves the prediction as the model gave it (never a slice of it) and the node table;
-    the backward is ONE launch that writes the full-size gradient."""
+    """The loss of both layouts.  With ``tn`` / ``err`` (the root nodes) it saves the prediction as the model gave it
+    (never a slice of it) and the node table, and the backward is ONE launch that writes the full-size gradient;
+    without them (None) the prediction has the shape of the target."""
 
     @staticmethod
     def forward(ctx, y_hat, y, mask, tn, err, kind, at, mask_nans):
-        inv = hip.target_nodes_table(tn, y_hat.shape[2], err)
-        loss, count = hip.masked_loss_nodes(y_hat, y, mask, tn, err, kind, at, mask_nans)
+        if tn is None:
+            inv = None
+            loss, count = hip.masked_loss(y_hat, y, mask, kind, at, mask_nans)
+        else:
+            inv = hip.target_nodes_table(tn, y_hat.shape[2], err)
+            loss, count = hip.masked_loss_nodes(y_hat, y, mask, tn, err, kind, at, mask_nans)
         ctx.save_for_backward(y_hat, y, mask, count, inv)
         ctx.cfg = (kind, at, mask_nans)
         return loss
@@ -332,11 +323,16 @@ class _MaskedLossNodesFn(torch.autograd.Function):
     def backward(ctx, g):
         y_hat, y, mask, count, inv = ctx.saved_tensors
         kind, at, mask_nans = ctx.cfg
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and inv is not None:
             raise NotImplementedError(f"masked_{kind}: no gradient with respect to the target through target_nodes")
+        if ctx.needs_input_grad[1] and kind == "mape":
+            raise NotImplementedError("masked_mape: no gradient with respect to the target")
         g = g.to(torch.float32).reshape(1).contiguous()
-        grad = hip.masked_loss_nodes_bwd(y_hat, y, mask, inv, kind, at, mask_nans, g, count)
-        return grad, None, None, None, None, None, None, None
+        if inv is None:
+            grad = hip.masked_loss_bwd(y_hat, y, mask, kind, at, mask_nans, g, count)
+        else:
+            grad = hip.masked_loss_nodes_bwd(y_hat, y, mask, inv, kind, at, mask_nans, g, count)
+        return grad, (-grad if ctx.needs_input_grad[1] else None), None, None, None, None, None, None
 
 
 def _masked_loss_nodes(y_hat, y, mask, kind, at, mask_nans, target_nodes, check, error_word):
@@ -344,10 +340,7 @@ def _masked_loss_nodes(y_hat, y, mask, kind, at, mask_nans, target_nodes, check,
         raise ValueError(f"masked_{kind}: check=False leaves the error word to the caller: pass error_word")
     tn = _target_nodes_operands(y_hat, y, mask, target_nodes, f"masked_{kind}")
     err = _error_word(error_word, tn.device)
-    yh = y_hat.to(tn.device, torch.float32).contiguous()
-    yt = y.to(tn.device, torch.float32).contiguous()
-    m = None if mask is None else mask.to(tn.device).bool().to(torch.uint8).contiguous()
-    loss = _MaskedLossNodesFn.apply(yh, yt, m, tn, err, kind, at, bool(mask_nans))
+    loss = _MaskedLossFn.apply(*_kernel_operands(y_hat, y, mask, detach=False), tn, err, kind, at, bool(mask_nans))
     if check:
         word = int(err.item())
         if word:
@@ -380,16 +373,10 @@ def masked_loss(y_hat, y, mask=None, kind="mae", at=None, mask_nans=False, targe
                          + ("" if mask is None else f", mask {tuple(mask.shape)}"))
     if y.dim() < 2 and at is not None:
         raise ValueError(f"masked_{kind}: at={at} needs [batch, horizon, ...]")
-    dev = y_hat.device
-    if not y_hat.is_cuda:
-        hip.require_gpu()
-        dev = torch.device("cuda")
-    yh = y_hat.to(dev, torch.float32).contiguous()
-    yt = y.to(dev, torch.float32).contiguous()
-    m = None if mask is None else mask.to(dev).bool().to(torch.uint8).contiguous()
+    yh, yt, m = _kernel_operands(y_hat, y, mask, detach=False)
     if y.dim() < 2:                                                     # without `at` the kernel sees one flat row anyway
         yh, yt, m = (None if t is None else t.reshape(1, 1, t.numel()) for t in (yh, yt, m))
-    loss = _MaskedLossFn.apply(yh, yt, m, kind, at, bool(mask_nans))
+    loss = _MaskedLossFn.apply(yh, yt, m, None, None, kind, at, bool(mask_nans))
     return loss if y_hat.is_cuda else loss.cpu()
 
 

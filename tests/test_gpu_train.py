@@ -8,12 +8,16 @@
   restated in fp64 on the same fp32 inputs: 1e-6 relative (at most three fp32 roundings of 2^-24 per element, fp64
   sums of non-negative terms, one rounding of the result), counts exact.
 * ``masked_mse`` / ``masked_mape``: forward and gradient against fp64 autograd of the restatement, 1e-6.
+* the whole-batch and the root-node loss / metrics paths, bit for bit, against a recording made before the two were
+  brought down to one set of kernels (``tests/golden/masked_parity.npz``).
 * ``Predictor``: 20 ``training_step`` s against the CPU fp32 restatement of tests/test_gpu_sgp_model.py under that
   test's own 1e-4, metrics in the original range, early stopping.
 """
 import copy
 import math
+import os
 
+import numpy as np
 import pytest
 import torch
 
@@ -384,6 +388,96 @@ def test_loss_edge_cases():
     assert math.isnan(float(masked_mse(yn.cuda(), y.cuda())))
     r = ref_loss("mse", torch.where(torch.isnan(yn), y, yn).double(), y.double(), None, None) * y.numel() / (y.numel() - 1)
     assert abs(float(masked_mse(yn.cuda(), y.cuda(), mask_nans=True)) - float(r)) <= 1e-6 * float(r)
+
+
+# ------------------------------------------------------------------------------------------------------- parity
+# (nodes_all, roots, channels) of tests/subgraph_predictor_ref.py: one unit; odd sizes with two channels; roots == nodes;
+# two units per horizon step; two grid-stride trips of the root-node backward
+PARITY_SHAPES = [(63, 1, 1), (65, 37, 2), (700, 700, 2), (1300, 1100, 1), (350001, 37, 1)]
+PARITY_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "masked_parity.npz")
+
+
+def masked_parity(shape):
+    """``{name: integer array}``: what the whole-batch entries (on the materialised slice) and the root-node entries
+    give on ``test_gpu_subgraph_predictor.inputs(*shape)``, as bit patterns.  Axes, in this order where they apply:
+    mask (none, given, mask_nans), index type (int32, int64), transform (none, root-wise), ``at`` (None, 1), loss kind
+    (mae, mse, mape), path (whole-batch, root nodes).  The gradients do not see the index type (the backward reads the
+    int32 table): they are taken under both and kept once.  The full-size gradient of the largest shape is kept as the
+    exact int64 sum of its bit patterns and the (index, bits) of its non-zero words, padded with -1 / 0."""
+    from test_gpu_subgraph_predictor import B, H, KINDS as LOSSES, MASKS as MKS, inputs, transform_of, with_nans
+    nodes_all, roots, c = shape
+    compact = nodes_all * B * H * c > 1 << 20
+    yh_cpu, y_cpu, mask_cpu, tn_cpu = inputs(*shape)
+    tr = transform_of("root_wise", roots, c, 7)
+    root_wise = (tr["scale"].reshape(roots, c).cuda().contiguous(), tr["bias"].reshape(roots, c).cuda().contiguous(), c)
+    bits32 = lambda t: t.contiguous().view(torch.int32).reshape(-1)
+    bits64 = lambda t: t.contiguous().view(torch.int64)
+    g = torch.tensor([1.5], device="cuda")
+    y = y_cpu.cuda()
+    loss_b, count_b, state_b, grad_b, gnodes_b, gsum_b, gidx_b = [], [], [], [], [], [], []
+    for mk in MKS:
+        yh = (with_nans(yh_cpu, tn_cpu) if mk == "mask_nans" else yh_cpu).cuda()
+        mask = None if mk == "none" else mask_cpu.cuda().to(torch.uint8)
+        nans = mk == "mask_nans"
+        per_dtype = []
+        for dtype in (torch.int32, torch.int64):
+            tn = tn_cpu.to(dtype).cuda()
+            sliced = yh[..., tn.long(), :].contiguous()
+            err = torch.zeros(1, dtype=torch.int32, device="cuda")
+            inv = hip.target_nodes_table(tn, nodes_all, err)
+            for sb in ((None, None, 0), root_wise):
+                zero = lambda: torch.zeros(H, hip.METRIC_COLS, dtype=torch.float64, device="cuda")
+                state_b += [bits64(hip.masked_metrics(sliced, y, mask, zero(), *sb, mask_nans=nans)),
+                            bits64(hip.masked_metrics_nodes(yh, y, mask, tn, err, zero(), *sb, mask_nans=nans))]
+            grads = []
+            for at in (None, 1):
+                for kind in LOSSES:
+                    loss0, count0 = hip.masked_loss(sliced, y, mask, kind, at, nans)
+                    loss, count = hip.masked_loss_nodes(yh, y, mask, tn, err, kind, at, nans)
+                    loss_b += [bits32(loss0), bits32(loss)]
+                    count_b += [bits64(count0), bits64(count)]
+                    grads.append((bits32(hip.masked_loss_bwd(sliced, y, mask, kind, at, nans, g, count0)),
+                                  bits32(hip.masked_loss_nodes_bwd(yh, y, mask, inv, kind, at, nans, g, count))))
+            assert int(err.item()) == 0
+            per_dtype.append(grads)
+        for (g0, gn), (g0_64, gn_64) in zip(*per_dtype):
+            assert torch.equal(g0, g0_64) and torch.equal(gn, gn_64), (shape, mk)
+            grad_b.append(g0)
+            if not compact:
+                gnodes_b.append(gn)
+                continue
+            nz = gn.nonzero().reshape(-1)
+            assert nz.numel() <= g0.numel()
+            pad = g0.numel() - nz.numel()
+            gsum_b.append(gn.to(torch.int64).sum().reshape(1))
+            gidx_b.append(torch.cat([nz, nz.new_full((pad,), -1)]))
+            gnodes_b.append(torch.cat([gn[nz], gn.new_zeros(pad)]))
+    n_m, n_k = len(MKS), len(LOSSES)
+    out = dict(loss=torch.cat(loss_b).reshape(n_m, 2, 2, n_k, 2), count=torch.cat(count_b).reshape(n_m, 2, 2, n_k, 2),
+               state=torch.stack(state_b).reshape(n_m, 2, 2, 2, H, hip.METRIC_COLS),
+               grad=torch.stack(grad_b).reshape(n_m, 2, n_k, -1), grad_nodes=torch.stack(gnodes_b).reshape(n_m, 2, n_k, -1))
+    if compact:
+        out.update(grad_nodes_sum=torch.cat(gsum_b).reshape(n_m, 2, n_k), grad_nodes_index=torch.stack(gidx_b).reshape(n_m, 2, n_k, -1))
+    tag = "x".join(map(str, shape))
+    return {f"{tag}/{k}": v.cpu().numpy() for k, v in out.items()}
+
+
+@pytest.fixture(scope="module")
+def parity_recording():
+    with np.load(PARITY_FILE) as z:
+        return {k: z[k] for k in z.files}
+
+
+@pytest.mark.parametrize("shape", PARITY_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_masked_paths_bit_equal_to_the_recording(shape, parity_recording):
+    """Loss, count, metric state and both gradients of both paths against the bits recorded from the two separate
+    kernel sets: equality, not closeness (the walk and the accumulation order are part of the contract)."""
+    got = masked_parity(shape)
+    want = {k: v for k, v in parity_recording.items() if k.startswith("x".join(map(str, shape)) + "/")}
+    assert sorted(got) == sorted(want) and len(got) >= 5
+    for k, v in got.items():
+        assert v.dtype == want[k].dtype and v.dtype.kind == "i" and v.shape == want[k].shape, k
+        assert np.array_equal(v, want[k]), (k, int((v != want[k]).sum()))
 
 
 # ------------------------------------------------------------------------------------------------------- Predictor
