@@ -1619,6 +1619,56 @@ int sgp_az_direct_f32(const float* x, int64_t x_step_stride, int64_t x_node_stri
 int sgp_az_finish(const int64_t* s, const int64_t* m, const double* weight, int64_t n_edges, int32_t n_tests,
                   const int64_t* st, const int64_t* mt, const int64_t* nonfinite, double* rec, sgp_stream_t stream);
 
+/* ------------------------------------- preparing a raw series ---
+ * The arithmetic between a dataset reader and the window data module (series.hip): temporal resampling, node groups
+ * and time encodings of an fp32 series.  Every tensor is contiguous.  A NaN in the source is skipped by every
+ * operation, as pandas' skipna=True skips it: sum = the sum of the others (0 if there are none), mean = that sum over
+ * their count, min / max over the others, and NaN for mean / min / max where nothing is left.  Sums are accumulated in
+ * fp64 in row (node) order and rounded to fp32 once; the mean is divided in fp64 by the count and then rounded.  All
+ * offsets are 64-bit: rows x cols beyond 2^31 elements is served by construction.
+ *
+ * sgp_series_resample_f32: x [rows, cols] (cols = nodes x feat), bin_ptr [bins + 1] int32: bin b holds the source rows
+ *   bin_ptr[b] .. bin_ptr[b + 1] - 1 (the rows are sorted by time, so a bin is a row range; entries are clamped to
+ *   [0, rows] before they index anything).  y [bins, cols] = op over the bin's rows, one thread per output element
+ *   walking its rows in order.  An empty bin gives 0 (sum) or NaN (mean, min, max).  op SGP_SERIES_TAKE: y[b] = row
+ *   src_row[b] of x (int32 [bins]; outside [0, rows), -1 by convention: NaN) -- asfreq and `nearest`, whose row choice
+ *   is host work; bin_ptr is then read for the mask only and may be NULL without one.
+ *   mask: NULL, or bytes [rows, cols] (mask_per_node == 0) or [rows, cols / feat] (mask_per_node != 0); mask_out has
+ *   the same columns and `bins` rows: (double) valid / (double) count >= 1.0 - mask_tol over the bin's rows, compared in
+ *   fp64; an empty bin is invalid.  The aggregation of x does not read the mask.
+ *   flags SGP_SERIES_NAN_TO_MASK (op TAKE, no mask): mask_out [bins, cols] = the value is not NaN, and a NaN is stored
+ *   as 0 (CEREn.load's mask = ~isnan, fillna(0)).
+ *     replaces PandasDataset.resample_ (tsl/datasets/prototypes/pd_dataset.py:117-150) and df.asfreq in CEREn.load
+ *     (lib/datasets/cer_en.py:120-124)
+ * sgp_series_group_f32: x [steps, nodes, feat], groups as a CSR over the nodes: grp_ptr [groups + 1], grp_node [nodes]
+ *   int32 (ascending within a group; pointers are clamped to [0, nodes], a node id outside [0, nodes) is skipped).
+ *   y [steps, groups, feat] = op over the group's nodes (SUM .. MAX); mask / mask_out as above with [steps, nodes(,
+ *   feat)] -> [steps, groups(, feat)].  regime 0: a thread per output walks its group in node order; regime 1: a
+ *   workgroup per (step, group), thread k takes the group's nodes k, k + 256, .. in order into fp64 partials and wg.h's
+ *   halving tree folds the 256 partials.  Both orders are fixed: the result does not change from run to run (it may
+ *   differ between the regimes in the last bit of a sum).  sgp_amd.series.launch_plan chooses.
+ *     replaces TabularDataset.aggregate_ (tsl/datasets/prototypes/tabular_dataset.py:329-375; CEREn.aggregate,
+ *     cluster_'s aggregation step)
+ * sgp_datetime_encode_f32: out [steps, 2 units] = sin | cos of 2 pi r / period per unit with r = index_ns mod
+ *   period_ns reduced in int64 (floored: 0 <= r < period, also before 1970), the angle and sin / cos in fp64, rounded
+ *   once.  period_ns [units] int64, each positive.
+ *     replaces TemporalFeaturesMixin.datetime_encoded (tsl/datasets/prototypes/mixin.py:97-115), whose fp64 product
+ *     index_nano * (2 pi / period) carries ~1e-11 of argument error at present-day timestamps */
+#define SGP_SERIES_SUM  0
+#define SGP_SERIES_MEAN 1
+#define SGP_SERIES_MIN  2
+#define SGP_SERIES_MAX  3
+#define SGP_SERIES_TAKE 4
+#define SGP_SERIES_NAN_TO_MASK 1
+int sgp_series_resample_f32(const float* x, int64_t rows, int64_t cols, int32_t feat, const uint8_t* mask,
+                            int32_t mask_per_node, const int32_t* bin_ptr, const int32_t* src_row, int64_t bins, int32_t op,
+                            int32_t flags, double mask_tol, float* y, uint8_t* mask_out, sgp_stream_t stream);
+int sgp_series_group_f32(const float* x, int64_t steps, int64_t nodes, int32_t feat, const uint8_t* mask,
+                         int32_t mask_per_node, const int32_t* grp_ptr, const int32_t* grp_node, int64_t groups, int32_t op,
+                         int32_t regime, double mask_tol, float* y, uint8_t* mask_out, sgp_stream_t stream);
+int sgp_datetime_encode_f32(const int64_t* index_ns, int64_t steps, const int64_t* period_ns, int32_t units, float* out,
+                            sgp_stream_t stream);
+
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were
  * launched on without importing a HIP binding. */

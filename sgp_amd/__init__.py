@@ -21,6 +21,7 @@ from .optim import FusedAdam
 from .predictors import Predictor, SubgraphPredictor
 from .sgp_preprocessing import (preprocess_adj, preprocess_dataset, reservoir_preprocessing_,
                                 sgp_spatial_embedding, sgp_spatial_support, window_spatial_embedding)
+from .series import Series, aggregate, asfreq, datetime_encoded, resample
 from .utils import encode_dataset, self_normalizing_activation
 from .whiteness import AZWhiteness, AZWhitenessMultiTestResult, AZWhitenessTestResult, az_whiteness_test
 
