@@ -1193,6 +1193,57 @@ int sgp_rnn_window_bwd_f32(int32_t cell, int32_t H, int32_t S, int64_t M, float*
                            const float* h_seq, const float* c_seq, const float* dy, int32_t dy_full,
                            sgp_stream_t stream);
 
+/* ------------------------------------------------ RNN imputers: the fill-in GRU recurrence -----
+ * rnn_impute.hip: the time loop of RNNImputerModel (tsl/nn/models/imputation/rnni_models.py:74-96) for M independent
+ * sequences of S steps with D fed-back columns,
+ *   h_0 given (NULL: zeros),  p_s = W_r h_s + b_r,  xp_s = m_s ? x_s : p_s,  h_{s+1} = GRUCell([xp_s | u_s | m_s], h_s)
+ * for s = 0 .. S-2 (x_{S-1} is never an input).  EXACT-FP32 contract as above: every product is a
+ * v_mfma_f32_16x16x4_f32, one k-ordered chain per output, no float atomics, bit-identical from run to run and
+ * independent of the tile a sequence falls into.  h and the backward carries stay on chip for the whole window.
+ * Domain: GRU; H a multiple of 16 in 16 .. 256; D in 1 .. 512; S, M >= 1; anything else returns SGP_EUNSUP with the
+ * reason in sgp_last_error (sgp_rnn_impute_supported answers without a GPU).
+ * Rows.  mask, xp, p, dP and gx lie in the window's own order: row (m / inner) * S * inner + t * inner + m % inner for
+ * step t of sequence m -- [b, s, n, c] read in place with inner = n (independent nodes, D = c) or inner = 1 (joint,
+ * D = n c).  gates, h_seq, dH and dp are [S][M][.].  reverse != 0 walks the window from its last step to its first and
+ * reads and writes rows at S-1-t, which is a forward run on the time-flipped window, flipped back.
+ * gates [S][M][4 H] (sgp_rnn_impute_workspace_bytes): on entry blocks 0 .. 2 hold the state-free part
+ * W_x (m . x) + W_u u + W_m m + b_ih (+ b_hr, b_hz; NOT b_hn) of all S M rows, one sgp_dense_f32 launch.
+ * packed: sgp_rnn_impute_packed_floats floats; W_hh [3 H, H], W_x = weight_ih[:, :D] and W_r [D, H] in the fragment
+ * order of both directions, zero padded to whole tiles of 16 along D. */
+int32_t sgp_rnn_impute_supported(int32_t H, int32_t D);
+int64_t sgp_rnn_impute_packed_floats(int32_t H, int32_t D);
+int64_t sgp_rnn_impute_workspace_bytes(int32_t H, int32_t D, int32_t S, int64_t M);
+int sgp_rnn_impute_pack_f32(const float* w_ih, int64_t w_ih_row_stride, const float* w_hh, const float* w_r, int32_t H,
+                            int32_t D, float* packed, sgp_stream_t stream);
+
+/* The launch form for these sizes (host only): plan[0] column tiles of 16 per wave (1, 2 or 4), [1] waves per
+ * workgroup, [2] tiles of 16 along D (1: every D tile is wave 0's; more: dealt round robin over the waves),
+ * [3] workgroups (16 sequences each), [4] / [5] bytes of LDS of the forward / backward launch. */
+int sgp_rnn_impute_plan(int32_t H, int32_t D, int64_t M, int32_t* plan);
+
+/* One launch for the whole window: p (every step's prediction) and h_seq (h_0 .. h_{S-1}) are stored.  mask: 0 / 1
+ * floats.  save != 0 (training): the gate buffer is overwritten with what backward reads (r, z, n and W_hn h + b_hn in
+ * block 3) and xp -- on entry m . x, the operand the state-free part was computed from -- receives p_s at the missing
+ * entries of steps 0 .. S-2, which makes it the merged input, the weight-gradient operand of W_x.
+ *   replaces the loop of tsl/nn/models/imputation/rnni_models.py:83-96 (init_hidden_state aside): readout,
+ *   _preprocess_input (lines 62-72), rnn_cell and the two stacks */
+int sgp_rnn_impute_fwd_f32(int32_t H, int32_t D, int32_t S, int64_t M, int64_t inner, int32_t reverse, float* gates,
+                           const float* packed, const float* b_hn, const float* b_r, const float* h0, const float* mask,
+                           int64_t mask_row_stride, float* xp, int64_t xp_row_stride, float* p, float* h_seq,
+                           int32_t save, sgp_stream_t stream);
+
+/* Time reversed, one launch.  dP: the cotangent of p; dH (may be NULL) [S][M][H]: the cotangent of h_seq (the Bi
+ * model's read_out).  The saved gates are overwritten in place with the gradients of the pre-activations
+ * [dr, dz, dn, dn r] (the input side reads blocks 0 .. 2, the hidden side 0, 1 and 3; the row of the last step is
+ * zeroed, so weight gradients run over all S M rows and S = 1 gives exact zeros).  dp [S][M][D]: the total
+ * dp_s = dP_s + (1 - m_s) . W_x^T dgates_s (detach != 0: dP_s alone), the operand of dW_r, db_r.  gx (may be NULL):
+ * m_s . W_x^T dgates_s, exactly zero at missing entries and at step S-1.
+ *   replaces what autograd derives for rnni_models.py:83-96 (detach_input: line 64) */
+int sgp_rnn_impute_bwd_f32(int32_t H, int32_t D, int32_t S, int64_t M, int64_t inner, int32_t reverse, int32_t detach,
+                           float* gates, const float* packed, const float* h_seq, const float* mask,
+                           int64_t mask_row_stride, const float* dP, const float* dH, float* dp, float* gx,
+                           sgp_stream_t stream);
+
 /* ------------------------------------------------ DCRNN baseline: diffusion convolution and its GRU cell -----
  * dcrnn.hip.  EXACT-FP32 contract as above: v_mfma_f32_16x16x4_f32 in the matrix kernels, plain FMAs in CSR order in
  * the hop; no float atomics, bit-identical from run to run; no persistent kernel and no barrier between workgroups (a

@@ -18,7 +18,7 @@ from .metrics import (MaskedMAE, MaskedMAPE, MaskedMRE, MaskedMSE, MetricSet, ma
                       masked_mse)
 from .nn.models import SGPOnlineModel
 from .optim import FusedAdam
-from .predictors import Predictor, SubgraphPredictor
+from .predictors import Imputer, Predictor, SubgraphPredictor
 from .sgp_preprocessing import (preprocess_adj, preprocess_dataset, reservoir_preprocessing_,
                                 sgp_spatial_embedding, sgp_spatial_support, window_spatial_embedding)
 from .series import Series, aggregate, asfreq, datetime_encoded, resample

@@ -2082,6 +2082,81 @@ def rnn_window_bwd(gates, cell, H, S, M, packed, h_seq, c_seq, dy, dy_full):
            "sgp_rnn_window_bwd_f32")
 
 
+# ---------------------------------------------------------------- RNN imputers: fill-in GRU recurrence (rnn_impute.hip)
+def rnn_impute_supported(H, D):
+    """Whether the fill-in recurrence covers hidden size ``H`` with ``D`` fed-back columns (no GPU needed)."""
+    return bool(load().sgp_rnn_impute_supported(int(H), int(D)))
+
+
+def rnn_impute_require(H, D):
+    if not rnn_impute_supported(H, D):
+        raise NotImplementedError("rnn_impute: " + load().sgp_last_error().decode())
+
+
+def rnn_impute_workspace_bytes(H, D, S, M):
+    """Bytes of the gate buffer [S, M, 4 H]."""
+    return int(load().sgp_rnn_impute_workspace_bytes(int(H), int(D), int(S), int(M)))
+
+
+def rnn_impute_plan(H, D, M):
+    """The launch form of ``sgp_rnn_impute_fwd_f32`` / ``_bwd_f32`` for these sizes (host only).  ``form`` names the
+    code path: ``ct<k>`` -- k column tiles of 16 per wave (1, 2 or 4) -- and ``d1`` (one tile along D, computed by wave
+    0 alone) or ``dn`` (several, dealt over the waves)."""
+    out = (c_i32 * 6)()
+    _check(load().sgp_rnn_impute_plan(int(H), int(D), int(M), ctypes.addressof(out)), "sgp_rnn_impute_plan")
+    ct, waves, d_tiles, wgs, lds_f, lds_b = (int(v) for v in out)
+    return dict(form=f"ct{ct}_{'d1' if d_tiles == 1 else 'dn'}", ct=ct, waves=waves, d_tiles=d_tiles, workgroups=wgs,
+                lds_fwd=lds_f, lds_bwd=lds_b)
+
+
+def rnn_impute_forms():
+    """Every form ``rnn_impute_plan`` can name over the kernels' domain."""
+    return sorted({rnn_impute_plan(H, D, 1)["form"] for H in range(16, 257, 16) for D in (1, 16, 17, 512)})
+
+
+@_on_device
+def rnn_impute_pack(w_ih, w_hh, w_r, D):
+    """``rnn_cell.weight_ih`` [3 H, >= D], ``rnn_cell.weight_hh`` [3 H, H] and ``readout.weight`` [D, H] (CUDA) ->
+    their packed copy for both directions (sgp_rnn_impute_pack_f32)."""
+    lib = require_gpu()
+    wi, wh, wr = (w.detach().float().contiguous() for w in (w_ih, w_hh, w_r))
+    H = wh.shape[1]
+    rnn_impute_require(H, D)
+    if wh.shape[0] != 3 * H or wi.shape[0] != 3 * H or wi.shape[1] < D or tuple(wr.shape) != (D, H):
+        raise ValueError(f"rnn_impute_pack: weight_ih {tuple(wi.shape)}, weight_hh {tuple(wh.shape)}, readout "
+                         f"{tuple(wr.shape)} do not fit H = {H}, D = {D}")
+    packed = torch.empty(lib.sgp_rnn_impute_packed_floats(H, D), dtype=torch.float32, device=wh.device)
+    _check(lib.sgp_rnn_impute_pack_f32(wi.data_ptr(), wi.stride(0), wh.data_ptr(), wr.data_ptr(), H, D,
+                                       packed.data_ptr(), _stream(wh)), "sgp_rnn_impute_pack_f32")
+    return packed
+
+
+@_on_device
+def rnn_impute_fwd(gates, H, D, S, M, inner, packed, b_hn, b_r, mask, p, h_seq, h0=None, xp=None, reverse=False,
+                   save=False):
+    """The whole window's fill-in recurrence (sgp_rnn_impute_fwd_f32).  ``gates`` [S M, 4 H] holds the state-free part
+    of the input projection; ``mask`` / ``xp`` [rows, >= D] (0 / 1 floats, the merged input) and ``p`` [rows, D] lie in
+    the window's own row order; ``h_seq`` [S M, H]."""
+    lib = require_gpu()
+    mp, mrs = _rows2(mask, "mask", D)
+    xpp, xrs = _rows2(xp, "xp", D) if xp is not None else (None, 0)
+    _check(lib.sgp_rnn_impute_fwd_f32(H, D, S, M, inner, int(bool(reverse)), gates.data_ptr(), packed.data_ptr(),
+                                      b_hn.data_ptr(), b_r.data_ptr(), _ptr(h0), mp, mrs, xpp, xrs, p.data_ptr(),
+                                      h_seq.data_ptr(), int(bool(save)), _stream(gates)), "sgp_rnn_impute_fwd_f32")
+
+
+@_on_device
+def rnn_impute_bwd(gates, H, D, S, M, inner, packed, h_seq, mask, dP, dp, dH=None, gx=None, reverse=False,
+                   detach=False):
+    """Backward through time (sgp_rnn_impute_bwd_f32): the saved gates become the pre-activation gradients in place,
+    ``dp`` [S M, D] the total cotangent of the predictions, ``gx`` [rows, D] the gradient of the observed inputs."""
+    lib = require_gpu()
+    mp, mrs = _rows2(mask, "mask", D)
+    _check(lib.sgp_rnn_impute_bwd_f32(H, D, S, M, inner, int(bool(reverse)), int(bool(detach)), gates.data_ptr(),
+                                      packed.data_ptr(), h_seq.data_ptr(), mp, mrs, dP.data_ptr(), _ptr(dH),
+                                      dp.data_ptr(), _ptr(gx), _stream(gates)), "sgp_rnn_impute_bwd_f32")
+
+
 # ---------------------------------------------------------------- DCRNN: diffusion hop and GRU cell (dcrnn.hip)
 def dcrnn_supported(H, k):
     """Whether the diffusion-GRU kernels cover hidden size ``H`` with ``k`` hops per support (no GPU needed)."""

@@ -2,6 +2,7 @@ from .esn_model import ESNModel
 from .sgp_model import OnlineSGPModel, SGPInputEncoder, SGPModel
 from .gated_gn_model import GatedGraphNetwork, GatedGraphNetworkMLPModel, GatedGraphNetworkModel
 from .rnn_model import FCRNNModel, RNNModel
+from .rnn_imputer import BiRNNImputerModel, RNNImputerModel
 from .dcrnn_model import DCRNNModel
 from .gwnet_model import GraphWaveNetModel
 from .sgp_online import SGPOnlineModel
@@ -9,4 +10,4 @@ from ...metrics import masked_mae        # the loss every model trains with live
 
 __all__ = ["SGPInputEncoder", "SGPModel", "OnlineSGPModel", "ESNModel", "masked_mae", "GatedGraphNetwork",
            "GatedGraphNetworkModel", "GatedGraphNetworkMLPModel", "RNNModel", "FCRNNModel", "DCRNNModel",
-           "GraphWaveNetModel", "SGPOnlineModel"]
+           "GraphWaveNetModel", "SGPOnlineModel", "RNNImputerModel", "BiRNNImputerModel"]

@@ -1,4 +1,5 @@
 from .predictor import Predictor
+from .imputer import Imputer
 from .subgraph_predictor import SubgraphPredictor
 
-__all__ = ["Predictor", "SubgraphPredictor"]
+__all__ = ["Predictor", "SubgraphPredictor", "Imputer"]
