@@ -1244,6 +1244,67 @@ int sgp_rnn_impute_bwd_f32(int32_t H, int32_t D, int32_t S, int64_t M, int64_t i
                            int64_t mask_row_stride, const float* dP, const float* dH, float* dp, float* gx,
                            sgp_stream_t stream);
 
+/* ------------------------------------------------ GRIN: the stages around the cells of one GRIL step -----
+ * grin.hip (tsl/nn/layers/graph_convs/grin_cell.py:200-227, SpatialDecoder.forward :82-104).  With hT the top layer's
+ * state entering the step, m the mask, R = b n rows, H hidden, C input and U exogenous columns:
+ *   stage 1  p1 = W_fs hT + b_fs,  x1 = m ? x : p1,  z = W_in [x1 | m | hT | u] + b_in  -> slot 0 of dec [R, 3 H]
+ *   (one sgp_diffuse_f32 launch: slots 1, 2 = A_f z, A_b z on the graph without self loops)
+ *   stage 2  g = W_f [A_f z | A_b z] + b_f,  o = PReLU(W_o [g | hT] + b_o),  repr = [o | hT],  p2 = W_ro repr + b_ro,
+ *            x2 = m ? x : p2,  [x2 | m | u] -> the leading columns of cell_in
+ * EXACT-FP32 contract as above: v_mfma_f32_16x16x4_f32, one k-ordered chain per output, no atomics, bit-identical
+ * from run to run and independent of the tile a row falls into; x is selected by the mask and never multiplied.
+ * Domain: H a multiple of 16 in 16 .. 128, C in 1 .. 16, U in 0 .. 64, k as sgp_dcrnn_supported; anything else
+ * returns SGP_EUNSUP with the reason in sgp_last_error (sgp_grin_supported answers without a GPU).
+ * Rows.  x, mask (0 / 1 floats), p1, p2, dP1, dP2, gx [., C] and u, gu [., U] are contiguous and lie in the
+ * window's own [b, S, n, .] order: row (r / inner) S inner + tt inner + r % inner for row r, inner = n, tt = t or, with
+ * reverse != 0, S - 1 - t.  repr / dRepr rows lie in the same order, repr_row_stride floats apart.  hT, dec, cell_in,
+ * the save buffers, ddec, carry, dp1 and dp2 [R][C] are rows of this step.
+ * packed: sgp_grin_packed_floats floats; first_stage.weight [C, H], lin_in.weight [H, 2 C + H + U],
+ * graph_conv.filters.weight [H, 2 H], lin_out.weight [H, 2 H], read_out.weight [C, 2 H] (all contiguous) in fragment
+ * order, then their transposes. */
+int32_t sgp_grin_supported(int32_t H, int32_t C, int32_t U, int32_t k);
+int64_t sgp_grin_packed_floats(int32_t H, int32_t C, int32_t U);
+int sgp_grin_pack_f32(const float* w_fs, const float* w_in, const float* w_f, const float* w_o, const float* w_ro,
+                      int32_t H, int32_t C, int32_t U, float* packed, sgp_stream_t stream);
+
+/* The launch form (host only): plan[0] tiles of 16 along H, [1] rounds of the 4 waves over them, [2] tiles of 16 along
+ * 2 C + H + U, [3] workgroups (16 rows each), [4] .. [7] bytes of LDS of stage 1, stage 2, stage 2 backward and
+ * stage 1 backward. */
+int sgp_grin_plan(int32_t H, int32_t C, int32_t U, int64_t R, int32_t* plan);
+
+/* save_in (may be NULL) [R][2 C + H + U]: the merged operand row of lin_in. */
+int sgp_grin_stage1_f32(int32_t H, int32_t C, int32_t U, int64_t R, int64_t inner, int32_t S, int32_t t, int32_t reverse,
+                        const float* packed, const float* b_fs, const float* b_in, const float* hT, int64_t h_row_stride,
+                        const float* x, const float* mask, const float* u, float* p1, float* dec, int64_t dec_row_stride,
+                        float* save_in, sgp_stream_t stream);
+
+/* slope: the PReLU weight, read on the device.  repr may be NULL (nothing reads the representations).  save_pre [R][H] and save_cat [R][2 H] (both or neither): the
+ * pre-activation of lin_out and its operand [g | hT]. */
+int sgp_grin_stage2_f32(int32_t H, int32_t C, int32_t U, int64_t R, int64_t inner, int32_t S, int32_t t, int32_t reverse,
+                        const float* packed, const float* b_f, const float* b_o, const float* b_ro, const float* slope,
+                        const float* dec, int64_t dec_row_stride, const float* hT, int64_t h_row_stride, const float* x,
+                        const float* mask, const float* u, float* p2, float* repr, int64_t repr_row_stride,
+                        float* cell_in, int64_t cell_row_stride, float* save_pre, float* save_cat, sgp_stream_t stream);
+
+/* dcell (may be NULL): the cotangent of cell_in.  dp2 = dP2 + (1 - m) dx2 (stored: the operand of read_out's weight
+ * gradient), gx = m dx2 (gx may be NULL); pre is overwritten with the cotangent of lin_out's pre-activation, dg [R][H]
+ * receives that of g; ddec [R, 3 H]: slots 1, 2 = W_f^T dg, slot 0 zeroed for the adjoint hop; carry [R][H] += the
+ * cotangent of hT; slope_partial [workgroups]: per-workgroup sums of the slope's gradient (fixed order, fp64 inside).
+ *   replaces what autograd derives for SpatialDecoder.forward :100-104 and grin_cell.py:216 */
+int sgp_grin_stage2_bwd_f32(int32_t H, int32_t C, int32_t U, int64_t R, int64_t inner, int32_t S, int32_t t,
+                            int32_t reverse, const float* packed, const float* slope, const float* mask, const float* dP2,
+                            const float* dRepr, int64_t drepr_row_stride, const float* dcell, int64_t cell_row_stride,
+                            float* pre, float* dg, float* ddec, int64_t ddec_row_stride, float* carry, float* gx,
+                            float* dp2, float* slope_partial, sgp_stream_t stream);
+
+/* After the adjoint hop: d[x1 | m | hT | u] = W_in^T (slot 0 of ddec); dp1 = dP1 + (1 - m) dx1 (stored), gx += m dx1,
+ * gu = du + the u columns of dcell, carry += W_fs^T dp1 + dhT.
+ *   replaces what autograd derives for grin_cell.py:206-208 and SpatialDecoder.forward :86-90 */
+int sgp_grin_stage1_bwd_f32(int32_t H, int32_t C, int32_t U, int64_t R, int64_t inner, int32_t S, int32_t t,
+                            int32_t reverse, const float* packed, const float* mask, const float* dP1, const float* dcell,
+                            int64_t cell_row_stride, const float* ddec, int64_t ddec_row_stride, float* carry, float* gx,
+                            float* dp1, float* gu, sgp_stream_t stream);
+
 /* ------------------------------------------------ DCRNN baseline: diffusion convolution and its GRU cell -----
  * dcrnn.hip.  EXACT-FP32 contract as above: v_mfma_f32_16x16x4_f32 in the matrix kernels, plain FMAs in CSR order in
  * the hop; no float atomics, bit-identical from run to run; no persistent kernel and no barrier between workgroups (a

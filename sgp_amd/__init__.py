@@ -16,7 +16,8 @@ from .readout import RidgeReadout, RidgePath, closed_form_readout, ridge_solve_p
 from .scalers import MinMaxScaler, RobustScaler, Scaler, StandardScaler
 from .metrics import (MaskedMAE, MaskedMAPE, MaskedMRE, MaskedMSE, MetricSet, masked_loss, masked_mae, masked_mape,
                       masked_mse)
-from .nn.models import SGPOnlineModel
+from .nn.layers import GRIL
+from .nn.models import GRINModel, SGPOnlineModel
 from .optim import FusedAdam
 from .predictors import Imputer, Predictor, SubgraphPredictor
 from .sgp_preprocessing import (preprocess_adj, preprocess_dataset, reservoir_preprocessing_,

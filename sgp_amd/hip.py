@@ -2240,6 +2240,130 @@ def dcrnn_bwd(phase, dh, ruc, h_prev, dz, H, ddrh=None):
                                  _stream(dh)), "sgp_dcrnn_bwd_f32")
 
 
+# ---------------------------------------------------------------- GRIN: the stages around the cells of a GRIL step (grin.hip)
+def grin_supported(H, C, U, k):
+    """Whether the GRIL stage kernels and the diffusion-GRU cells cover these sizes (no GPU needed)."""
+    return bool(load().sgp_grin_supported(int(H), int(C), int(U), int(k)))
+
+
+def grin_require(H, C, U, k):
+    if not grin_supported(H, C, U, k):
+        raise NotImplementedError("grin: " + load().sgp_last_error().decode())
+
+
+def grin_plan(H, C, U, R):
+    """The launch form of the four stage kernels (host only).  ``form``: ``r<n>``, the rounds of the 4 waves over the
+    ``H / 16`` output tiles as ``sgp_grin_plan`` reports them."""
+    out = (c_i32 * 8)()
+    _check(load().sgp_grin_plan(int(H), int(C), int(U), int(R), ctypes.addressof(out)), "sgp_grin_plan")
+    v = [int(q) for q in out]
+    return dict(form=f"r{v[1]}", h_tiles=v[0], rounds=v[1], in_tiles=v[2], workgroups=v[3],
+                lds_stage1=v[4], lds_stage2=v[5], lds_stage2_bwd=v[6], lds_stage1_bwd=v[7])
+
+
+def grin_forms():
+    """Every form ``grin_plan`` can name over the kernels' domain."""
+    return sorted({grin_plan(H, C, U, 1)["form"] for H in range(16, 129, 16) for C in (1, 16) for U in (0, 64)})
+
+
+@_on_device
+def grin_pack(w_fs, w_in, w_f, w_o, w_ro, U):
+    """The five weights of a GRIL's stages (CUDA) -> their packed copy for both directions (sgp_grin_pack_f32)."""
+    lib = require_gpu()
+    ws = [w.detach().float().contiguous() for w in (w_fs, w_in, w_f, w_o, w_ro)]
+    C, H = ws[0].shape
+    shapes = [(C, H), (H, 2 * C + H + U), (H, 2 * H), (H, 2 * H), (C, 2 * H)]
+    if [tuple(w.shape) for w in ws] != shapes:
+        raise ValueError(f"grin_pack: weights {[tuple(w.shape) for w in ws]} do not fit H = {H}, C = {C}, U = {U}")
+    n = lib.sgp_grin_packed_floats(H, C, U)
+    if n < 0:
+        grin_require(H, C, U, 1)
+    packed = torch.empty(n, dtype=torch.float32, device=ws[0].device)
+    _check(lib.sgp_grin_pack_f32(*[w.data_ptr() for w in ws], H, C, U, packed.data_ptr(), _stream(packed)),
+           "sgp_grin_pack_f32")
+    return packed
+
+
+def _grin_win(t, name, rows, width):
+    if t is None:
+        return None
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != rows * width:
+        raise ValueError(f"{name}: expected a contiguous float32 CUDA tensor of {rows} x {width}, got {tuple(t.shape)} "
+                         f"{t.dtype} {t.device}")
+    return t.data_ptr()
+
+
+@_on_device
+def grin_stage1(dims, t, reverse, packed, b_fs, b_in, hT, x, mask, u, p1, dec, save_in=None):
+    """Stage 1 of step ``t`` (sgp_grin_stage1_f32).  ``dims = (H, C, U, R, n, S)``; ``x``, ``mask``, ``u``, ``p1``: the
+    whole window ``[b, S, n, .]``; ``hT`` [R, >= H], ``dec`` [R, >= 3 H] views with unit column stride."""
+    lib = require_gpu()
+    H, C, U, R, n, S = dims
+    rows = R * S
+    hp, hrs = _rows2(hT, "hT", H)
+    dp, drs = _rows2(dec, "dec", 3 * H)
+    _check(lib.sgp_grin_stage1_f32(H, C, U, R, n, S, int(t), int(bool(reverse)), packed.data_ptr(), b_fs.data_ptr(),
+                                   b_in.data_ptr(), hp, hrs, _grin_win(x, "x", rows, C), _grin_win(mask, "mask", rows, C),
+                                   _grin_win(u, "u", rows, U), _grin_win(p1, "p1", rows, C), dp, drs,
+                                   _grin_win(save_in, "save_in", R, 2 * C + H + U), _stream(dec)), "sgp_grin_stage1_f32")
+
+
+@_on_device
+def grin_stage2(dims, t, reverse, packed, b_f, b_o, b_ro, slope, dec, hT, x, mask, u, p2, repr2, cell_in,
+                save_pre=None, save_cat=None):
+    """Stage 2 of step ``t`` (sgp_grin_stage2_f32).  ``repr2``: 2-D view ``[b S n, >= 2 H]`` of the representations'
+    column block; ``cell_in`` [R, >= 2 C + U]."""
+    lib = require_gpu()
+    H, C, U, R, n, S = dims
+    rows = R * S
+    hp, hrs = _rows2(hT, "hT", H)
+    dp, drs = _rows2(dec, "dec", 3 * H)
+    rp, rrs = _rows2(repr2, "repr", 2 * H) if repr2 is not None else (None, 0)
+    cp, crs = _rows2(cell_in, "cell_in", 2 * C + U)
+    if repr2 is not None and repr2.shape[0] != rows:
+        raise ValueError(f"repr: {repr2.shape[0]} rows, {rows} expected")
+    _check(lib.sgp_grin_stage2_f32(H, C, U, R, n, S, int(t), int(bool(reverse)), packed.data_ptr(), b_f.data_ptr(),
+                                   b_o.data_ptr(), b_ro.data_ptr(), slope.data_ptr(), dp, drs, hp, hrs,
+                                   _grin_win(x, "x", rows, C), _grin_win(mask, "mask", rows, C),
+                                   _grin_win(u, "u", rows, U), _grin_win(p2, "p2", rows, C), rp, rrs, cp, crs,
+                                   _grin_win(save_pre, "save_pre", R, H), _grin_win(save_cat, "save_cat", R, 2 * H),
+                                   _stream(dec)), "sgp_grin_stage2_f32")
+
+
+@_on_device
+def grin_stage2_bwd(dims, t, reverse, packed, slope, mask, dP2, dRepr2, dcell, pre, dg, ddec, carry, gx, dp2, partial):
+    """Backward of stage 2 at step ``t`` (sgp_grin_stage2_bwd_f32); ``partial`` [>= ceil(R / 16)]."""
+    lib = require_gpu()
+    H, C, U, R, n, S = dims
+    rows = R * S
+    rp, rrs = _rows2(dRepr2, "dRepr", 2 * H) if dRepr2 is not None else (None, 0)
+    cp, crs = _rows2(dcell, "dcell", 2 * C + U) if dcell is not None else (None, 0)
+    dp, drs = _rows2(ddec, "ddec", 3 * H)
+    if partial.numel() < (R + 15) // 16 or (dRepr2 is not None and dRepr2.shape[0] != rows):
+        raise ValueError("grin_stage2_bwd: partial or dRepr too short")
+    _check(lib.sgp_grin_stage2_bwd_f32(H, C, U, R, n, S, int(t), int(bool(reverse)), packed.data_ptr(), slope.data_ptr(),
+                                       _grin_win(mask, "mask", rows, C), _grin_win(dP2, "dP2", rows, C), rp, rrs, cp, crs,
+                                       _grin_win(pre, "pre", R, H), _grin_win(dg, "dg", R, H), dp, drs,
+                                       _grin_win(carry, "carry", R, H), _grin_win(gx, "gx", rows, C),
+                                       _grin_win(dp2, "dp2", R, C), partial.data_ptr(), _stream(ddec)),
+           "sgp_grin_stage2_bwd_f32")
+
+
+@_on_device
+def grin_stage1_bwd(dims, t, reverse, packed, mask, dP1, dcell, ddec, carry, gx, dp1, gu):
+    """Backward of stage 1 at step ``t``, after the adjoint decoder hop (sgp_grin_stage1_bwd_f32)."""
+    lib = require_gpu()
+    H, C, U, R, n, S = dims
+    rows = R * S
+    cp, crs = _rows2(dcell, "dcell", 2 * C + U) if dcell is not None else (None, 0)
+    dp, drs = _rows2(ddec, "ddec", H)
+    _check(lib.sgp_grin_stage1_bwd_f32(H, C, U, R, n, S, int(t), int(bool(reverse)), packed.data_ptr(),
+                                       _grin_win(mask, "mask", rows, C), _grin_win(dP1, "dP1", rows, C), cp, crs, dp, drs,
+                                       _grin_win(carry, "carry", R, H), _grin_win(gx, "gx", rows, C),
+                                       _grin_win(dp1, "dp1", R, C), _grin_win(gu, "gu", rows, U), _stream(ddec)),
+           "sgp_grin_stage1_bwd_f32")
+
+
 # ---------------------------------------------------------------- Graph WaveNet: gated TCN, dense operator, norm (gwnet.hip)
 def gwnet_supported(H, Kt):
     """Whether the Graph WaveNet kernels cover hidden size ``H`` with temporal kernel size ``Kt`` (no GPU needed)."""

@@ -2,7 +2,8 @@ from .gated_gn import GatedGraphNetwork, edge_plan
 from .rnn import RNN
 from .diff_conv import DiffConv, DiffusionPlan, diffusion_plan
 from .dcrnn import DCRNN, DCRNNCell
+from .grin import GRIL, SpatialDecoder
 from .gwnet import GatedTemporalConv, Norm, SpatialConvOrderK, TemporalConvNet
 
 __all__ = ["GatedGraphNetwork", "edge_plan", "RNN", "DiffConv", "DiffusionPlan", "diffusion_plan", "DCRNN", "DCRNNCell",
-           "GatedTemporalConv", "TemporalConvNet", "SpatialConvOrderK", "Norm"]
+           "GatedTemporalConv", "TemporalConvNet", "SpatialConvOrderK", "Norm", "GRIL", "SpatialDecoder"]

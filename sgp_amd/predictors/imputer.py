@@ -145,10 +145,11 @@ class Imputer(Predictor):
 
     # ------------------------------------------------------------------------------------------------ a whole series
     @torch.no_grad()
-    def fill(self, x, mask, u=None, window=24, transform=None, batch_size=64):
+    def fill(self, x, mask, u=None, window=24, transform=None, batch_size=64, edge_index=None, edge_weight=None):
         """Fill the gaps of a series ``x [T, N, C]`` (``mask``: what is observed; ``u [T, N, E]``): windows of stride
         ``window``, plus one tail window ending at ``T`` that is used only for the steps not already covered.
-        ``transform`` (``{bias, scale}``): the model sees the scaled series.  Returns the filled series on the device;
+        ``transform`` (``{bias, scale}``): the model sees the scaled series.  ``edge_index`` / ``edge_weight`` are handed
+        to the model when given (graph imputers).  Returns the filled series on the device;
         observed entries are returned bit-unchanged."""
         self._require_gpu()
         self.eval()
@@ -171,6 +172,10 @@ class Imputer(Predictor):
         for i in range(0, len(starts), batch_size):
             st = starts[i:i + batch_size]
             kw = {} if u is None else dict(u=torch.stack([u[s:s + w] for s in st]))
+            if edge_index is not None:
+                kw["edge_index"] = edge_index
+            if edge_weight is not None:
+                kw["edge_weight"] = edge_weight
             y_hat = self.forward(x=torch.stack([xs[s:s + w] for s in st]), mask=torch.stack([mask[s:s + w] for s in st]),
                                  **kw)
             if isinstance(y_hat, (list, tuple)):
