@@ -2262,7 +2262,8 @@ def grin_plan(H, C, U, R):
 
 
 def grin_forms():
-    """Every form ``grin_plan`` can name over the kernels' domain."""
+    """Every form ``grin_plan`` can name over the kernels' domain (``r1`` / ``r2``).  The name alone is not what the
+    tests cover: the kernels branch on far more than the rounds (tests/grin_forms.py counts those facets)."""
     return sorted({grin_plan(H, C, U, 1)["form"] for H in range(16, 129, 16) for C in (1, 16) for U in (0, 64)})
 
 
