@@ -966,7 +966,8 @@ int sgp_dense_pack_f32(const float* w, int64_t w_row_stride, int32_t transpose, 
  *   dmode = 1, c < n_act:  v = v * act'(dpre[r * dpre_row_stride + c]) * keep(r, c)      (the backward pass)
  *   then v += add[r * add_row_stride + c] (add != NULL), stored at
  *   out[(r / m0) m1 + (r % m0) m2 + (c / m3) m4 + (c % m3) m5] with out_map = {m0, .., m5} (host array).
- * act: 0 linear, 1 relu, 2 silu; keep(r, c) = the Philox dropout factor of decoder.hip at flat index
+ * act: 0 linear, 1 relu, 2 silu, 3 elu (alpha 1: v > 0 ? v : expm1(v), act' = z > 0 ? 1 : exp(z); this entry and
+ * sgp_grouped_linear_dact_f32 only); keep(r, c) = the Philox dropout factor of decoder.hip at flat index
  * r * drop_width + c (1 when dropout_p = 0, 0 when dropout_p = 1).
  *   replaces nn.Linear + activation + Dropout of tsl Dense (tsl/nn/base/dense.py:19-23), the stacked Linear1 / skip
  *   of ResidualMLP (tsl/nn/blocks/encoders/mlp.py:86-111), lin_emb + the positional add (sgp_model.py:76,97), the
@@ -1780,6 +1781,49 @@ int sgp_series_group_f32(const float* x, int64_t steps, int64_t nodes, int32_t f
                          int32_t regime, double mask_tol, float* y, uint8_t* mask_out, sgp_stream_t stream);
 int sgp_datetime_encode_f32(const int64_t* index_ns, int64_t steps, const int64_t* period_ns, int32_t units, float* out,
                             sgp_stream_t stream);
+
+/* ------------------------------------------------------------ Attention -----
+ * Multi-head scaled dot-product attention, forward and backward (attention.hip).  EXACT-FP32 contract as
+ * the decoder section: every product is a v_mfma_f32_16x16x4_f32, no 16-bit operand, softmax statistics in fp32 with
+ * the row maximum subtracted and the library's exp.
+ *
+ * For every sequence s < n_seq and head h < heads: O = softmax(Q K^T / sqrt(d) + mask) V over L tokens.  Q, K, V, O
+ * (and dO, dQ, dK, dV) are separate pointers with their own row strides in floats, so they may be column ranges of one
+ * [rows, 3 heads d] projection buffer; head h owns columns [h d, (h + 1) d).  Token t of sequence s is row
+ *     (s / inner) * outer_rows + (s % inner) * inner_rows + t * tok_rows
+ * of every operand: attention over the steps and over the nodes of a [b, s, n, .] tensor read the rows where they lie.
+ * causal = 1: key j is visible to query i iff j <= i.  Only the queries q_first .. L - 1 are computed: the forward
+ * leaves the rows below q_first of O untouched, the backward ignores those rows of dO and writes zeros to those of dQ
+ * (dK, dV cover every key).  lse [n_seq, heads, L] (forward: may be NULL) is the log-sum-exp of a query's scaled
+ * scores; the backward recomputes the probabilities from it.  work: sgp_attention_workspace_bytes (the row sums of
+ * dO * O).  No float atomics: every output tile has one owner and sums run in tile order, so results are bit-identical
+ * from run to run and a sequence computed alone has the bits it has in a batch.
+ *
+ * Domain: d a multiple of 8 in 8 .. 128, heads * d <= 256, L >= 1 (no upper bound: keys are streamed with the online
+ * softmax), n_seq >= 1 with n_seq * heads * ceil(L / 16) < 2^31, 0 <= q_first < L; outside it SGP_EUNSUP with the
+ * reason.  Pointers 16-byte aligned, row strides multiples of 4 (SGP_EINVAL otherwise).
+ * sgp_attention_plan (host only; the entries dispatch on the same answer) fills plan[8]:
+ *   [0] form = channel tiles a wave's registers are built for: 1 (d <= 16), 2 (d <= 32), 4 (d <= 64), 8 (d <= 128)
+ *   [1] ceil(d / 16)   [2] query tiles ceil((L - q_first) / 16)   [3] key tiles ceil(L / 16)   [4] waves per workgroup
+ *   [5] workgroups of the forward and of the dQ pass   [6] workgroups of the dK / dV pass   [7] 0
+ *   replaces F.multi_head_attention_forward's bmm / softmax / bmm called by nn.MultiheadAttention.forward under
+ *   tsl/nn/base/attention/attention.py:131-137 (with the causal mask of lines 14-19 and 125-130 and the rearranges of
+ *   lines 122-123 and 138), and what autograd derives for them */
+int sgp_attention_plan(int32_t L, int32_t d, int32_t heads, int64_t n_seq, int32_t causal, int32_t q_first, int32_t* plan);
+int64_t sgp_attention_workspace_bytes(int32_t L, int32_t heads, int64_t n_seq);
+int sgp_attention_fwd_f32(const float* Q, int64_t q_row_stride, const float* K, int64_t k_row_stride,
+                          const float* V, int64_t v_row_stride, float* O, int64_t o_row_stride, float* lse,
+                          int32_t L, int32_t d, int32_t heads, int64_t n_seq,
+                          int64_t inner, int64_t outer_rows, int64_t inner_rows, int64_t tok_rows,
+                          int32_t causal, int32_t q_first, sgp_stream_t stream);
+int sgp_attention_bwd_f32(const float* dO, int64_t do_row_stride, const float* Q, int64_t q_row_stride,
+                          const float* K, int64_t k_row_stride, const float* V, int64_t v_row_stride,
+                          const float* O, int64_t o_row_stride, const float* lse,
+                          float* dQ, int64_t dq_row_stride, float* dK, int64_t dk_row_stride,
+                          float* dV, int64_t dv_row_stride, void* work, int64_t work_bytes,
+                          int32_t L, int32_t d, int32_t heads, int64_t n_seq,
+                          int64_t inner, int64_t outer_rows, int64_t inner_rows, int64_t tok_rows,
+                          int32_t causal, int32_t q_first, sgp_stream_t stream);
 
 /* -------------------------------------------------------------- Timing -----
  * HIP-event helpers so that Python can time kernels on the stream they were

@@ -408,7 +408,7 @@ int sgp_grouped_linear_dact_f32(const float* dy, int64_t dy_row_stride, const fl
     SGP_REQUIRE(dropout_p >= 0.0 && dropout_p < 1.0, "sgp_grouped_linear_dact_f32: dropout_p must lie in [0, 1)");
     unsigned thresh, k0, k1; float scale;
     set_dropout(thresh, k0, k1, scale, dropout_p, seed);
-    SGP_REQUIRE(n_rows >= 0 && width > 0 && act >= 0 && act <= 2, "sgp_grouped_linear_dact_f32: bad argument");
+    SGP_REQUIRE(n_rows >= 0 && width > 0 && act >= 0 && act <= 3, "sgp_grouped_linear_dact_f32: bad argument");
     if (n_rows == 0) return 0;
     long long grid = (n_rows * width + 255) / 256;
     if (grid > 8192) grid = 8192;

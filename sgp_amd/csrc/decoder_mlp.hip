@@ -261,7 +261,7 @@ int sgp_dense_f32(const float* X, int64_t x_row_stride, const int32_t* gather, i
                   float* out, const int64_t* out_map, sgp_stream_t stream) {
     SGP_REQUIRE(X && w_packed && out && out_map, "sgp_dense_f32: null pointer");
     SGP_REQUIRE(n_rows >= 0 && k > 0 && n_out > 0 && x_row_stride >= k && row_mod >= 0, "sgp_dense_f32: bad size");
-    SGP_REQUIRE(act >= 0 && act <= 2 && n_act >= 0 && n_act <= n_out, "sgp_dense_f32: bad activation");
+    SGP_REQUIRE(act >= 0 && act <= 3 && n_act >= 0 && n_act <= n_out, "sgp_dense_f32: bad activation");
     SGP_REQUIRE(dropout_p >= 0.0 && dropout_p <= 1.0, "sgp_dense_f32: dropout_p must lie in [0, 1]");
     SGP_REQUIRE(!dmode || (dpre && dpre_row_stride >= n_act), "sgp_dense_f32: the backward epilogue needs dpre");
     SGP_REQUIRE(!dmode || !pre, "sgp_dense_f32: pre is a forward output");

@@ -29,12 +29,14 @@ __device__ __forceinline__ float keep_factor(unsigned long long idx, unsigned th
 __device__ __forceinline__ float activate(float v, int act) {
     if (act == 1) return fmaxf(v, 0.f);                                   // relu
     if (act == 2) return v * sgp::sigmoid_f32(v);                        // silu = x * sigmoid(x)
+    if (act == 3) return v > 0.f ? v : sgp::expm1_f32(v);                // elu, alpha = 1
     return v;
 }
 
 __device__ __forceinline__ float dactivate(float z, int act) {
     if (act == 1) return z > 0.f ? 1.f : 0.f;
     if (act == 2) { const float sg = sgp::sigmoid_f32(z); return sg * (1.f + z * (1.f - sg)); }
+    if (act == 3) return z > 0.f ? 1.f : sgp::exp_f32(z);
     return 1.f;
 }
 

@@ -1,11 +1,17 @@
 // Small device helpers with more than one user: the tanh family of the reservoir kernels (also the tanh of the DCRNN,
-// Graph WaveNet and LSTM / GRU cells), the sigmoid of every gate and of silu, and the 16-byte load / store.
+// Graph WaveNet and LSTM / GRU cells), the sigmoid of every gate and of silu, the full-accuracy exponential family of
+// the attention softmax and of ELU, and the 16-byte load / store.
 #pragma once
 #include "common.h"
 
 namespace sgp {
 
 __device__ __forceinline__ float sigmoid_f32(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
+// the library's exp / log / expm1 (about 1 ulp, every range), not the fast hardware approximations: a softmax weight is
+// exp(s - max) with s of any size, and ELU's expm1 has to be relative-accurate near zero
+__device__ __forceinline__ float exp_f32(float v) { return expf(v); }
+__device__ __forceinline__ float log_f32(float v) { return logf(v); }
+__device__ __forceinline__ float expm1_f32(float v) { return expm1f(v); }
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 

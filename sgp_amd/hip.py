@@ -1500,6 +1500,8 @@ def csr_take_rows(a, n_rows, index, rowptr, col, val, nnz, err, ws, phase=None, 
 
 
 GL_ACT_CODES = {None: 0, "linear": 0, "identity": 0, "relu": 1, "silu": 2}
+# sgp_dense_f32 and sgp_grouped_linear_dact_f32 also have ELU (alpha 1); the grouped input layer and the edge kernels do not
+DENSE_ACT_CODES = {**GL_ACT_CODES, "elu": 3}
 
 
 @_on_device
@@ -1561,7 +1563,7 @@ def grouped_linear_dact(dy, pre, activation, dropout_p=0., seed=0):
         raise ValueError(f"pre: expected a contiguous 2-D float32 tensor (the kernel indexes pre and dz flat), got "
                          f"{tuple(pre.shape)} {pre.dtype} strides {pre.stride()}")
     dz = torch.empty_like(pre)
-    _check(lib.sgp_grouped_linear_dact_f32(dy.data_ptr(), dy.stride(0), pre.data_ptr(), GL_ACT_CODES[activation],
+    _check(lib.sgp_grouped_linear_dact_f32(dy.data_ptr(), dy.stride(0), pre.data_ptr(), DENSE_ACT_CODES[activation],
                                            float(dropout_p), int(seed), dz.data_ptr(), pre.shape[0], pre.shape[1],
                                            _stream(dz)), "sgp_grouped_linear_dact_f32")
     return dz
@@ -1689,7 +1691,7 @@ def dense(x, packed, n_out, k, n_rows=None, bias=None, gather=None, row_mod=0, a
     if n_rows is None:
         n_rows = x.shape[0]
     if n_act is None:
-        n_act = n_out if (GL_ACT_CODES[activation] or dpre is not None or dropout_p > 0.) else 0
+        n_act = n_out if (DENSE_ACT_CODES[activation] or dpre is not None or dropout_p > 0.) else 0
     if out is None:
         out = torch.empty(n_rows, n_out, dtype=torch.float32, device=x.device)
     if out_map is None:
@@ -1699,7 +1701,7 @@ def dense(x, packed, n_out, k, n_rows=None, bias=None, gather=None, row_mod=0, a
     pp, prs = _rows2(pre, "pre", n_act) if pre is not None else (None, 0)
     ap, ars = _rows2(add, "add", n_out) if add is not None else (None, 0)
     _check(lib.sgp_dense_f32(xp, xrs, _ptr(gather), int(row_mod), packed.data_ptr(), _ptr(bias), n_rows, k, n_out,
-                             GL_ACT_CODES[activation], n_act, int(dpre is not None), dp, dprs, pp, prs,
+                             DENSE_ACT_CODES[activation], n_act, int(dpre is not None), dp, dprs, pp, prs,
                              float(dropout_p), int(seed), int(n_act if drop_width is None else drop_width),
                              ap, ars, out.data_ptr(), om, _stream(out)), "sgp_dense_f32")
     return out
@@ -2523,6 +2525,82 @@ def gwnet_norm_bwd(dout, z, stats, kind, training, weight=None, eps=1e-5, dropou
                                       _ptr(dw), _ptr(db), R, H, _ptr(work), work.numel() if work is not None else 0,
                                       _stream(dout)), "sgp_gwnet_norm_bwd_f32")
     return dy, dres, dw, db
+
+
+# ---------------------------------------------------------------- attention (attention.hip)
+ATTENTION_FORMS = (1, 2, 4, 8)      # plan["form"]: the channel tiles (16 columns each) a wave's registers are built for
+_ATTENTION_PLAN_KEYS = ("form", "dtiles", "qtiles", "ktiles", "waves", "grid_q", "grid_k", "reserved")
+
+
+def attention_plan(L, d, heads, n_seq, causal=False, q_first=0):
+    """The launch form of the attention entries for these sizes (host only: ``sgp_attention_plan``, on whose answer the
+    entries dispatch) as a dict; ``NotImplementedError`` with the reason outside the domain."""
+    plan = (c_i32 * 8)()
+    _check(load().sgp_attention_plan(int(L), int(d), int(heads), int(n_seq), int(causal), int(q_first), plan),
+           "sgp_attention_plan")
+    return dict(zip(_ATTENTION_PLAN_KEYS, plan))
+
+
+def attention_require(L, d, heads, n_seq, causal=False, q_first=0):
+    """Raise ``NotImplementedError`` with the reason when the attention kernels have no form for these sizes (no GPU
+    needed, before any launch)."""
+    attention_plan(L, d, heads, n_seq, causal, q_first)
+
+
+class TokenMap(tuple):
+    """``(inner, outer_rows, inner_rows, tok_rows)``: token ``t`` of sequence ``q`` is row ``(q // inner) * outer_rows +
+    (q % inner) * inner_rows + t * tok_rows`` of every operand."""
+
+    def __new__(cls, inner, outer_rows, inner_rows, tok_rows):
+        return super().__new__(cls, (int(inner), int(outer_rows), int(inner_rows), int(tok_rows)))
+
+    def last_row(self, n_seq, L):
+        inner, outer, inr, tok = self
+        return ((n_seq - 1) // inner) * outer + ((n_seq - 1) % inner) * inr + (L - 1) * tok
+
+
+def _attn_operand(t, name, E, rows):
+    p, rs = _rows2(t, name, E)
+    if t.shape[0] < rows:
+        raise ValueError(f"{name}: {t.shape[0]} rows, the token map reaches row {rows - 1}")
+    return p, rs
+
+
+@_on_device
+def attention_fwd(q, k, v, out, L, d, heads, n_seq, token_map, causal=False, q_first=0, lse=None):
+    """``out = softmax(q k^T / sqrt(d) + causal mask) v`` per (sequence, head) (sgp_attention_fwd_f32).  ``q, k, v, out``:
+    2-D float32 views ``[rows, heads d]`` (column ranges of a wider buffer are fine); ``lse [n_seq, heads, L]`` is filled
+    when given.  Queries below ``q_first`` are not computed and their rows of ``out`` stay as they are."""
+    lib = require_gpu()
+    attention_require(L, d, heads, n_seq, causal, q_first)
+    E = heads * d
+    rows = TokenMap(*token_map).last_row(n_seq, L) + 1
+    ops = [x for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out")) for x in _attn_operand(t, nm, E, rows)]
+    if lse is not None and (lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != n_seq * heads * L):
+        raise ValueError("lse: expected a contiguous float32 [n_seq, heads, L]")
+    _check(lib.sgp_attention_fwd_f32(*ops, _ptr(lse), L, d, heads, n_seq, *token_map, int(bool(causal)), int(q_first),
+                                     _stream(out)), "sgp_attention_fwd_f32")
+    return out
+
+
+@_on_device
+def attention_bwd(dout, q, k, v, out, lse, dq, dk, dv, L, d, heads, n_seq, token_map, causal=False, q_first=0):
+    """``dq, dk, dv`` of :func:`attention_fwd` from ``dout`` and the forward's operands, ``out`` and ``lse``
+    (sgp_attention_bwd_f32: probabilities recomputed, no atomics).  Rows below ``q_first`` of ``dout`` are not read and
+    those of ``dq`` are written as zeros."""
+    lib = require_gpu()
+    attention_require(L, d, heads, n_seq, causal, q_first)
+    E = heads * d
+    rows = TokenMap(*token_map).last_row(n_seq, L) + 1
+    ins = [x for t, nm in ((dout, "dout"), (q, "q"), (k, "k"), (v, "v"), (out, "out")) for x in _attn_operand(t, nm, E, rows)]
+    outs = [x for t, nm in ((dq, "dq"), (dk, "dk"), (dv, "dv")) for x in _attn_operand(t, nm, E, rows)]
+    if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != n_seq * heads * L:
+        raise ValueError("lse: expected a contiguous float32 [n_seq, heads, L]")
+    nb = lib.sgp_attention_workspace_bytes(L, heads, n_seq)
+    work = torch.empty(nb // 4, dtype=torch.float32, device=dout.device)
+    _check(lib.sgp_attention_bwd_f32(*ins, lse.data_ptr(), *outs, work.data_ptr(), nb, L, d, heads, n_seq, *token_map,
+                                     int(bool(causal)), int(q_first), _stream(dout)), "sgp_attention_bwd_f32")
+    return dq, dk, dv
 
 
 # ---------------------------------------------------------------- graph construction (sgp_amd/connectivity.py)

@@ -7,8 +7,10 @@ from .dcrnn_model import DCRNNModel
 from .grin_model import GRINModel
 from .gwnet_model import GraphWaveNetModel
 from .sgp_online import SGPOnlineModel
+from .transformer_model import TransformerModel
 from ...metrics import masked_mae        # the loss every model trains with lives with the other losses
 
 __all__ = ["SGPInputEncoder", "SGPModel", "OnlineSGPModel", "ESNModel", "masked_mae", "GatedGraphNetwork",
            "GatedGraphNetworkModel", "GatedGraphNetworkMLPModel", "RNNModel", "FCRNNModel", "DCRNNModel",
-           "GraphWaveNetModel", "SGPOnlineModel", "RNNImputerModel", "BiRNNImputerModel", "GRINModel"]
+           "GraphWaveNetModel", "SGPOnlineModel", "RNNImputerModel", "BiRNNImputerModel", "GRINModel",
+           "TransformerModel"]
