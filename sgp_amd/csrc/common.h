@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <atomic>
 #include "../../include/sgp_amd.h"
 
 namespace sgp {
@@ -14,6 +15,23 @@ int fail(int code, const char* fmt, ...);
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail((int)e, "%s: %s", what, hipGetErrorString(e));
+    return 0;
+}
+
+// A launch with more than 48 KB of dynamic LDS needs the kernel's limit raised first; callers enter this only above
+// 48 KB, with `cap` the largest size they ever ask of the kernel.  Done once per kernel and device (the attribute
+// belongs to the device's copy of the function): the state hangs on the kernel itself, a template VALUE, so two
+// instantiations of one signature never share it.  A refusal is reported here, under the caller's name, instead of
+// at the launch that would follow.
+template <auto Kernel>
+int raise_lds_limit(int cap, const char* who) {
+    static std::atomic<bool> done[64];
+    int dev = 0;
+    const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;    // (an unknown device: set every time)
+    if (known && done[dev].load(std::memory_order_relaxed)) return 0;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
+    if (e != hipSuccess) return fail((int)e, "%s: %d bytes of LDS refused: %s", who, cap, hipGetErrorString(e));
+    if (known) done[dev].store(true, std::memory_order_relaxed);
     return 0;
 }
 

@@ -12,32 +12,14 @@
 // IS the B operand of 4 consecutive MFMAs (the same trick as the reservoir kernel).
 #include "common.h"
 #include "decoder_ops.h"
+#include "frag.h"
 
 using sgp::f32x4;
 
 namespace {
 
-// packed weights: Wp[g][jt][kb][lane][s] = W[g*oc + 16 jt + (l & 15)][16 kb + 4 (l >> 4) + s]
-__host__ __device__ inline long long packed_floats(int groups, int ic, int oc) {
-    const long long JT = (oc + 15) / 16, KB = (ic + 15) / 16;
-    return (long long)groups * JT * KB * 256;
-}
-
-__global__ void pack_grouped(const float* __restrict__ w, float* __restrict__ out,
-                             int groups, int ic, int oc) {
-    const int JT = (oc + 15) / 16, KB = (ic + 15) / 16;
-    const long long total = packed_floats(groups, ic, oc);
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const int s = (int)(i & 3), l = (int)((i >> 2) & 63);
-        long long r = i >> 8;
-        const int kb = (int)(r % KB); r /= KB;
-        const int jt = (int)(r % JT);
-        const int g = (int)(r / JT);
-        const int j = 16 * jt + (l & 15), k = 16 * kb + 4 * (l >> 4) + s;
-        out[i] = (j < oc && k < ic) ? w[((long long)g * oc + j) * ic + k] : 0.f;
-    }
-}
+// packed weights: group g's block W[g*oc .. (g+1)*oc, :] of [oc, ic] in the fragment order of frag.h, one group after the other
+inline long long packed_floats(int groups, int ic, int oc) { return groups * sgp::frag_floats(oc, ic); }
 
 // The source of the rows: FMT 0 = fp32, SGP_STORE_BF16 / SGP_STORE_F16 = the 16-bit embedding store.
 // A 16-bit element is widened to fp32 in registers -- exactly, in both formats: bf16 is the upper half of the fp32
@@ -324,10 +306,7 @@ int sgp_grouped_linear_pack_f32(const float* w, float* packed, int32_t groups, i
                                 sgp_stream_t stream) {
     SGP_REQUIRE(w && packed, "sgp_grouped_linear_pack_f32: null pointer");
     SGP_REQUIRE(groups > 0 && ic > 0 && oc > 0, "sgp_grouped_linear_pack_f32: bad size");
-    const long long total = packed_floats(groups, ic, oc);
-    int grid = (int)((total + 255) / 256);
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(pack_grouped, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, packed, groups, ic, oc);
+    for (int g = 0; g < groups; ++g) sgp::frag_pack_to(packed, w + (long long)g * oc * ic, ic, oc, ic, 0, (hipStream_t)stream);
     return sgp::check_launch("pack_grouped");
 }
 

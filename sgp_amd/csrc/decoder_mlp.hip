@@ -14,29 +14,13 @@
 #include "common.h"
 #include "decoder_ops.h"
 #include "dense_tile.h"
+#include "frag.h"
 #include "wg.h"
 
 using sgp::f32x4;
 
 namespace {
 using namespace sgp_dense;
-
-// writes the packed layout described in dense_tile.h
-__global__ void dense_pack(const float* __restrict__ w, long long w_rs, int transpose, int n_out, int k,
-                           float* __restrict__ out) {
-    const int KB = (k + 15) / 16;
-    const long long total = dense_packed_floats(n_out, k);
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const int s = (int)(i & 3), l = (int)((i >> 2) & 63);
-        const long long r = i >> 8;
-        const int kb = (int)(r % KB), jt = (int)(r / KB);
-        const int j = 16 * jt + (l & 15), kk = 16 * kb + 4 * (l >> 4) + s;
-        float v = 0.f;
-        if (j < n_out && kk < k) v = transpose ? w[(long long)kk * w_rs + j] : w[(long long)j * w_rs + kk];
-        out[i] = v;
-    }
-}
 
 // source row of output row r: gidx[r % row_mod] when an index vector is given, r % row_mod without one
 // (row_mod = 0: r itself)
@@ -240,16 +224,16 @@ extern "C" {
 
 int64_t sgp_dense_packed_floats(int32_t n_out, int32_t k) {
     if (n_out <= 0 || k <= 0) return -1;
-    return dense_packed_floats(n_out, k);
+    return sgp::frag_floats(n_out, k);
 }
 
 int sgp_dense_pack_f32(const float* w, int64_t w_row_stride, int32_t transpose, int32_t n_out, int32_t k,
                        float* packed, sgp_stream_t stream) {
     SGP_REQUIRE(w && packed, "sgp_dense_pack_f32: null pointer");
     SGP_REQUIRE(n_out > 0 && k > 0 && w_row_stride > 0, "sgp_dense_pack_f32: bad size");
-    const long long total = dense_packed_floats(n_out, k);
-    hipLaunchKernelGGL(dense_pack, dim3(grid_for(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
-                       w, (long long)w_row_stride, (int)transpose, n_out, k, packed);
+    // M [n_out, k] is w itself, or the transpose of w [k, n_out]
+    if (transpose) sgp::frag_pack_to(packed, w, w_row_stride, k, n_out, 1, (hipStream_t)stream);
+    else sgp::frag_pack_to(packed, w, w_row_stride, n_out, k, 0, (hipStream_t)stream);
     return sgp::check_launch("dense_pack");
 }
 
@@ -268,7 +252,7 @@ int sgp_dense_f32(const float* X, int64_t x_row_stride, const int32_t* gather, i
     SGP_REQUIRE(dropout_p == 0.0 || drop_width >= n_act, "sgp_dense_f32: drop_width below n_act");
     SGP_REQUIRE(out_map[0] > 0 && out_map[3] > 0, "sgp_dense_f32: out_map divisors must be positive");
     SGP_REQUIRE(sgp::aligned16(w_packed), "sgp_dense_f32: packed weights must be 16-byte aligned");
-    SGP_REQUIRE(dense_packed_floats(n_out, k) / 256 <= 0x7fffffffll, "sgp_dense_f32: packed weights too large");
+    SGP_REQUIRE(sgp::frag_floats(n_out, k) / 256 <= 0x7fffffffll, "sgp_dense_f32: packed weights too large");
     if (n_rows == 0) return 0;
     DenseArgs a;
     a.x = X; a.xrs = x_row_stride; a.gidx = gather; a.row_mod = row_mod;

@@ -18,11 +18,7 @@
 namespace sgp_dense {
 using sgp::f32x4;
 
-// packed M[N, K]: Mp[jt][kb][lane][s] = M[16 jt + (l & 15)][16 kb + 4 (l >> 4) + s] (zero outside), the A operand of
-// 4 consecutive MFMAs whose B operand is a lane's 16-byte piece of its row (the layout of decoder.hip).
-__host__ __device__ inline long long dense_packed_floats(int n_out, int k) {
-    return (long long)((n_out + 15) / 16) * ((k + 15) / 16) * 256;
-}
+// The packed M[N, K] (wp below) is in the fragment order of frag.h: sgp_dense_pack_f32, sgp::frag_floats(N, K) floats.
 
 constexpr int DT_KCH = 4;                          // k blocks of 16 per LDS stage
 constexpr int DT_TILES = 4;                        // packed 16-column tiles per workgroup

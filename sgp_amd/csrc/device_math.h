@@ -58,3 +58,13 @@ __device__ __forceinline__ float leak(float h, float v, float alpha, float one_m
 }
 
 }  // namespace sgp_res
+
+namespace sgp {
+
+// the gates of the LSTM / GRU cells, four features of a lane at a time
+__device__ __forceinline__ f32x4 sigmoid4(f32x4 v) { return f32x4{sigmoid_f32(v[0]), sigmoid_f32(v[1]), sigmoid_f32(v[2]), sigmoid_f32(v[3])}; }
+__device__ __forceinline__ f32x4 tanh4(f32x4 v) {
+    return f32x4{sgp_res::tanh_f32(v[0]), sgp_res::tanh_f32(v[1]), sgp_res::tanh_f32(v[2]), sgp_res::tanh_f32(v[3])};
+}
+
+}  // namespace sgp

@@ -484,17 +484,9 @@ int launch_bwd(const GgArgs& a, int n_wg, hipStream_t s) {
     constexpr int SH = 16 * HT + 16;
     constexpr int SK = (16 * KT) % 32 == 16 ? 16 * KT : 16 * KT + 16;
     const int bytes = 64 * (SH + SK) * 4;
-    auto kern = edge_bwd<HT, KT>;
-    static thread_local int opted_in = -1;                           // device that has the LDS opt-in of this instantiation
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (opted_in != dev) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return sgp::fail((int)e, "gated_gn_edge_bwd: LDS opt-in: %s", hipGetErrorString(e));
-        opted_in = dev;
-    }
-    hipLaunchKernelGGL(kern, dim3(n_wg), dim3(64 * GG_WAVES), (size_t)bytes, s, a);
+    if (bytes > 48 * 1024)                                           // an instantiation asks for this one size only
+        if (int rc = sgp::raise_lds_limit<edge_bwd<HT, KT>>(bytes, "gated_gn_edge_bwd")) return rc;
+    hipLaunchKernelGGL((edge_bwd<HT, KT>), dim3(n_wg), dim3(64 * GG_WAVES), (size_t)bytes, s, a);
     return sgp::check_launch("gated_gn_edge_bwd");
 }
 

@@ -13,7 +13,8 @@
 // Mapping: a workgroup of 4 waves owns ONE tile of 16 rows.  Every product is a v_mfma_f32_16x16x4_f32 with the packed
 // weight as the A operand (rows = output features) and the rows' vector, read from LDS, as the B operand; the waves
 // deal the output tiles of 16 features round robin, the products of a chain hand their result to the next through LDS
-// with one barrier in between.  Vectors are zero padded in LDS to whole k-blocks of 16, the packed weights likewise.
+// with one barrier in between.  Vectors are zero padded in LDS to whole k-blocks of 16, the packed weights (fragment
+// order, frag.h) likewise.
 // Arithmetic: exact fp32 products, one k-ordered chain per output starting from the bias, no atomics: every kernel is
 // bit-identical from run to run and independent of the tile a row falls into.  x is only ever selected by the mask,
 // never multiplied: a value at a missing entry is not read into any result.
@@ -21,49 +22,18 @@
 // (r / n) S n + tt n + r % n for row r of step tt; `reverse` makes tt = S - 1 - t.  Everything else is [R, .] of the step.
 // LDS (floats; the budget per kernel is in DESIGN.md 9u): at most 2 * 16 (2 H + 4) + 16 * 20, 34 KB at H = 128.
 #include "common.h"
-#include "device_math.h"
+#include "frag.h"
 #include "wg.h"
 
 namespace {
 using sgp::f32x4;
 using sgp::ld4;
 using sgp::st4;
+using sgp::kPad;
+using sgp::tile_prod;
+using sgp::bias4;
 
-constexpr int kPad = 4;                                     // floats of padding per LDS row (rows stay 16-byte aligned)
 constexpr int kThreads = 256, kWaves = 4;
-
-__device__ __forceinline__ f32x4 mfma4(f32x4 w, f32x4 b, f32x4 acc) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[s], b[s], acc, 0, 0, 0);
-    return acc;
-}
-
-// output tile jt of a packed matrix with KB k-blocks times the lane's LDS row piece `in` (= row + 4 q)
-__device__ __forceinline__ f32x4 tile_prod(const float* wp, int jt, int KB, const float* in, f32x4 acc, int lane) {
-    const float* w = wp + ((long long)jt * KB * 64 + lane) * 4;
-    for (int kb = 0; kb < KB; ++kb) acc = mfma4(ld4(w + (long long)kb * 256), ld4(in + 16 * kb), acc);
-    return acc;
-}
-
-__device__ __forceinline__ f32x4 bias4(const float* b, int col, int n_out) {
-    f32x4 v;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) v[s] = col + s < n_out ? b[col + s] : 0.f;
-    return v;
-}
-
-// ---- packed weights: [T tiles][KB k-blocks][64 lanes][4 s], zero outside [R, C] (the layout of rnn_impute.hip) -------
-__global__ void grin_pack(const float* src, long long ld, int R, int C, int T, int KB, int trans, float* out) {
-    const long long total = (long long)T * KB * 256;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int s = (int)(i & 3), l = (int)((i >> 2) & 63);
-        const long long tk = i >> 8;
-        const int kb = (int)(tk % KB), t = (int)(tk / KB);
-        const int a = 16 * t + (l & 15), k = 16 * kb + 4 * (l >> 4) + s;
-        const int r = trans ? k : a, c = trans ? a : k;
-        out[i] = (r < R && c < C) ? src[(long long)r * ld + c] : 0.f;
-    }
-}
 
 struct Dims {
     int H, C, U, K1, JT, KT;                                // K1 = 2 C + H + U; JT = H / 16; KT = tiles of 16 along K1
@@ -444,13 +414,7 @@ int sgp_grin_pack_f32(const float* w_fs, const float* w_in, const float* w_f, co
     SGP_REQUIRE(sgp::aligned16(packed), "sgp_grin_pack_f32: packed must be 16-byte aligned");
     const Dims d(H, C, U);
     hipStream_t s = (hipStream_t)stream;
-    float* o = packed;
-    auto run = [&](const float* src, int R, int Cc, int trans) {      // src [R, Cc] contiguous
-        const int T = ((trans ? Cc : R) + 15) / 16, KB = ((trans ? R : Cc) + 15) / 16;
-        const long long total = (long long)T * KB * 256;
-        hipLaunchKernelGGL(grin_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, (long long)Cc, R, Cc, T, KB, trans, o);
-        o += total;
-    };
+    auto run = [&](const float* src, int R, int Cc, int trans) { sgp::frag_pack_to(packed, src, Cc, R, Cc, trans, s); };   // src [R, Cc] contiguous
     for (int trans = 0; trans < 2; ++trans) {
         run(w_fs, C, H, trans);
         run(w_in, H, d.K1, trans);

@@ -19,7 +19,7 @@
 // as the B operand (columns = sequences).  h passes between the waves through a double buffer in LDS, the masked
 // prediction (backward: the gate gradients and dp) through a second LDS array; two barriers per step forward, three
 // backward.  h and dh stay in registers from the first step to the last.  Weights are read every step from packed
-// copies in fragment order, zero padded to whole D tiles, resident in L2.
+// copies in fragment order (frag.h), zero padded to whole D tiles, resident in L2.
 // LDS, floats: forward 2 * 16 (H + 4) + 16 (16 DT + 4), at most 66 KB; backward 16 (4 H + 4) + 16 (16 DT + 4), at most
 // 97 KB (H = 256, D = 512) of the CU's 160 KB.
 // Arithmetic: exact fp32 products, fp32 accumulation, one k-ordered chain per output (W_hh blocks, then the feedback
@@ -27,40 +27,10 @@
 // sequence falls into.  `reverse` walks the window from its last step to its first, reading and writing rows at
 // S-1-t: the backward model of BiRNNImputerModel needs no flipped copies.
 #include "common.h"
-#include "device_math.h"
+#include "recurrent.h"
 
 namespace {
-using sgp::f32x4;
-using sgp::sigmoid_f32;
-using sgp::ld4;
-using sgp::st4;
-
-constexpr int kPad = 4;                                     // floats of padding per LDS row (keeps rows 16-byte aligned)
-
-__device__ __forceinline__ f32x4 sigmoid4(f32x4 v) { return f32x4{sigmoid_f32(v[0]), sigmoid_f32(v[1]), sigmoid_f32(v[2]), sigmoid_f32(v[3])}; }
-__device__ __forceinline__ f32x4 tanh4(f32x4 v) {
-    return f32x4{sgp_res::tanh_f32(v[0]), sgp_res::tanh_f32(v[1]), sgp_res::tanh_f32(v[2]), sgp_res::tanh_f32(v[3])};
-}
-__device__ __forceinline__ f32x4 mfma4(f32x4 w, f32x4 b, f32x4 acc) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[s], b[s], acc, 0, 0, 0);
-    return acc;
-}
-
-// ---- packed weights: one matrix in fragment order, [T tiles][KB k-blocks][64 lanes][4 s], zero outside [R, C] -------
-//   plain      A[16 t + (l & 15)][16 kb + 4 (l >> 4) + s] = src[that row][that column]
-//   transposed A[..][..] = src[16 kb + 4 (l >> 4) + s][16 t + (l & 15)]
-__global__ void impute_pack(const float* src, long long ld, int R, int C, int T, int KB, int trans, float* out) {
-    const long long total = (long long)T * KB * 256;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int s = (int)(i & 3), l = (int)((i >> 2) & 63);
-        const long long tk = i >> 8;
-        const int kb = (int)(tk % KB), t = (int)(tk / KB);
-        const int a = 16 * t + (l & 15), k = 16 * kb + 4 * (l >> 4) + s;
-        const int r = trans ? k : a, c = trans ? a : k;
-        out[i] = (r < R && c < C) ? src[(long long)r * ld + c] : 0.f;
-    }
-}
+using namespace sgp;
 
 struct Sizes {                                              // floats of the packed parts of one direction
     long long whh, wx, wr;
@@ -95,28 +65,19 @@ __global__ __launch_bounds__(256) void impute_fwd(ImpArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int H = a.H, JT = H / 16, LDH = H + kPad, D = a.D, DT = (D + 15) / 16, LDD = 16 * DT + kPad;
     float* pbuf = lds + 2 * 16 * LDH;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const int n = lane & 15, q = lane >> 4;
-    const long long m = (long long)blockIdx.x * 16 + n;
-    const bool ok = m < a.M;
-    const long long mc = ok ? m : a.M - 1;                  // lanes past the end compute on a valid row, store nothing
-    const long long xr0 = src_row0(mc, a.inner, a.S);
-    int jt[CT]; bool tv[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        tv[c] = wave * CT + c < JT;                         // wave-uniform
-        jt[c] = tv[c] ? wave * CT + c : JT - 1;
-    }
+    const SeqTile<CT> my(a.M, JT);
+    const int nw = blockDim.x >> 6;
+    const long long xr0 = src_row0(my.mc, a.inner, a.S);
     f32x4 h[CT], bn[CT];
     {
-        const long long row = (long long)(a.reverse ? a.S - 1 : 0) * a.M + mc;
+        const long long row = (long long)(a.reverse ? a.S - 1 : 0) * a.M + my.mc;
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
-            const int col = 16 * jt[c] + 4 * q;
-            h[c] = a.h0 ? ld4(a.h0 + mc * H + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+            const int col = my.col(c);
+            h[c] = a.h0 ? ld4(a.h0 + my.mc * H + col) : f32x4{0.f, 0.f, 0.f, 0.f};
             bn[c] = ld4(a.bhn + col);
-            if (tv[c]) st4(lds + n * LDH + col, h[c]);
-            if (ok && tv[c]) st4(a.hseq + row * H + col, h[c]);
+            if (my.tv[c]) st4(lds + my.n * LDH + col, h[c]);
+            if (my.ok && my.tv[c]) st4(a.hseq + row * H + col, h[c]);
         }
     }
     __syncthreads();
@@ -124,37 +85,33 @@ __global__ __launch_bounds__(256) void impute_fwd(ImpArgs a) {
     for (int t = 0; t < a.S; ++t) {
         const int tt = a.reverse ? a.S - 1 - t : t;
         const long long xrow = xr0 + (long long)tt * a.inner;
-        const float* hb = lds + cur * 16 * LDH + n * LDH + 4 * q;
+        const float* hb = lds + cur * 16 * LDH + my.n * LDH + 4 * my.q;
         // p_t = W_r h_t + b_r, stored; what is fed back goes to LDS with zeros at the observed entries
-        for (int dt = wave; dt < DT; dt += nw) {
-            f32x4 acc;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { const int d = 16 * dt + 4 * q + s; acc[s] = d < D ? a.br[d] : 0.f; }
-            for (int kb = 0; kb < JT; ++kb)
-                acc = mfma4(ld4(a.wr + (((long long)dt * JT + kb) * 64 + lane) * 4), ld4(hb + 16 * kb), acc);
+        for (int dt = my.wave; dt < DT; dt += nw) {
+            const f32x4 acc = tile_prod(a.wr, dt, JT, hb, bias4(a.br, 16 * dt + 4 * my.q, D), my.lane);
             f32x4 pm = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                const int d = 16 * dt + 4 * q + s;
+                const int d = 16 * dt + 4 * my.q + s;
                 if (d < D) {
                     const bool seen = a.msk[xrow * a.ldm + d] != 0.f;
                     pm[s] = seen ? 0.f : acc[s];
-                    if (ok) {
+                    if (my.ok) {
                         a.p[xrow * D + d] = acc[s];
                         if (a.save && !seen && t < a.S - 1) a.xp[xrow * a.ldx + d] = acc[s];
                     }
                 }
             }
-            st4(pbuf + n * LDD + 16 * dt + 4 * q, pm);
+            st4(pbuf + my.n * LDD + 16 * dt + 4 * my.q, pm);
         }
         if (t == a.S - 1) break;                            // uniform: the last step's value is never an input
         __syncthreads();
-        const long long row = (long long)tt * a.M + mc;
+        const long long row = (long long)tt * a.M + my.mc;
         float* grow = a.gates + row * 4 * H;
         f32x4 acc[CT][2], gxn[CT], hn[CT];
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
-            const int col = 16 * jt[c] + 4 * q;
+            const int col = my.col(c);
             acc[c][0] = ld4(grow + col); acc[c][1] = ld4(grow + H + col); gxn[c] = ld4(grow + 2 * H + col);
             hn[c] = bn[c];
         }
@@ -164,35 +121,32 @@ __global__ __launch_bounds__(256) void impute_fwd(ImpArgs a) {
             for (int c = 0; c < CT; ++c) {
 #pragma unroll
                 for (int g = 0; g < 2; ++g)
-                    acc[c][g] = mfma4(ld4(a.whh + (((long long)(g * JT + jt[c]) * JT + kb) * 64 + lane) * 4), b, acc[c][g]);
-                hn[c] = mfma4(ld4(a.whh + (((long long)(2 * JT + jt[c]) * JT + kb) * 64 + lane) * 4), b, hn[c]);
+                    acc[c][g] = mfma4(ld4(a.whh + (((long long)(g * JT + my.jt[c]) * JT + kb) * 64 + my.lane) * 4), b, acc[c][g]);
+                hn[c] = mfma4(ld4(a.whh + (((long long)(2 * JT + my.jt[c]) * JT + kb) * 64 + my.lane) * 4), b, hn[c]);
             }
         }
-        const float* pb = pbuf + n * LDD + 4 * q;
+        const float* pb = pbuf + my.n * LDD + 4 * my.q;
         for (int kb = 0; kb < DT; ++kb) {
             const f32x4 b = ld4(pb + 16 * kb);
 #pragma unroll
             for (int c = 0; c < CT; ++c) {
 #pragma unroll
                 for (int g = 0; g < 2; ++g)
-                    acc[c][g] = mfma4(ld4(a.wx + (((long long)(g * JT + jt[c]) * DT + kb) * 64 + lane) * 4), b, acc[c][g]);
-                gxn[c] = mfma4(ld4(a.wx + (((long long)(2 * JT + jt[c]) * DT + kb) * 64 + lane) * 4), b, gxn[c]);
+                    acc[c][g] = mfma4(ld4(a.wx + (((long long)(g * JT + my.jt[c]) * DT + kb) * 64 + my.lane) * 4), b, acc[c][g]);
+                gxn[c] = mfma4(ld4(a.wx + (((long long)(2 * JT + my.jt[c]) * DT + kb) * 64 + my.lane) * 4), b, gxn[c]);
             }
         }
-        float* hnext = lds + (cur ^ 1) * 16 * LDH + n * LDH;
-        const long long nrow = (long long)(a.reverse ? tt - 1 : tt + 1) * a.M + mc;
+        float* hnext = lds + (cur ^ 1) * 16 * LDH + my.n * LDH;
+        const long long nrow = (long long)(a.reverse ? tt - 1 : tt + 1) * a.M + my.mc;
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
-            const int col = 16 * jt[c] + 4 * q;
-            const bool st = ok && tv[c];
-            const f32x4 r = sigmoid4(acc[c][0]), z = sigmoid4(acc[c][1]);
-            const f32x4 nn = tanh4(gxn[c] + r * hn[c]);
-            h[c] = (1.f - z) * nn + z * h[c];
-            if (a.save && st) {
-                st4(grow + col, r); st4(grow + H + col, z); st4(grow + 2 * H + col, nn); st4(grow + 3 * H + col, hn[c]);
-            }
+            const int col = my.col(c);
+            const bool st = my.ok && my.tv[c];
+            const GruStep gs = gru_step(acc[c][0], acc[c][1], gxn[c], hn[c], h[c]);
+            h[c] = gs.h;
+            if (a.save && st) st_gates(grow, H, col, gs.r, gs.z, gs.n, hn[c]);
             if (st) st4(a.hseq + nrow * H + col, h[c]);
-            if (tv[c]) st4(hnext + col, h[c]);
+            if (my.tv[c]) st4(hnext + col, h[c]);
         }
         __syncthreads();                                    // h_{t+1} is complete; the other buffer and pbuf are free again
         cur ^= 1;
@@ -209,68 +163,54 @@ __global__ __launch_bounds__(256) void impute_bwd(ImpArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int H = a.H, JT = H / 16, LDG = 4 * H + kPad, D = a.D, DT = (D + 15) / 16, LDD = 16 * DT + kPad;
     float* dpbuf = lds + 16 * LDG;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const int n = lane & 15, q = lane >> 4;
-    const long long m = (long long)blockIdx.x * 16 + n;
-    const bool ok = m < a.M;
-    const long long mc = ok ? m : a.M - 1;
-    const long long xr0 = src_row0(mc, a.inner, a.S);
-    int jt[CT]; bool tv[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        tv[c] = wave * CT + c < JT;
-        jt[c] = tv[c] ? wave * CT + c : JT - 1;
-    }
+    const SeqTile<CT> my(a.M, JT);
+    const int nw = blockDim.x >> 6;
+    const long long xr0 = src_row0(my.mc, a.inner, a.S);
     f32x4 dh[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) dh[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float* dgl = lds + n * LDG;
+    float* dgl = lds + my.n * LDG;
     for (int t = a.S - 1; t >= 0; --t) {
         const int tt = a.reverse ? a.S - 1 - t : t;
         const bool last = t == a.S - 1;                     // uniform
-        const long long row = (long long)tt * a.M + mc, xrow = xr0 + (long long)tt * a.inner;
+        const long long row = (long long)tt * a.M + my.mc, xrow = xr0 + (long long)tt * a.inner;
         float* grow = a.gates + row * 4 * H;
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
         f32x4 keep[CT];
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
-            const int col = 16 * jt[c] + 4 * q;
-            const bool st = ok && tv[c];
+            const int col = my.col(c);
+            const bool st = my.ok && my.tv[c];
             if (last) {
                 keep[c] = zero;
-                if (st) { st4(grow + col, zero); st4(grow + H + col, zero); st4(grow + 2 * H + col, zero); st4(grow + 3 * H + col, zero); }
+                if (st) st_gates(grow, H, col, zero, zero, zero, zero);
             } else {
                 const f32x4 r = ld4(grow + col), z = ld4(grow + H + col), nn = ld4(grow + 2 * H + col), hn = ld4(grow + 3 * H + col);
-                const f32x4 hp = ld4(a.hseq + row * H + col);
-                const f32x4 dan = dh[c] * (1.f - z) * (1.f - nn * nn);
-                const f32x4 daz = dh[c] * (hp - nn) * z * (1.f - z);
-                const f32x4 dar = dan * hn * r * (1.f - r), dhn = dan * r;
-                keep[c] = dh[c] * z;
-                if (st) { st4(grow + col, dar); st4(grow + H + col, daz); st4(grow + 2 * H + col, dan); st4(grow + 3 * H + col, dhn); }
-                if (tv[c]) { st4(dgl + col, dar); st4(dgl + H + col, daz); st4(dgl + 2 * H + col, dan); st4(dgl + 3 * H + col, dhn); }
+                const GruStepBwd d = gru_step_bwd(dh[c], r, z, nn, hn, ld4(a.hseq + row * H + col));
+                keep[c] = d.keep;
+                if (st) st_gates(grow, H, col, d.dar, d.daz, d.dan, d.dhn);
+                if (my.tv[c]) st_gates(dgl, H, col, d.dar, d.daz, d.dan, d.dhn);
             }
         }
         if (!last) __syncthreads();
-        for (int dt = wave; dt < DT; dt += nw) {
+        for (int dt = my.wave; dt < DT; dt += nw) {
             f32x4 acc = zero;
-            if (!last)
-                for (int kb = 0; kb < 3 * JT; ++kb)
-                    acc = mfma4(ld4(a.wx + (((long long)dt * 3 * JT + kb) * 64 + lane) * 4), ld4(dgl + 4 * q + 16 * kb), acc);
+            if (!last) acc = tile_prod(a.wx, dt, 3 * JT, dgl + 4 * my.q, acc, my.lane);
             f32x4 dpl = zero;
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                const int d = 16 * dt + 4 * q + s;
+                const int d = 16 * dt + 4 * my.q + s;
                 if (d < D) {
                     const bool seen = a.msk[xrow * a.ldm + d] != 0.f;
                     const float back = (seen || a.detach) ? 0.f : acc[s];
                     dpl[s] = a.dP[xrow * D + d] + back;
-                    if (ok) {
+                    if (my.ok) {
                         a.dp[row * D + d] = dpl[s];
                         if (a.p) a.p[xrow * D + d] = seen ? acc[s] : 0.f;
                     }
                 }
             }
-            st4(dpbuf + n * LDD + 16 * dt + 4 * q, dpl);
+            st4(dpbuf + my.n * LDD + 16 * dt + 4 * my.q, dpl);
         }
         if (t == 0) break;                                  // uniform: nothing is carried past the first step
         __syncthreads();
@@ -279,20 +219,20 @@ __global__ __launch_bounds__(256) void impute_bwd(ImpArgs a) {
         for (int c = 0; c < CT; ++c) acc[c] = keep[c];
         if (!last)
             for (int kb = 0; kb < 3 * JT; ++kb) {
-                const f32x4 b = ld4(dgl + 4 * q + 16 * kb + (kb >= 2 * JT ? H : 0));
+                const f32x4 b = ld4(dgl + 4 * my.q + 16 * kb + (kb >= 2 * JT ? H : 0));
 #pragma unroll
                 for (int c = 0; c < CT; ++c)
-                    acc[c] = mfma4(ld4(a.whh + (((long long)jt[c] * 3 * JT + kb) * 64 + lane) * 4), b, acc[c]);
+                    acc[c] = mfma4(ld4(a.whh + (((long long)my.jt[c] * 3 * JT + kb) * 64 + my.lane) * 4), b, acc[c]);
             }
         for (int kb = 0; kb < DT; ++kb) {
-            const f32x4 b = ld4(dpbuf + n * LDD + 4 * q + 16 * kb);
+            const f32x4 b = ld4(dpbuf + my.n * LDD + 4 * my.q + 16 * kb);
 #pragma unroll
             for (int c = 0; c < CT; ++c)
-                acc[c] = mfma4(ld4(a.wr + (((long long)jt[c] * DT + kb) * 64 + lane) * 4), b, acc[c]);
+                acc[c] = mfma4(ld4(a.wr + (((long long)my.jt[c] * DT + kb) * 64 + my.lane) * 4), b, acc[c]);
         }
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
-            if (a.dH) acc[c] += ld4(a.dH + row * H + 16 * jt[c] + 4 * q);
+            if (a.dH) acc[c] += ld4(a.dH + row * H + my.col(c));
             dh[c] = acc[c];
         }
         __syncthreads();                                    // all reads of this step's gate gradients and dp are done
@@ -304,37 +244,24 @@ const char* domain_error(int H, int D) {
     if (D < 1 || D > 512) return "the fed-back width must be in 1 .. 512";
     return nullptr;
 }
-// column tiles per wave: at most 4 waves; the form with 3 is not instantiated (4 accumulator sets per tile here)
+// column tiles per wave: at most 4 waves.  Unlike rnn_window.hip's ct_of, on purpose: the form with 3 is not
+// instantiated (4 accumulator sets per tile here)
 int ct_of(int H) { const int jt = H / 16; return jt <= 4 ? 1 : (jt <= 8 ? 2 : 4); }
 size_t lds_bytes(bool bwd, int H, int D) {
     const size_t dd = (size_t)16 * (16 * ((D + 15) / 16) + kPad);
     return ((bwd ? (size_t)16 * (4 * H + kPad) : (size_t)2 * 16 * (H + kPad)) + dd) * 4;
 }
 
-// More than 48 KB of LDS needs the limit raised once per instantiation (and device); a refusal is reported here
-// instead of at the launch that would follow.
-template <typename K>
-int raise_lds_limit(K kernel, int* done, size_t shm) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (done[dev]) return 0;
-    const int cap = (int)lds_bytes(true, 256, 512);                    // the largest this file asks for
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e != hipSuccess) return sgp::fail((int)e, "rnn_impute: %zu bytes of LDS refused: %s", shm, hipGetErrorString(e));
-    done[dev] = 1;
-    return 0;
-}
-
 template <int CT>
 int launch_ct(bool bwd, const ImpArgs& a, dim3 grid, dim3 block, size_t shm, hipStream_t s) {
-    static int done_f[64] = {0}, done_b[64] = {0};
+    const int cap = (int)lds_bytes(true, 256, 512);                    // the largest this file asks for
     if (bwd) {
         if (shm > 48 * 1024)
-            if (int rc = raise_lds_limit(impute_bwd<CT>, done_b, shm)) return rc;
+            if (int rc = raise_lds_limit<impute_bwd<CT>>(cap, "rnn_impute")) return rc;
         hipLaunchKernelGGL((impute_bwd<CT>), grid, block, shm, s, a);
     } else {
         if (shm > 48 * 1024)
-            if (int rc = raise_lds_limit(impute_fwd<CT>, done_f, shm)) return rc;
+            if (int rc = raise_lds_limit<impute_fwd<CT>>(cap, "rnn_impute")) return rc;
         hipLaunchKernelGGL((impute_fwd<CT>), grid, block, shm, s, a);
     }
     return 0;
@@ -399,20 +326,11 @@ int sgp_rnn_impute_pack_f32(const float* w_ih, int64_t w_ih_row_stride, const fl
     SGP_REQUIRE(w_ih && w_hh && w_r && packed, "sgp_rnn_impute_pack_f32: null pointer");
     SGP_REQUIRE(w_ih_row_stride >= D, "sgp_rnn_impute_pack_f32: weight_ih rows of %lld floats hold no %d columns", (long long)w_ih_row_stride, D);
     SGP_REQUIRE(sgp::aligned16(packed), "sgp_rnn_impute_pack_f32: packed must be 16-byte aligned");
-    const int JT = H / 16, DT = (D + 15) / 16;
-    hipStream_t s = (hipStream_t)stream;
-    float* o = packed;
-    auto run = [&](const float* src, long long ld, int R, int C, int T, int KB, int trans) {
-        const long long total = (long long)T * KB * 256;
-        hipLaunchKernelGGL(impute_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, ld, R, C, T, KB, trans, o);
-        o += total;
-    };
-    run(w_hh, H, 3 * H, H, 3 * JT, JT, 0);                              // forward: W_hh, W_x, W_r
-    run(w_ih, w_ih_row_stride, 3 * H, D, 3 * JT, DT, 0);
-    run(w_r, H, D, H, DT, JT, 0);
-    run(w_hh, H, 3 * H, H, JT, 3 * JT, 1);                              // backward: their transposes
-    run(w_ih, w_ih_row_stride, 3 * H, D, DT, 3 * JT, 1);
-    run(w_r, H, D, H, JT, DT, 1);
+    for (int trans = 0; trans < 2; ++trans) {                           // forward: W_hh, W_x, W_r; backward: their transposes
+        frag_pack_to(packed, w_hh, H, 3 * H, H, trans, (hipStream_t)stream);
+        frag_pack_to(packed, w_ih, w_ih_row_stride, 3 * H, D, trans, (hipStream_t)stream);
+        frag_pack_to(packed, w_r, H, D, H, trans, (hipStream_t)stream);
+    }
     return sgp::check_launch("sgp_rnn_impute_pack_f32");
 }
 

@@ -18,45 +18,19 @@
 // h (backward: the gate gradients) passes between the waves through LDS, one barrier per step (backward: two); h, c,
 // dh and dc themselves stay in registers from the first step to the last.
 // W_hh (256 KB at H = 128, 1 MB at H = 256) does not fit LDS: it is read every step from a packed copy in fragment
-// order (one coalesced 1 KB read per wave feeds 4 MFMAs), resident in L2 because every workgroup reads the same bytes.
+// order (frag.h), resident in L2 because every workgroup reads the same bytes.
 // Arithmetic: exact fp32 products, fp32 accumulation, one k-ordered chain per output; no atomics anywhere, so forward
 // and backward are bit-identical from run to run and independent of which tile a sequence falls into.
 #include "common.h"
 #include "decoder_ops.h"
-#include "device_math.h"
+#include "recurrent.h"
 
 namespace {
-using sgp::f32x4;
-using sgp::sigmoid_f32;
-using sgp::ld4;
-using sgp::st4;
+using namespace sgp;
 
 constexpr int CELL_LSTM = 0, CELL_GRU = 1;
-constexpr int kPad = 4;                                     // floats of padding per LDS row (keeps rows 16-byte aligned)
 
-__device__ __forceinline__ f32x4 sigmoid4(f32x4 v) { return f32x4{sigmoid_f32(v[0]), sigmoid_f32(v[1]), sigmoid_f32(v[2]), sigmoid_f32(v[3])}; }
-__device__ __forceinline__ f32x4 tanh4(f32x4 v) {
-    return f32x4{sgp_res::tanh_f32(v[0]), sgp_res::tanh_f32(v[1]), sgp_res::tanh_f32(v[2]), sgp_res::tanh_f32(v[3])};
-}
-
-// ---- packed W_hh (floats): forward part, then backward part, G H H each ---------------------------------------
-//   fwd [G JT row tiles][JT kb][64 lanes][4 s] = W_hh[16 rt + (l & 15)][16 kb + 4 (l >> 4) + s]
-//   bwd [JT col tiles][G JT kb][64 lanes][4 s] = W_hh[16 kb + 4 (l >> 4) + s][16 jt + (l & 15)]
-__global__ void rnn_pack(const float* w, int G, int H, float* out) {
-    const long long GHH = (long long)G * H * H;
-    const int JT = H / 16;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * GHH; i += (long long)gridDim.x * blockDim.x) {
-        const bool bwd = i >= GHH;
-        const long long e = bwd ? i - GHH : i;
-        const int s = (int)(e & 3), l = (int)((e >> 2) & 63);
-        const long long tk = e >> 8;
-        const int KB = bwd ? G * JT : JT;
-        const int kb = (int)(tk % KB), t = (int)(tk / KB);
-        const int a = 16 * t + (l & 15), k = 16 * kb + 4 * (l >> 4) + s;
-        out[i] = bwd ? w[(long long)k * H + a] : w[(long long)a * H + k];
-    }
-}
-
+// The packed buffer (frag.h), G H H floats each: W_hh [G H, H] for the forward kernel, then its transpose for the backward one.
 struct RnnArgs {
     float* gates;             // [S][M][4 H]: in the input projection, out (save) what backward reads; backward: dgates in place
     const float* wp;          // packed W_hh (this direction's part)
@@ -77,71 +51,52 @@ __global__ __launch_bounds__(256) void rnn_fwd(RnnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int G = CELL == CELL_LSTM ? 4 : 3;
     const int H = a.H, JT = H / 16, LDH = H + kPad;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = lane & 15, q = lane >> 4;
-    const long long m = (long long)blockIdx.x * 16 + n;
-    const bool ok = m < a.M;
-    const long long mc = ok ? m : a.M - 1;                  // lanes past the end compute on a valid row, store nothing
-    int jt[CT]; bool tv[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        tv[c] = wave * CT + c < JT;                         // wave-uniform
-        jt[c] = tv[c] ? wave * CT + c : JT - 1;
-    }
+    const SeqTile<CT> my(a.M, JT);
     f32x4 h[CT], cst[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) h[c] = cst[c] = f32x4{0.f, 0.f, 0.f, 0.f};
     f32x4 bn[CT];
 #pragma unroll
-    for (int c = 0; c < CT; ++c)
-        bn[c] = (CELL == CELL_GRU && a.bhn) ? ld4(a.bhn + 16 * jt[c] + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < CT; ++c) bn[c] = (CELL == CELL_GRU && a.bhn) ? ld4(a.bhn + my.col(c)) : f32x4{0.f, 0.f, 0.f, 0.f};
     int cur = 0;
     for (int t = 0; t < a.S; ++t) {
-        const long long row = (long long)t * a.M + mc;
+        const long long row = (long long)t * a.M + my.mc;
         float* grow = a.gates + row * 4 * H;
         f32x4 acc[CT][G], gxn[CT];
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
-            const int col = 16 * jt[c] + 4 * q;
 #pragma unroll
-            for (int g = 0; g < G; ++g) acc[c][g] = ld4(grow + g * H + col);
+            for (int g = 0; g < G; ++g) acc[c][g] = ld4(grow + g * H + my.col(c));
             if constexpr (CELL == CELL_GRU) { gxn[c] = acc[c][2]; acc[c][2] = bn[c]; }
         }
         if (t > 0) {
-            const float* hb = lds + cur * 16 * LDH + n * LDH + 4 * q;
+            const float* hb = lds + cur * 16 * LDH + my.n * LDH + 4 * my.q;
             for (int kb = 0; kb < JT; ++kb) {
                 const f32x4 b = ld4(hb + 16 * kb);
 #pragma unroll
                 for (int c = 0; c < CT; ++c)
 #pragma unroll
-                    for (int g = 0; g < G; ++g) {
-                        const f32x4 w = ld4(a.wp + (((long long)(g * JT + jt[c]) * JT + kb) * 64 + lane) * 4);
-#pragma unroll
-                        for (int s = 0; s < 4; ++s)
-                            acc[c][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[s], b[s], acc[c][g], 0, 0, 0);
-                    }
+                    for (int g = 0; g < G; ++g)
+                        acc[c][g] = mfma4(ld4(a.wp + (((long long)(g * JT + my.jt[c]) * JT + kb) * 64 + my.lane) * 4), b, acc[c][g]);
             }
         }
-        float* hnext = lds + (cur ^ 1) * 16 * LDH + n * LDH;
+        float* hnext = lds + (cur ^ 1) * 16 * LDH + my.n * LDH;
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
-            const int col = 16 * jt[c] + 4 * q;
-            const bool st = ok && tv[c];
+            const int col = my.col(c);
+            const bool st = my.ok && my.tv[c];
             if constexpr (CELL == CELL_LSTM) {
                 const f32x4 gi = sigmoid4(acc[c][0]), gf = sigmoid4(acc[c][1]), gg = tanh4(acc[c][2]), go = sigmoid4(acc[c][3]);
                 cst[c] = gf * cst[c] + gi * gg;
                 h[c] = go * tanh4(cst[c]);
                 if (a.save && st) {
-                    st4(grow + col, gi); st4(grow + H + col, gf); st4(grow + 2 * H + col, gg); st4(grow + 3 * H + col, go);
+                    st_gates(grow, H, col, gi, gf, gg, go);
                     st4(a.cseq + row * H + col, cst[c]);
                 }
             } else {
-                const f32x4 r = sigmoid4(acc[c][0]), z = sigmoid4(acc[c][1]), hn = acc[c][2];
-                const f32x4 nn = tanh4(gxn[c] + r * hn);
-                h[c] = (1.f - z) * nn + z * h[c];
-                if (a.save && st) {
-                    st4(grow + col, r); st4(grow + H + col, z); st4(grow + 2 * H + col, nn); st4(grow + 3 * H + col, hn);
-                }
+                const GruStep gs = gru_step(acc[c][0], acc[c][1], gxn[c], acc[c][2], h[c]);
+                h[c] = gs.h;
+                if (a.save && st) st_gates(grow, H, col, gs.r, gs.z, gs.n, acc[c][2]);
             }
             if (st) {
                 if (a.hseq) st4(a.hseq + row * H + col, h[c]);
@@ -153,15 +108,15 @@ __global__ __launch_bounds__(256) void rnn_fwd(RnnArgs a) {
                     st4(a.hdrop + row * H + col, d);
                 }
             }
-            if (tv[c]) st4(hnext + col, h[c]);
+            if (my.tv[c]) st4(hnext + col, h[c]);
         }
         __syncthreads();                                    // h of this step is complete; the other buffer is free again
         cur ^= 1;
     }
-    if (a.hlast && ok) {
+    if (a.hlast && my.ok) {
 #pragma unroll
         for (int c = 0; c < CT; ++c)
-            if (tv[c]) st4(a.hlast + m * H + 16 * jt[c] + 4 * q, h[c]);
+            if (my.tv[c]) st4(a.hlast + my.m * H + my.col(c), h[c]);
     }
 }
 
@@ -174,31 +129,21 @@ __global__ __launch_bounds__(256) void rnn_bwd(RnnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int G = CELL == CELL_LSTM ? 4 : 3;
     const int H = a.H, JT = H / 16, LDG = G * H + kPad, KB = G * JT;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = lane & 15, q = lane >> 4;
-    const long long m = (long long)blockIdx.x * 16 + n;
-    const bool ok = m < a.M;
-    const long long mc = ok ? m : a.M - 1;
-    int jt[CT]; bool tv[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        tv[c] = wave * CT + c < JT;
-        jt[c] = tv[c] ? wave * CT + c : JT - 1;
-    }
+    const SeqTile<CT> my(a.M, JT);
     f32x4 dh[CT], dc[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) dh[c] = dc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float* dgl = lds + n * LDG;
+    float* dgl = lds + my.n * LDG;
     for (int t = a.S - 1; t >= 0; --t) {
-        const long long row = (long long)t * a.M + mc;
+        const long long row = (long long)t * a.M + my.mc;
         float* grow = a.gates + row * 4 * H;
         f32x4 keep[CT];                                     // GRU: dh z, the direct path to dh_{t-1}
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
-            const int col = 16 * jt[c] + 4 * q;
-            const bool st = ok && tv[c];
+            const int col = my.col(c);
+            const bool st = my.ok && my.tv[c];
             if (a.dy_full) dh[c] += ld4(a.dy + row * H + col);
-            else if (t == a.S - 1) dh[c] += ld4(a.dy + mc * H + col);
+            else if (t == a.S - 1) dh[c] += ld4(a.dy + my.mc * H + col);
             const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
             if constexpr (CELL == CELL_LSTM) {
                 const f32x4 gi = ld4(grow + col), gf = ld4(grow + H + col), gg = ld4(grow + 2 * H + col), go = ld4(grow + 3 * H + col);
@@ -209,17 +154,15 @@ __global__ __launch_bounds__(256) void rnn_bwd(RnnArgs a) {
                 const f32x4 dag = dcv * gi * (1.f - gg * gg), dao = dh[c] * tc * go * (1.f - go);
                 dc[c] = dcv * gf;
                 keep[c] = zero;
-                if (st) { st4(grow + col, dai); st4(grow + H + col, daf); st4(grow + 2 * H + col, dag); st4(grow + 3 * H + col, dao); }
-                if (tv[c]) { st4(dgl + col, dai); st4(dgl + H + col, daf); st4(dgl + 2 * H + col, dag); st4(dgl + 3 * H + col, dao); }
+                if (st) st_gates(grow, H, col, dai, daf, dag, dao);
+                if (my.tv[c]) st_gates(dgl, H, col, dai, daf, dag, dao);
             } else {
                 const f32x4 r = ld4(grow + col), z = ld4(grow + H + col), nn = ld4(grow + 2 * H + col), hn = ld4(grow + 3 * H + col);
                 const f32x4 hp = t > 0 ? ld4(a.hseq + (row - a.M) * H + col) : zero;
-                const f32x4 dan = dh[c] * (1.f - z) * (1.f - nn * nn);
-                const f32x4 daz = dh[c] * (hp - nn) * z * (1.f - z);
-                const f32x4 dar = dan * hn * r * (1.f - r), dhn = dan * r;
-                keep[c] = dh[c] * z;
-                if (st) { st4(grow + col, dar); st4(grow + H + col, daz); st4(grow + 2 * H + col, dan); st4(grow + 3 * H + col, dhn); }
-                if (tv[c]) { st4(dgl + col, dar); st4(dgl + H + col, daz); st4(dgl + 2 * H + col, dhn); }
+                const GruStepBwd d = gru_step_bwd(dh[c], r, z, nn, hn, hp);
+                keep[c] = d.keep;
+                if (st) st_gates(grow, H, col, d.dar, d.daz, d.dan, d.dhn);
+                if (my.tv[c]) { st4(dgl + col, d.dar); st4(dgl + H + col, d.daz); st4(dgl + 2 * H + col, d.dhn); }   // the hidden side's three
             }
         }
         if (t == 0) break;                                  // uniform: nothing is carried past the first step
@@ -227,16 +170,12 @@ __global__ __launch_bounds__(256) void rnn_bwd(RnnArgs a) {
         f32x4 acc[CT];
 #pragma unroll
         for (int c = 0; c < CT; ++c) acc[c] = keep[c];
-        const float* gb = dgl + 4 * q;
+        const float* gb = dgl + 4 * my.q;
         for (int kb = 0; kb < KB; ++kb) {
             const f32x4 b = ld4(gb + 16 * kb);
 #pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                const f32x4 w = ld4(a.wp + (((long long)jt[c] * KB + kb) * 64 + lane) * 4);
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[s], b[s], acc[c], 0, 0, 0);
-            }
+            for (int c = 0; c < CT; ++c)
+                acc[c] = mfma4(ld4(a.wp + (((long long)my.jt[c] * KB + kb) * 64 + my.lane) * 4), b, acc[c]);
         }
 #pragma unroll
         for (int c = 0; c < CT; ++c) dh[c] = acc[c];
@@ -249,23 +188,10 @@ const char* domain_error(int cell, int H) {
     if (H < 16 || H > 256 || H % 16) return "hidden size must be a multiple of 16 in 16 .. 256";
     return nullptr;
 }
+// column tiles per wave: at most 4 waves.  (rnn_impute.hip's ct_of differs on purpose: it has no form with 3.)
 int ct_of(int H) { const int jt = H / 16; return jt <= 4 ? 1 : (jt <= 8 ? 2 : (jt <= 12 ? 3 : 4)); }
 
-// The backward kernel of the LSTM at H = 256 needs 64.25 KB of LDS: the limit is raised once per instantiation (and
-// device), and a refusal is reported here instead of at the launch that would follow.
-template <int CELL, int CT>
-int raise_lds_limit(size_t shm) {
-    static int done[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (done[dev]) return 0;
-    const int cap = 16 * (4 * 256 + kPad) * 4;                         // the largest this file asks for
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_bwd<CELL, CT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e != hipSuccess) return sgp::fail((int)e, "rnn_bwd: %zu bytes of LDS refused: %s", shm, hipGetErrorString(e));
-    done[dev] = 1;
-    return 0;
-}
+constexpr int kLdsCap = 16 * (4 * 256 + kPad) * 4;          // the largest this file asks for: the LSTM's backward at H = 256, 64.25 KB
 
 template <int CELL>
 int launch(bool bwd, const RnnArgs& a, hipStream_t s) {
@@ -276,7 +202,7 @@ int launch(bool bwd, const RnnArgs& a, hipStream_t s) {
 #define SGP_RNN_LAUNCH(CT_)                                                                   \
     if (bwd) {                                                                                \
         if (shm > 48 * 1024)                                                                  \
-            if (int rc = raise_lds_limit<CELL, CT_>(shm)) return rc;                          \
+            if (int rc = raise_lds_limit<rnn_bwd<CELL, CT_>>(kLdsCap, "rnn_bwd")) return rc;  \
         hipLaunchKernelGGL((rnn_bwd<CELL, CT_>), grid, block, shm, s, a);                     \
     } else hipLaunchKernelGGL((rnn_fwd<CELL, CT_>), grid, block, shm, s, a)
     switch (ct) {
@@ -322,8 +248,8 @@ int sgp_rnn_window_pack_f32(const float* w_hh, int32_t cell, int32_t H, float* p
     SGP_REQUIRE(w_hh && packed, "sgp_rnn_window_pack_f32: null pointer");
     SGP_REQUIRE(sgp::aligned16(packed), "sgp_rnn_window_pack_f32: packed must be 16-byte aligned");
     const int G = cell == CELL_LSTM ? 4 : 3;
-    const long long total = 2ll * G * H * H;
-    hipLaunchKernelGGL(rnn_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w_hh, G, H, packed);
+    frag_pack_to(packed, w_hh, H, G * H, H, 0, (hipStream_t)stream);
+    frag_pack_to(packed, w_hh, H, G * H, H, 1, (hipStream_t)stream);
     return sgp::check_launch("sgp_rnn_window_pack_f32");
 }
 

@@ -21,6 +21,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from frag_layout import pack_one                                       # (GF.pack_one: the one matrix in fragment order)
 from sgp_amd import hip
 
 JTS = tuple(range(1, 9))
@@ -377,16 +378,6 @@ def meets(got, ref, bnd):
 
 
 # ---------------------------------------------------------------------------------------------------- packed layout
-def pack_one(src, trans):
-    """One matrix [R, C] (numpy) in fragment order ``[T][KB][64][4]``, zero outside: element (t, kb, l, s) is row
-    a = 16 t + l % 16, column k = 16 kb + 4 (l / 16) + s of the matrix (its transpose where ``trans``)."""
-    a = src.T if trans else src
-    T, KB = -(-a.shape[0] // 16), -(-a.shape[1] // 16)
-    m = np.zeros((16 * T, 16 * KB), np.float32)
-    m[:a.shape[0], :a.shape[1]] = a
-    return m.reshape(T, 16, KB, 4, 4).transpose(0, 2, 3, 1, 4).reshape(-1)        # [t, n, kb, q, s] -> [t, kb, q, n, s]
-
-
 def packed_layout(w_fs, w_in, w_f, w_o, w_ro):
     """The whole packed buffer: W_fs, W_in, W_f, W_o, W_ro, then their transposes in the same order (``Dims``)."""
     ws = [np.asarray(w, np.float32) for w in (w_fs, w_in, w_f, w_o, w_ro)]
