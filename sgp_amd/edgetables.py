@@ -49,6 +49,13 @@ def sort_plan(n, E):
     return SortPlan(passes, SORT_TILE, tiles, nbytes)
 
 
+def on_device(edge_index, device):
+    """Whether :func:`default_tables` takes ``edge_index`` as it is: an int32 / int64 ``[2, E]`` tensor on ``device``.
+    The layers' ``plan_for`` send every other list through the torch builds."""
+    return (torch.is_tensor(edge_index) and edge_index.is_cuda and edge_index.device == torch.device(device)
+            and edge_index.dim() == 2 and edge_index.shape[0] == 2 and edge_index.dtype in (torch.int32, torch.int64))
+
+
 def _rows(edge_index, n):
     """``(src, dst)`` of a CUDA int32 / int64 ``edge_index [2, E]`` as contiguous rows (no copy when they are)."""
     if edge_index.dim() != 2 or edge_index.shape[0] != 2:

@@ -3,7 +3,8 @@
 
 * Parameter holders with the reference's module paths, shapes and construction order (so ``torch.manual_seed(s)``
   before a constructor draws the reference's initial values and ``load_state_dict`` of a reference checkpoint works);
-  the holders never compute.
+  the holders never compute.  The holders of the baselines' conditional encoder and MLP decoder, and the functions
+  that run them through this module, are one level up in ``nn/blocks.py``.
 * ``PackCache``: packed copies of parameters on one device, rebuilt when a parameter changed.
 * ``DenseFn`` / ``PositionalFn`` / ``TrunkFn``: the autograd functions over ``hip.dense`` / ``hip.dense_wgrad``, and
   ``linear`` / ``readout``, which call them with named arguments.

@@ -22,6 +22,7 @@ from torch import nn
 from ... import edgetables, hip
 from .. import dense
 from .gated_gn import checked_edge_index
+from .graph_cache import GraphCache
 
 
 class DiffusionPlan:
@@ -73,43 +74,24 @@ def diffusion_plan(edge_index, edge_weight, n):
     return DiffusionPlan(n, _csr(dst, src, wf, n), _csr(src, dst, wb, n), _csr(src, dst, wf, n), _csr(dst, src, wb, n))
 
 
-def _on_device(edge_index, device):
-    """An edge list the device build takes as it is: int32 / int64 ``[2, E]`` already on ``device``."""
-    return (torch.is_tensor(edge_index) and edge_index.is_cuda and edge_index.device == torch.device(device)
-            and edge_index.dim() == 2 and edge_index.shape[0] == 2 and edge_index.dtype in (torch.int32, torch.int64))
+def device_plan(edge_index, edge_weight, n, device):
+    """The :class:`DiffusionPlan` of any edge list, on ``device``: a list that lives there is built on the stream
+    (bit-identical), any other is checked, moved and built by :func:`diffusion_plan`."""
+    if edgetables.on_device(edge_index, device):
+        return edgetables.default_tables().diffusion(edge_index, edge_weight, n)
+    ei = checked_edge_index(edge_index, n).to(device)
+    ew = edge_weight.to(device) if edge_weight is not None else None
+    return diffusion_plan(ei, ew, n)
 
 
-class _PlanCache:
-    """Diffusion plans of the last two graphs (a training and a validation one), keyed by the identity and version of
-    ``edge_index`` and ``edge_weight`` (both kept alive here)."""
-
-    def __init__(self, size=2):
-        self._d, self._size = {}, size
-
-    def get(self, edge_index, edge_weight, n, device):
-        key = (id(edge_index), id(edge_weight) if edge_weight is not None else None, n, str(device))
-        ver = (edge_index._version, edge_weight._version if edge_weight is not None else 0)
-        hit = self._d.get(key)
-        if hit is None or hit[0] is not edge_index or hit[1] is not edge_weight or hit[2] != ver:
-            if _on_device(edge_index, device):                        # built on the stream (DESIGN.md 9j), bit-identical
-                plan = edgetables.default_tables().diffusion(edge_index, edge_weight, n)
-            else:
-                ei = checked_edge_index(edge_index, n).to(device)
-                ew = edge_weight.to(device) if edge_weight is not None else None
-                plan = diffusion_plan(ei, ew, n)
-            if len(self._d) >= self._size:
-                self._d.pop(next(iter(self._d)))
-            hit = (edge_index, edge_weight, ver, plan)
-            self._d[key] = hit
-        return hit[3]
-
-
-_plans = _PlanCache()
+_plans = GraphCache()
 
 
 def plan_for(edge_index, edge_weight, n, device):
-    """The cached :class:`DiffusionPlan` of ``(edge_index, edge_weight)`` over ``n`` nodes on ``device``."""
-    return _plans.get(edge_index, edge_weight, n, device)
+    """The cached :class:`DiffusionPlan` of ``(edge_index, edge_weight)`` over ``n`` nodes on ``device`` (the graph
+    cache of DESIGN.md 9w: the last two graphs, by the tensors' identity and version)."""
+    return _plans.get((edge_index, edge_weight), (n, str(device)),
+                      lambda: device_plan(edge_index, edge_weight, n, device))
 
 
 def n_slots(k, root_weight=True, add_backward=True):

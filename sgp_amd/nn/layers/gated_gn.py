@@ -17,6 +17,7 @@ from torch import nn
 
 from ... import edgetables, hip
 from .. import dense
+from .graph_cache import GraphCache
 
 
 class EdgePlan:
@@ -80,46 +81,23 @@ def checked_edge_index(edge_index, n):
     return edge_index
 
 
-class _PlanCache:
-    """Edge plans of the last two edge lists (a training and a validation graph), keyed by the tensor object (kept
-    alive here) and its version.  A loop that brings a new ``edge_index`` per batch (subgraph sampling) rebuilds the
-    tables per batch and pins at most two stale ones."""
-
-    def __init__(self, size=2):
-        self._d, self._size = {}, size
-
-    def get(self, edge_index, n, device):
-        if edge_index is None:
-            key, ver = ("full", n, str(device)), 0
-        else:
-            key, ver = (id(edge_index), n, str(device)), edge_index._version
-        hit = self._d.get(key)
-        if hit is None or hit[0] is not edge_index or hit[1] != ver:
-            chunk = hip.load().sgp_gated_gn_chunk_edges()
-            if (edge_index is not None and edge_index.is_cuda and edge_index.device == torch.device(device)
-                    and edge_index.dim() == 2 and edge_index.shape[0] == 2
-                    and edge_index.dtype in (torch.int32, torch.int64)):
-                plan = edgetables.default_tables().gated(edge_index, n, chunk)    # on the stream (DESIGN.md 9j), identical
-            else:
-                if edge_index is None:
-                    nodes = torch.arange(n, device=device)
-                    ei = torch.cartesian_prod(nodes, nodes).T
-                else:
-                    ei = checked_edge_index(edge_index, n).to(device)
-                plan = edge_plan(ei, n, chunk)
-            if len(self._d) >= self._size:
-                self._d.pop(next(iter(self._d)))
-            hit = (edge_index, ver, plan)
-            self._d[key] = hit
-        return hit[2]
-
-
-_plans = _PlanCache()
+_plans = GraphCache()
 
 
 def plan_for(edge_index, n, device):
-    """The cached :class:`EdgePlan` of ``edge_index`` (``None``: all ``n^2`` pairs, self pairs included) on ``device``."""
-    return _plans.get(edge_index, n, device)
+    """The cached :class:`EdgePlan` of ``edge_index`` (``None``: all ``n^2`` pairs, self pairs included) on ``device``
+    (the graph cache of DESIGN.md 9w: the last two edge lists, by the tensor's identity and version)."""
+    def build():
+        chunk = hip.load().sgp_gated_gn_chunk_edges()
+        if edgetables.on_device(edge_index, device):                  # on the stream (DESIGN.md 9j), identical
+            return edgetables.default_tables().gated(edge_index, n, chunk)
+        if edge_index is None:
+            nodes = torch.arange(n, device=device)
+            ei = torch.cartesian_prod(nodes, nodes).T
+        else:
+            ei = checked_edge_index(edge_index, n).to(device)
+        return edge_plan(ei, n, chunk)
+    return _plans.get((edge_index,), (n, str(device)), build)
 
 
 def _w1_stacked(w1, fin):

@@ -18,9 +18,7 @@ so nothing can be hoisted over the window as ``layers/dcrnn.py`` does.  Per step
   saved rows.
 
 The cells use the graph as given (self loops are ordinary edges); the decoder's plan has them removed: two cached
-plans per ``(edge_index, edge_weight)``.  Both caches hold the last two graphs (a training and a validation one), keyed
-by the tensors' identity and version, oldest evicted first: a model that alternates among more graphs, such as
-subgraph batches, refilters the edge list and rebuilds both plans on every call.
+plans per ``(edge_index, edge_weight)``, each in a graph cache of its own.
 
 Differences from the reference: ``edge_weight=None`` means unit weights; ``decoder_order > 1``, ``layer_norm=True`` and
 ``dropout > 0`` between stacked cells raise ``NotImplementedError``; ``forward`` takes ``reverse=True`` to walk the
@@ -33,7 +31,8 @@ from torch import nn
 from ... import hip
 from .. import dense
 from .dcrnn import DCRNNCell, merge_grads, split_filters
-from .diff_conv import DiffConv, _PlanCache, hop_adjoint, hop_forward, plan_for
+from .diff_conv import DiffConv, device_plan, hop_adjoint, hop_forward, plan_for
+from .graph_cache import GraphCache
 
 
 class SpatialDecoder(nn.Module):
@@ -61,24 +60,17 @@ class SpatialDecoder(nn.Module):
         raise RuntimeError("this decoder runs inside GRIL's HIP kernels; call the GRIL layer")
 
 
-_dec_graphs = {}
-_dec_plans = _PlanCache()
+_dec_plans = GraphCache()
 
 
 def decoder_plan_for(edge_index, edge_weight, n, device):
     """The cached diffusion plan of the graph with its self loops removed (``grin_cell.py:98``)."""
-    key = (id(edge_index), id(edge_weight) if edge_weight is not None else None)
-    ver = (edge_index._version, edge_weight._version if edge_weight is not None else 0)
-    hit = _dec_graphs.get(key)
-    if hit is None or hit[0] is not edge_index or hit[1] is not edge_weight or hit[2] != ver:
+    def build():
         keep = edge_index[0] != edge_index[1]
         ei = edge_index[:, keep].contiguous()
         ew = edge_weight[keep].contiguous() if edge_weight is not None else None
-        if len(_dec_graphs) >= 2:
-            _dec_graphs.pop(next(iter(_dec_graphs)))
-        hit = (edge_index, edge_weight, ver, ei, ew)
-        _dec_graphs[key] = hit
-    return _dec_plans.get(hit[3], hit[4], n, device)
+        return device_plan(ei, ew, n, device)
+    return _dec_plans.get((edge_index, edge_weight), (n, str(device)), build)
 
 
 def _window_rows(b, S, n, reverse, device):

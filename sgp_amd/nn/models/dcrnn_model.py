@@ -4,17 +4,16 @@ dcrnn`` of the baseline drivers builds).
 ``input_encoder`` (a ``ConditionalBlock`` when ``exog_size > 0``, else a bare ``nn.Linear`` WITHOUT activation -- unlike
 ``RNNModel``, which applies a ReLU there) -> ``DCRNN`` (``sgp_amd.nn.layers.dcrnn``: the diffusion-GRU stack over the
 window) -> ``MLPDecoder`` on the last step's state only (``mlp_decoder.py:48-55``, ``n_layers = 1``, dropout in the
-readout only).  The conditional encoder and the decoder are ``RNNModel``'s (``_ConditionalBlock``, ``_MLPDecoder``,
-``dense.TrunkFn``); every matrix product is a HIP kernel, forward and backward.  Parameters keep the reference's
-module paths, shapes and construction order.
+readout only).  The conditional encoder and the decoder, holders and compute, are the shared blocks of
+``sgp_amd.nn.blocks`` run on this model's holders and pack cache; every matrix product is a HIP kernel, forward and
+backward.  Parameters keep the reference's module paths, shapes and construction order.
 """
 from torch import nn
 
 from ... import hip
-from .. import dense
+from .. import blocks, dense
 from ..encoders._args import opt_list
 from ..layers import dcrnn as _dcrnn_layer
-from .rnn_model import _ACTS, _ConditionalBlock, _MLPDecoder, RNNModel
 
 
 class DCRNNModel(nn.Module):
@@ -24,9 +23,7 @@ class DCRNNModel(nn.Module):
     def __init__(self, input_size, hidden_size, ff_size, output_size, n_layers, exog_size, horizon, activation='relu',
                  dropout=0., kernel_size=2):
         super().__init__()
-        act = activation.lower() if isinstance(activation, str) else activation
-        if act not in _ACTS:
-            raise NotImplementedError(f"activation '{activation}': the HIP kernels have relu, silu and linear")
+        self.activation = blocks.checked_activation(activation)
         if not 0. <= float(dropout) <= 1.:
             raise ValueError(f"dropout probability has to be between 0 and 1, but got {dropout}")
         if n_layers < 1:
@@ -34,29 +31,31 @@ class DCRNNModel(nn.Module):
         self.input_size, self.hidden_size = int(input_size), int(hidden_size)
         self.exog_size = int(exog_size or 0)
         self.output_size, self.horizon = int(output_size), int(horizon)
-        self.ff_size, self.ff_layers, self.ff_dropout = int(ff_size), 1, float(dropout)
-        self.activation = None if act in ('linear', 'identity') else act
+        self.ff_size, self.ff_dropout = int(ff_size), float(dropout)
         if self.exog_size > 0:
-            self.input_encoder = _ConditionalBlock(input_size, exog_size, hidden_size)
+            self.input_encoder = blocks.ConditionalBlock(input_size, exog_size, hidden_size)
         else:
             self.input_encoder = dense.Linear(input_size, hidden_size)
         self.dcrnn = _dcrnn_layer.DCRNN(input_size=hidden_size, hidden_size=hidden_size, n_layers=n_layers,
                                         k=kernel_size)
-        self.readout = _MLPDecoder(hidden_size, ff_size, output_size, horizon, 1)
+        self.readout = blocks.MLPDecoder(hidden_size, ff_size, output_size, horizon, 1)
         self._packs = dense.PackCache()
 
-    # the conditional encoder and the decoder are RNNModel's, run on this model's holders
-    _lin = RNNModel._lin
-    _encode_conditional = RNNModel._encode
-    _decode = RNNModel._decode
-
     def _encode(self, x, u):
-        if self.exog_size > 0:
-            return self._encode_conditional(x, u)
-        if u is not None:
-            raise ValueError("u given, but the model was built with exog_size = 0")
         b, s, n, f = x.shape
-        return self._lin("input", self.input_encoder, x.reshape(b * s * n, f))     # no activation (dcrnn_model.py:47)
+        rows = x.reshape(b * s * n, f)
+        enc = self.input_encoder
+        if self.exog_size == 0:
+            if u is not None:
+                raise ValueError("u given, but the model was built with exog_size = 0")
+            return dense.linear(rows, enc, self._packs.linear("input", enc, rows.device))    # bare (dcrnn_model.py:47)
+        urows, nu = blocks.exog_rows(u, b, s, n, self.exog_size, x.device)
+        return blocks.conditional_encode(enc, self._packs, rows, urows, (b * s, n, nu), self.activation)
+
+    def _decode(self, h, b, n):
+        return blocks.mlp_decode(self.readout.readout[0], self._packs, h, b, n, hidden=self.ff_size,
+                                 horizon=self.horizon, channels=self.output_size, activation=self.activation,
+                                 p=self.ff_dropout if self.training else 0.)
 
     def forward(self, x, edge_index, edge_weight=None, u=None, **kwargs):
         if x.dim() != 4 or x.shape[-1] != self.input_size:

@@ -27,11 +27,10 @@ import torch
 from torch import nn
 
 from ... import hip
-from .. import dense
+from .. import blocks, dense
 from ..encoders._args import opt_list, str_to_bool
 from ..layers import gwnet as G
 from ..layers.diff_conv import DiffConv, plan_for
-from .rnn_model import _MLPDecoder
 
 
 class GraphWaveNetModel(nn.Module):
@@ -80,7 +79,7 @@ class GraphWaveNetModel(nn.Module):
                 dense_sconvs.append(G.SpatialConvOrderK(hidden_size, hidden_size, support_len=1,
                                                         order=spatial_kernel_size, include_self=False, channel_last=True))
         self.dense_sconvs = nn.ModuleList(dense_sconvs)
-        self.readout = nn.Sequential(nn.ReLU(), _MLPDecoder(ff_size, 2 * ff_size, output_size, horizon, 1))
+        self.readout = nn.Sequential(nn.ReLU(), blocks.MLPDecoder(ff_size, 2 * ff_size, output_size, horizon, 1))
         self._packs = dense.PackCache()
 
     def get_learned_adj(self, node_index=None, device=None):
@@ -106,13 +105,8 @@ class GraphWaveNetModel(nn.Module):
         return dense.DenseFn.apply(cat, w, b, None, cat.shape[0], 'relu', 0., 0, packs)
 
     def _decode(self, h, b, n):
-        mlp = self.readout[1].readout[0]
-        lins = [d.layer[0] for d in mlp.mlp] + [mlp.readout]
-        packs = [self._packs.linear(f"ff{i}", lin, h.device) for i, lin in enumerate(lins)]
-        params = [q for lin in lins for q in (lin.weight, lin.bias)]
-        spec = dense.TrunkSpec(resnet=False, n_layers=1, hidden=2 * self.ff_size, activation='relu', p=0.,
-                               horizon=self.horizon, channels=self.output_size, b=b, n=n)
-        return dense.TrunkFn.apply(h, spec, packs, (0,), *params)
+        return blocks.mlp_decode(self.readout[1].readout[0], self._packs, h, b, n, hidden=2 * self.ff_size,
+                                 horizon=self.horizon, channels=self.output_size, activation='relu', p=0.)
 
     def forward(self, x, edge_index, edge_weight=None, u=None, node_index=None, **kwargs):
         if x.dim() != 4 or x.shape[-1] != self.input_size:

@@ -3,51 +3,19 @@
 
 ``input_encoder`` (a ``ConditionalBlock``, ``tsl/nn/blocks/encoders/conditional.py:43-67``, or ``Linear + ReLU``) ->
 ``RNN`` (``sgp_amd.nn.layers.rnn``: LSTM / GRU over the window, last state) -> ``MLPDecoder``
-(``tsl/nn/blocks/decoders/mlp_decoder.py:38-46``: MLP, linear readout, ``'b n (h c) -> b h n c'`` in the store).  Every
-matrix product is a HIP kernel, forward and backward (``sgp_dense_f32`` / ``sgp_dense_wgrad_f32`` through
-``sgp_amd.nn.dense``, ``sgp_rnn_window_fwd_f32`` / ``_bwd_f32`` for the recurrence); torch adds the two branches of the
-conditional block (``u`` is projected once per ``(b, s)`` and broadcast over the nodes by that add) and applies its
-ReLU.  Parameters keep the reference's module paths, shapes and construction order.
+(``tsl/nn/blocks/decoders/mlp_decoder.py:38-46``: MLP, linear readout, ``'b n (h c) -> b h n c'`` in the store).  The
+encoder and the decoder, holders and compute, are the shared blocks of ``sgp_amd.nn.blocks``, run on this model's
+holders and pack cache; this file adds the recurrence and what is RNNModel's own: without ``u`` the encoder is
+``Linear + ReLU`` whatever ``activation``.  Every matrix product is a HIP kernel, forward and backward
+(``sgp_dense_f32`` / ``sgp_dense_wgrad_f32`` through ``sgp_amd.nn.dense``, ``sgp_rnn_window_fwd_f32`` / ``_bwd_f32`` for
+the recurrence).  Parameters keep the reference's module paths, shapes and construction order.
 """
-import torch
 from torch import nn
 
 from ... import hip
-from .. import dense
+from .. import blocks, dense
 from ..encoders._args import opt_list
 from ..layers import rnn as _rnn_layer
-
-
-class _ConditionalBlock(nn.Module):
-    """Parameter holder of tsl ``ConditionalBlock(dropout=0, skip_connection=False)``."""
-
-    def __init__(self, input_size, exog_size, output_size):
-        super().__init__()
-        self.input_affinity = dense.Linear(input_size, output_size)
-        self.condition_affinity = dense.Linear(exog_size, output_size)
-        self.out_inputs_affinity = dense.Linear(output_size, output_size)
-        self.out_cond_affinity = dense.Linear(output_size, output_size, bias=False)
-        self.register_parameter('skip_conn', None)
-
-
-class _MLPReadout(dense.MLP):
-    """tsl ``MLP(output_size=...)``: the Dense layers, then ``readout`` (mlp.py:43-44)."""
-
-    def __init__(self, input_size, hidden_size, output_size, n_layers):
-        super().__init__(input_size, hidden_size, None, n_layers)
-        self.readout = dense.Linear(hidden_size, output_size)
-
-
-class _MLPDecoder(nn.Module):
-    """tsl ``MLPDecoder(receptive_field=1)``: ``readout.0`` is the MLP, ``readout.1`` the Rearrange."""
-
-    def __init__(self, input_size, hidden_size, output_size, horizon, n_layers):
-        super().__init__()
-        self.readout = nn.Sequential(_MLPReadout(input_size, hidden_size, output_size * horizon, n_layers),
-                                     nn.Identity())
-
-
-_ACTS = ('relu', 'silu', 'linear', 'identity')
 
 
 class RNNModel(nn.Module):
@@ -57,9 +25,7 @@ class RNNModel(nn.Module):
     def __init__(self, input_size, hidden_size, output_size, ff_size, exog_size, rec_layers, ff_layers, rec_dropout,
                  ff_dropout, horizon, cell_type='gru', activation='relu'):
         super().__init__()
-        act = activation.lower() if isinstance(activation, str) else activation
-        if act not in _ACTS:
-            raise NotImplementedError(f"activation '{activation}': the HIP kernels have relu, silu and linear")
+        self.activation = blocks.checked_activation(activation)
         for name, v in (("rec_dropout", rec_dropout), ("ff_dropout", ff_dropout)):
             if not 0. <= float(v) <= 1.:
                 raise ValueError(f"{name}: dropout probability has to be between 0 and 1, but got {v}")
@@ -69,20 +35,16 @@ class RNNModel(nn.Module):
         self.exog_size = int(exog_size or 0)
         self.output_size, self.horizon = int(output_size), int(horizon)
         self.ff_size, self.ff_layers, self.ff_dropout = int(ff_size), int(ff_layers), float(ff_dropout)
-        self.activation = None if act in ('linear', 'identity') else act
         if self.exog_size > 0:
-            self.input_encoder = _ConditionalBlock(input_size, exog_size, hidden_size)
+            self.input_encoder = blocks.ConditionalBlock(input_size, exog_size, hidden_size)
         else:
             self.input_encoder = nn.Sequential(dense.Linear(input_size, hidden_size), nn.Identity())
         self.rnn = _rnn_layer.RNN(input_size=hidden_size, hidden_size=hidden_size, n_layers=rec_layers,
                                   dropout=rec_dropout, cell=cell_type)
-        self.readout = _MLPDecoder(hidden_size, ff_size, output_size, horizon, ff_layers)
+        self.readout = blocks.MLPDecoder(hidden_size, ff_size, output_size, horizon, ff_layers)
         self._packs = dense.PackCache()
 
     # -------------------------------------------------------------- pieces
-    def _lin(self, name, lin, rows, activation=None):
-        return dense.linear(rows, lin, self._packs.linear(name, lin, rows.device), activation)
-
     def _encode(self, x, u):
         b, s, n, f = x.shape
         rows = x.reshape(b * s * n, f)
@@ -90,39 +52,15 @@ class RNNModel(nn.Module):
         if self.exog_size == 0:
             if u is not None:
                 raise ValueError("u given, but the model was built with exog_size = 0")
-            return self._lin("input", enc[0], rows, 'relu')           # nn.ReLU whatever `activation` (rnn_model.py:53)
-        if u is None:
-            raise ValueError(f"the model needs u with {self.exog_size} exogenous features")
-        u = u.to(x.device, torch.float32)
-        if u.dim() == 3:
-            u = u[:, :, None]                                          # 'b s f -> b s 1 f'
-        if u.dim() != 4 or u.shape[-1] != self.exog_size or u.shape[:2] != x.shape[:2] or u.shape[2] not in (1, n):
-            raise ValueError(f"u: expected [{b}, {s}, (n,) {self.exog_size}], got {tuple(u.shape)}")
-        nu = u.shape[2]
-        urows = u.contiguous().reshape(b * s * nu, self.exog_size)
-        act = self.activation
-        out = self._lin("in", enc.input_affinity, rows, act)
-        cond = self._lin("cond", enc.condition_affinity, urows, act)  # once per (b, s) when u has no node axis
-        a = self._lin("out_in", enc.out_inputs_affinity, out)
-        c = self._lin("out_cond", enc.out_cond_affinity, cond)
-        z = a.reshape(b * s, n, -1) + c.reshape(b * s, nu, -1)
-        if act == 'relu':
-            z = torch.relu(z)
-        elif act == 'silu':
-            z = torch.nn.functional.silu(z)
-        return z.reshape(b * s * n, -1)
+            lin = enc[0]                                               # nn.ReLU whatever `activation` (rnn_model.py:53)
+            return dense.linear(rows, lin, self._packs.linear("input", lin, rows.device), 'relu')
+        urows, nu = blocks.exog_rows(u, b, s, n, self.exog_size, x.device)
+        return blocks.conditional_encode(enc, self._packs, rows, urows, (b * s, n, nu), self.activation)
 
     def _decode(self, h, b, n):
-        dev = h.device
-        mlp = self.readout.readout[0]
-        lins = [d.layer[0] for d in mlp.mlp] + [mlp.readout]
-        packs = [self._packs.linear(f"ff{i}", lin, dev) for i, lin in enumerate(lins)]
-        params = [q for lin in lins for q in (lin.weight, lin.bias)]
-        p = self.ff_dropout if self.training else 0.
-        seeds = tuple(dense.seed() if p > 0. else 0 for _ in range(self.ff_layers))
-        spec = dense.TrunkSpec(resnet=False, n_layers=self.ff_layers, hidden=self.ff_size, activation=self.activation,
-                               p=p, horizon=self.horizon, channels=self.output_size, b=b, n=n)
-        return dense.TrunkFn.apply(h, spec, packs, seeds, *params)
+        return blocks.mlp_decode(self.readout.readout[0], self._packs, h, b, n, hidden=self.ff_size,
+                                 horizon=self.horizon, channels=self.output_size, activation=self.activation,
+                                 p=self.ff_dropout if self.training else 0.)
 
     def forward(self, x, u=None, **kwargs):
         if x.dim() != 4 or x.shape[-1] != self.input_size:

@@ -13,9 +13,8 @@ import torch
 from torch import nn
 
 from ... import hip
-from .. import dense
+from .. import blocks, dense
 from ..encoders._args import opt_list
-from .rnn_model import _ACTS, _MLPDecoder
 
 
 class SGPOnlineModel(nn.Module):
@@ -28,9 +27,7 @@ class SGPOnlineModel(nn.Module):
     def __init__(self, input_size, n_nodes, hidden_size, output_size, n_layers, window, horizon, k=2,
                  bidirectional=True, dropout=0., activation='relu'):
         super().__init__()
-        act = activation.lower() if isinstance(activation, str) else activation
-        if act not in _ACTS:
-            raise NotImplementedError(f"activation '{activation}': the HIP kernels have relu, silu and linear")
+        self.activation = blocks.checked_activation(activation)
         if not 0. <= float(dropout) <= 1.:
             raise ValueError(f"dropout probability has to be between 0 and 1, but got {dropout}")
         if n_layers < 1 or k < 0:
@@ -39,12 +36,11 @@ class SGPOnlineModel(nn.Module):
         self.hidden_size, self.output_size, self.horizon = int(hidden_size), int(output_size), int(horizon)
         self.n_layers, self.p = int(n_layers), float(dropout)
         self.k, self.bidirectional = int(k), bool(bidirectional)
-        self.activation = None if act in ('linear', 'identity') else act
         n_features = self.input_size * self.window
         self.embedding_size = n_features * (1 + self.k * (int(self.bidirectional) + 1))
         self.mlp = dense.MLP(self.embedding_size, hidden_size, None, n_layers)
         self.node_emb = dense.StaticGraphEmbedding(n_nodes, hidden_size)
-        self.readout = _MLPDecoder(hidden_size, hidden_size, output_size, horizon, 1)
+        self.readout = blocks.MLPDecoder(hidden_size, hidden_size, output_size, horizon, 1)
         self._packs = dense.PackCache()
 
     def check_inputs(self, x, node_index=None):
@@ -75,13 +71,8 @@ class SGPOnlineModel(nn.Module):
         return window_spatial_embedding(x, edge_index, edge_weight, k=self.k, bidirectional=self.bidirectional)
 
     def _decode(self, h, b, n):
-        mlp = self.readout.readout[0]
-        lins = [d.layer[0] for d in mlp.mlp] + [mlp.readout]
-        packs = [self._packs.linear(f"ff{i}", lin, h.device) for i, lin in enumerate(lins)]
-        params = [q for lin in lins for q in (lin.weight, lin.bias)]
-        spec = dense.TrunkSpec(resnet=False, n_layers=1, hidden=self.hidden_size, activation='relu', p=0.,
-                               horizon=self.horizon, channels=self.output_size, b=b, n=n)
-        return dense.TrunkFn.apply(h, spec, packs, (0,), *params)
+        return blocks.mlp_decode(self.readout.readout[0], self._packs, h, b, n, hidden=self.hidden_size,
+                                 horizon=self.horizon, channels=self.output_size, activation='relu', p=0.)
 
     def forward(self, x, edge_index, edge_weight=None, node_index=None, **kwargs):
         self.check_inputs(x, node_index)

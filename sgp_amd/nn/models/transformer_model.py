@@ -14,16 +14,12 @@ layer computes only that step's query and runs everything behind the temporal at
 The reference builds every layer with ``causal=True``, which its attention refuses over the nodes: ``axis='nodes'``
 raises the reference's ``ValueError`` here too (``Transformer(axis='nodes', causal=False)`` is available as a block).
 """
-import torch
 from torch import nn
 
 from ... import hip
-from .. import dense
+from .. import blocks, dense
 from ..encoders._args import opt_list
 from ..layers.attention import ACTIVATIONS, PositionalEncoding, Transformer
-from .rnn_model import _ConditionalBlock, _MLPDecoder
-
-_ACT_FNS = {'elu': nn.functional.elu, 'relu': torch.relu, 'silu': nn.functional.silu}
 
 
 class TransformerModel(nn.Module):
@@ -40,7 +36,7 @@ class TransformerModel(nn.Module):
         self.output_size, self.horizon = int(output_size), int(horizon)
         self.activation, self.p = activation, float(dropout)
         if self.exog_size > 0:
-            self.input_encoder = _ConditionalBlock(input_size, exog_size, hidden_size)
+            self.input_encoder = blocks.ConditionalBlock(input_size, exog_size, hidden_size)
         else:
             self.input_encoder = dense.Linear(input_size, hidden_size)
         self.pe = PositionalEncoding(hidden_size, max_len=100)
@@ -48,13 +44,10 @@ class TransformerModel(nn.Module):
             Transformer(input_size=hidden_size, hidden_size=hidden_size, ff_size=ff_size, n_heads=n_heads,
                         n_layers=n_layers, activation=activation, dropout=dropout, axis=axis),
             nn.Identity())
-        self.readout = _MLPDecoder(hidden_size, ff_size, output_size, horizon, 1).readout
+        self.readout = blocks.MLPDecoder(hidden_size, ff_size, output_size, horizon, 1).readout
         self._packs = dense.PackCache()
 
     # -------------------------------------------------------------- pieces
-    def _lin(self, name, lin, rows, activation=None):
-        return dense.linear(rows, lin, self._packs.linear(name, lin, rows.device), activation)
-
     def _encode(self, x, u):
         b, s, n, f = x.shape
         rows = x.reshape(b * s * n, f)
@@ -62,34 +55,13 @@ class TransformerModel(nn.Module):
         if self.exog_size == 0:
             if u is not None:
                 raise ValueError("u given, but the model was built with exog_size = 0")
-            return self._lin("input", enc, rows)
-        if u is None:
-            raise ValueError(f"the model needs u with {self.exog_size} exogenous features")
-        u = u.to(x.device, torch.float32)
-        if u.dim() == 3:
-            u = u[:, :, None]                                          # 'b s f -> b s 1 f'
-        if u.dim() != 4 or u.shape[-1] != self.exog_size or u.shape[:2] != x.shape[:2] or u.shape[2] not in (1, n):
-            raise ValueError(f"u: expected [{b}, {s}, (n,) {self.exog_size}], got {tuple(u.shape)}")
-        nu = u.shape[2]
-        urows = u.contiguous().reshape(b * s * nu, self.exog_size)
-        act = self.activation
-        out = self._lin("in", enc.input_affinity, rows, act)
-        cond = self._lin("cond", enc.condition_affinity, urows, act)  # once per (b, s) when u has no node axis
-        a = self._lin("out_in", enc.out_inputs_affinity, out)
-        c = self._lin("out_cond", enc.out_cond_affinity, cond)
-        z = _ACT_FNS[act](a.reshape(b * s, n, -1) + c.reshape(b * s, nu, -1))
-        return z.reshape(b * s * n, -1)
+            return dense.linear(rows, enc, self._packs.linear("input", enc, rows.device))
+        urows, nu = blocks.exog_rows(u, b, s, n, self.exog_size, x.device)
+        return blocks.conditional_encode(enc, self._packs, rows, urows, (b * s, n, nu), self.activation)
 
-    def _decode(self, h, b, n):
-        dev = h.device
-        mlp = self.readout[0]
-        lins = [d.layer[0] for d in mlp.mlp] + [mlp.readout]
-        packs = [self._packs.linear(f"ff{i}", lin, dev) for i, lin in enumerate(lins)]
-        params = [q for lin in lins for q in (lin.weight, lin.bias)]
-        p = self.p if self.training else 0.
-        spec = dense.TrunkSpec(resnet=False, n_layers=1, hidden=self.ff_size, activation='relu', p=p,
-                               horizon=self.horizon, channels=self.output_size, b=b, n=n)
-        return dense.TrunkFn.apply(h, spec, packs, (dense.seed() if p > 0. else 0,), *params)
+    def _decode(self, h, b, n):                                        # tsl MLP: relu whatever `activation`
+        return blocks.mlp_decode(self.readout[0], self._packs, h, b, n, hidden=self.ff_size, horizon=self.horizon,
+                                 channels=self.output_size, activation='relu', p=self.p if self.training else 0.)
 
     def forward(self, x, u=None, **kwargs):
         if x.dim() != 4 or x.shape[-1] != self.input_size:

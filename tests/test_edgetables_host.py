@@ -68,8 +68,8 @@ def test_cpu_edge_lists_keep_the_torch_build():
     """plan_for sends only device-resident lists to the device build: a CPU list still goes through the torch functions
     (and then needs the GPU only for the copy, which this box does not have)."""
     from sgp_amd.nn.layers import diff_conv
-    assert not diff_conv._on_device(torch.tensor([[0, 1], [1, 2]]), "cuda:0")
-    assert not diff_conv._on_device(None, "cuda:0")
+    assert not ET.on_device(torch.tensor([[0, 1], [1, 2]]), "cuda:0")
+    assert not ET.on_device(None, "cuda:0")
     p = diff_conv.DiffusionPlan(3, *([(torch.tensor([0, 1, 2, 2], dtype=torch.int32), torch.zeros(2, dtype=torch.int32),
                                         torch.zeros(2))] * 4))
     assert p.n_edges == 2
